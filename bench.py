@@ -10,6 +10,11 @@ output Linear -> CTC loss+grad -> BPTT -> [RCCL all-reduce of the flat gradient]
 clip_by_global_norm + Adam.  Dropout keep (0.8, 0.5) as the reference trains.  Weak scaling:
 every rank processes its own batch of 32 ten-second utterances (BASELINE.json configs[1]).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line (headline + roofline of the timed run).  --full adds
+the other measurements: CPU baselines, the model-only / ragged / bucketed / drop-in / RCCL extras, configs[2] and the
+bf16 modes in child processes, the split-precision alt line, and the ragged section of a multi-rank job.
+--dump-outputs DIR writes what the last timed step computed (loss, logits, parameters, gradients) as float32 .npy files.
 """
 import argparse
 import json
@@ -198,6 +203,22 @@ def kernel_src_sha16():
     return h.hexdigest()[:16]
 
 
+DUMP_MAX_VALUES = 1 << 22          # per array (16 MB of float32): logits, parameters, gradients and the B losses stay under 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array.  An array of more than DUMP_MAX_VALUES values is written as
+    a sample of its flattened values at sorted indices drawn with a fixed seed, so two runs or two builds compare entry
+    for entry."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_VALUES:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=DUMP_MAX_VALUES, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     global L, H, D, B, T, MODE
     ap = argparse.ArgumentParser()
@@ -213,13 +234,19 @@ def main():
     ap.add_argument("--sync-each-step", action="store_true",
                     help="counter (rocprofv3 --pmc) passes only: bound the number of outstanding dispatches; the "
                          "profiler's queue interceptor faults once several thousand are in flight. Never for timing.")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra measurements (model-only, ragged lengths, drop-in API)")
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the extra measurements (model-only, ragged lengths, drop-in API)")
     ap.add_argument("--ragged", action="store_true",
                     help="also time RAGGED mini-batches (lengths ~U[600, T]) dealt by dataparallel.shard_bucketed (global length "
-                         "buckets) and by rank-local buckets: multi_gpu.ragged.  On by default in a multi-rank job")
-    ap.add_argument("--no-ragged", action="store_true", help="multi-rank job: skip multi_gpu.ragged")
+                         "buckets) and by rank-local buckets: multi_gpu.ragged.  On with --full in a multi-rank job")
+    ap.add_argument("--no-ragged", action="store_true", help="multi-rank job with --full: skip multi_gpu.ragged")
     ap.add_argument("--alt-bf16x3", action="store_true",
-                    help="also time the opt-in split-precision mode (on by default at cfg2 on one GPU unless --no-alt)")
+                    help="also time the opt-in split-precision mode (on with --full at cfg2 on one GPU unless --no-alt)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run the other measurements: cpu_baseline (unless --no-cpu-baseline), extras incl. "
+                         "configs[2] and the bf16 modes (unless --no-alt), alt_bf16x3, and multi_gpu.ragged in a multi-rank job")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write the last timed step's loss, logits, parameters and gradients to "
+                         "DIR/<name>.npy (float32; rank 0's; arrays over %d values as a fixed seeded sample)" % DUMP_MAX_VALUES)
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     L, H, D, B, T, MODE = cfg["L"], cfg["H"], cfg["D"], cfg["B"], cfg["T"], cfg["mode"]
@@ -280,6 +307,12 @@ def main():
     grp = dataparallel.current()                   # world > 1: RCCL communicator behind the C ABI + gloo host channel
     BIDIR = bool(cfg.get("bidirectional", False))
     eng = Engine(L, H, D, C, B, T, U, seed=1234, precision=args.precision, bidirectional=BIDIR)   # same seed on every rank
+    # Every warm-up and timed step starts from these seeded parameters (Adam's moments and step count carry on), so what the
+    # steps compute repeats from run to run.  With the parameters chained it would not: the f32 atomics of the gradient sums
+    # round in arrival order, Adam turns such a difference in a near-zero gradient into a full-size update, and every later
+    # step starts from it.  (One 25 MB device copy per step at cfg2.)
+    params0 = eng.params.clone()
+    torch.cuda.synchronize()        # (the snapshot is taken on the default stream; the steps run on eng.stream)
     # the whole job runs on a real (non-NULL) stream (see Engine.on_stream)
     torch.cuda.set_stream(eng.stream)
     n = SR * SECONDS
@@ -315,6 +348,7 @@ def main():
 
     def step(i, e=None):
         e = eng if e is None else e
+        e.params.copy_(params0)          # (the bf16x3 engine of the alt line starts from the same seeded parameters)
         if args.no_frontend:
             x, hook = feat, None
         else:
@@ -395,6 +429,8 @@ def main():
         elapsed = float(tt[0])
     loss = float(eng.loss.mean().cpu())
     eng.check()          # the dataflow kernels' bounded waits: a time-out would have left an error flag
+    if args.dump_outputs and rank == 0:      # (before anything below runs the engine again)
+        dump_outputs(args.dump_outputs, {"loss": eng.loss, "logits": eng.logits, "params": eng.params, "grads": eng.grads})
 
     # Real data is ragged.  The headline above times equal-length utterances (BASELINE's 10 s clips); this section times the same
     # step on mini-batches whose lengths are ~U[600, T], dealt to the ranks in the two ways a data-parallel job can deal them:
@@ -406,7 +442,7 @@ def main():
     # utterance per step, and the drop-in step with the reference's beam decoder on host threads (host cores busy per rank).
     # (size ordering in the reference: /root/reference/models/SpeechRecognizer.py:58-99; global padding: AcousticModel.py:825-827)
     ragged_dp = None
-    if (args.ragged or (world > 1 and not args.no_ragged)) and not args.no_frontend:
+    if (args.ragged or (args.full and world > 1 and not args.no_ragged)) and not args.no_frontend:
         pool_n = N_ROTATE * B * world
         pool = np.random.RandomState(77).randint(600, T + 1, size=pool_n)
         items = [[j, None, float(pool[j])] for j in range(pool_n)]
@@ -481,7 +517,7 @@ def main():
     # front end excluded, a batch with ragged lengths ~U[600,T] (masking + early stop at the longest), and the
     # drop-in API path (AcousticModel.run_train_step from raw host signals)
     extras = None
-    if world == 1 and not args.no_alt and not args.no_frontend:
+    if args.full and world == 1 and not args.no_alt and not args.no_frontend:
         def timed(fn):
             for i in range(args.warmup):
                 fn(i)
@@ -594,7 +630,7 @@ def main():
         extras["dropin_run_train_step_beam"] = dropin_run_train_step(max(8, min(args.steps, 20)), train_decoder="beam")
         torch.cuda.set_stream(eng.stream)
 
-    # BASELINE configs[2] (5x1024, 120-dim fbank + deltas, batch 64) in the same default run, so that it is driver-measured:
+    # BASELINE configs[2] (5x1024, 120-dim fbank + deltas, batch 64) in the same --full run, so that it is driver-measured:
     # a child process runs this script with --config cfg3 for 3 steps (this process idles meanwhile) and its line is embedded
     if extras is not None and args.config == "cfg2" and os.environ.get("AMDSPEECH_BENCH_CFG3", "1") != "0":
         import subprocess
@@ -627,7 +663,7 @@ def main():
 
     # separately reported: the opt-in split-precision mode (NOT the headline)
     alt = None
-    if args.precision == "f32" and (args.alt_bf16x3 or (world == 1 and not args.no_alt and args.config == "cfg2")):
+    if args.precision == "f32" and (args.alt_bf16x3 or (args.full and world == 1 and not args.no_alt and args.config == "cfg2")):
         eng3 = Engine(L, H, D, C, B, T, U, seed=1234, precision="bf16x3", bidirectional=BIDIR)
         ref_logits = Engine(L, H, D, C, B, T, U, seed=1234, bidirectional=BIDIR).forward(feat, lengths).clone()
         diff = float(((eng3.forward(feat, lengths) - ref_logits).abs().max() / ref_logits.abs().max()).cpu())
@@ -739,7 +775,7 @@ def main():
             out["alt_bf16x3"] = alt
         if args.precision != "f32":
             out["dtype"] = "f32 storage, %s MFMA products (opt-in mode)" % args.precision
-        if not args.no_cpu_baseline and world == 1 and not BIDIR:      # (the CPU restatements timed here are unidirectional)
+        if args.full and not args.no_cpu_baseline and world == 1 and not BIDIR:      # (the CPU restatements timed here are unidirectional)
             # bounded sample: ~10-30 s of CPU work whatever the configuration
             t_s = T if args.config == "cfg2" else 120
             a, b = cpu_baseline(t_s), cpu_baseline_torch(t_s)

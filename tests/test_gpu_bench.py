@@ -1,4 +1,5 @@
-"""bench.py's contract: the single-GPU line carries `roofline` and `cpu_baseline`-shaped objects, and the multi-rank line the
+"""bench.py's contract: a plain single-GPU line carries the headline and `roofline` only (and --dump-outputs writes the last
+timed step's arrays), the --full line adds `extras` and `cpu_baseline`-shaped objects, and the multi-rank line the
 diagnostics a disappointing 8-GPU run would have to be explained with (rehearsed here with two ranks time-slicing this box's
 one GPU over gloo -- the 8-GPU run itself is the driver's)."""
 import json
@@ -6,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +27,7 @@ def test_two_rank_rehearsal_reports_channel_ranks_allreduce_and_rank_spread():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(AMDSPEECH_BENCH_SHARE_GPU="1", AMDSPEECH_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-alt"],
+                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-alt", "--full"],
                          env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = _last_json(out.stdout)
@@ -73,8 +75,8 @@ def test_single_gpu_ragged_section():
 
 
 def test_single_gpu_line_shape_and_cfg3_extra():
-    """The default command's line (short): roofline + extras incl. configs[2] timed by a child process."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    """The --full command's line (short): roofline + extras incl. configs[2] timed by a child process."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = _last_json(out.stdout)
@@ -97,3 +99,40 @@ def test_single_gpu_line_shape_and_cfg3_extra():
     assert "error" not in b3 and "error" not in b5, (b3, b5)
     assert "bf16 MFMA" in b3["dtype"] and "bf16x3" not in b3["dtype"] and b3["ms_per_step"] < a3["ms_per_step"] < c3["ms_per_step"]
     assert b5["ms_per_step"] < a5["ms_per_step"] and line["dtype"] == "f32"
+
+
+def test_plain_line_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """The plain command times the steps and prints the headline (no extras, baselines or alt lines); --dump-outputs writes the
+    last timed step's loss, logits, parameters and gradients as float32 .npy files, 64 MB at most in all."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    line = _last_json(out.stdout)
+    assert line["metric"] == "audio_frames_per_sec_train_3x512_lstm_ctc" and line["unit"] == "frames/s" and line["dtype"] == "f32"
+    assert line["higher_is_better"] is True and line["steps"] == 2 and line["warmup"] == 1
+    assert abs(line["value"] - 32 * 1001 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert not {"extras", "cpu_baseline", "cpu_baseline_other", "alt_bf16x3", "ragged", "multi_gpu"} & set(line)
+    got = {f: np.load(os.path.join(str(tmp_path), f)) for f in sorted(os.listdir(str(tmp_path)))}
+    assert sorted(got) == ["grads.npy", "logits.npy", "loss.npy", "params.npy"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(os.path.getsize(os.path.join(str(tmp_path), f)) for f in got) <= 64 << 20
+    assert got["loss.npy"].shape == (32,) and got["logits.npy"].shape == (1001, 32, 80)
+    assert abs(float(got["loss.npy"].mean()) - line["config"]["mean_ctc_loss"]) < 1e-5 * abs(line["config"]["mean_ctc_loss"])
+    assert got["params.npy"].shape == got["grads.npy"].shape == (1 << 22,) and np.abs(got["grads.npy"]).max() > 0
+
+
+def test_two_plain_runs_dump_the_same_outputs(tmp_path):
+    """Same arguments, same inputs, same results: every step starts from the seeded parameters, so two runs' last steps agree
+    to rounding -- the forward outputs to 1e-6 of their largest value, the gradients (f32 atomics, summed in arrival order) and
+    the parameters Adam made of them within test_gpu_fullsize's bound for one repeated step, 1e-5."""
+    dumps = []
+    for k in range(2):
+        d = str(tmp_path / ("run%d" % k))
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", d], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+        dumps.append({n: np.load(os.path.join(d, n + ".npy")) for n in ("loss", "logits", "params", "grads")})
+    a, b = dumps
+    for name, tol in (("loss", 1e-6), ("logits", 1e-6), ("grads", 1e-5), ("params", 1e-5)):
+        scale = float(np.abs(a[name]).max())
+        assert scale > 0 and float(np.abs(a[name] - b[name]).max()) <= tol * scale, (name, float(np.abs(a[name] - b[name]).max()), scale)

@@ -62,5 +62,5 @@ for k, d in sorted(red.items()):
     if "lstm" in k and isinstance(d, dict):
         print(k, {c: (v if isinstance(v, float) else v["median"]) for c, v in d.items()})
 EOF
-timeout 900 python $ROOT/bench.py --config $CFG 2> "$OUT/bench.log" | grep '^{' | tail -1 > "$OUT/bench_line.json"
+timeout 900 python $ROOT/bench.py --config $CFG --full 2> "$OUT/bench.log" | grep '^{' | tail -1 > "$OUT/bench_line.json"
 cut -c1-600 "$OUT/bench_line.json"
