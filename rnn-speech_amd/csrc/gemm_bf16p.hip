@@ -280,11 +280,12 @@ int bf16p_transpose(hipStream_t s, const unsigned short* src, long rows, int col
     AS_CHECK_LAUNCH();
     return AMDSPEECH_OK;
 }
+constexpr int SPLIT_TILES_MAX = 256;      // bf16p_splits never makes more partial tiles than this, whatever the shape
 static int bf16p_splits(int M, int N, int K) {
     const int tiles = ceil_div(M, BM) * ceil_div(N, BN), nkt = K / BKT;
     int splits = 1;
     if (tiles < 192 && nkt >= 64) {
-        splits = 256 / tiles;
+        splits = SPLIT_TILES_MAX / tiles;
         if (splits > 8) splits = 8;
         if (splits < 1) splits = 1;
     }
@@ -295,6 +296,7 @@ size_t bf16p_partial_bytes(int M, int N, int K) {
     const int splits = bf16p_splits(M, N, K);
     return splits > 1 ? (size_t)splits * ceil_div(M, BM) * ceil_div(N, BN) * BM * BN * sizeof(float) : 0;
 }
+size_t bf16p_partial_bytes_max() { return (size_t)SPLIT_TILES_MAX * BM * BN * sizeof(float); }
 // C[M][N] (+)= Ak[M][K] . Bk[N][K]^T (+ bias), both operands bf16 with k contiguous (lda, ldb in elements, multiples of 8)
 int bf16p_gemm(hipStream_t s, int M, int N, int K, const unsigned short* Ak, long lda, const unsigned short* Bk, long ldb, float* C, long ldc,
                const float* bias, bool accumulate, void* partial, size_t partial_bytes) {

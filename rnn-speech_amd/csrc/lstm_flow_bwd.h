@@ -51,7 +51,7 @@ struct FlowBwdArgs {
 template <int H>
 __device__ void bwd_gemm_worker(const FlowBwdArgs& a, float* smem, int worker, int nworkers, unsigned long long t_begin) {
     const int T = a.T, B = a.B, L = a.L;
-    // w_mode (dev, AMDSPEECH_FLOW_WORKER_MODE): 1 = only the first team of a workgroup computes (one wave per SIMD), 2 = nobody
+    // w_mode (0 from the host; a power / clock experiment edits it): 1 = only the first team of a workgroup computes (one wave per SIMD), 2 = nobody
     // does (the gates are still watched; gradients are then WRONG -- for power / clock experiments only)
     const bool active = a.w_mode == 0 || (a.w_mode == 1 && (threadIdx.x >> 8) == 0);
     const int team = a.w_mode == 1 ? worker : worker * 2 + (threadIdx.x >> 8), nteams = a.w_mode == 1 ? nworkers : nworkers * 2;
@@ -204,6 +204,10 @@ __device__ void bwd_gemm_worker(const FlowBwdArgs& a, float* smem, int worker, i
 #endif
 
 
+// Q of lstm_bwd_flow2<NTW, PR>: the workgroups that share a K slice (the kernel, and the host's LDS sizing: (Q - 1) partner tiles)
+constexpr int flow2_q(int ntw, int pr) {
+    return pr != 0 ? 1 : (ntw % FLOW2_Q == 0 ? FLOW2_Q : (ntw % 2 == 0 && FLOW2_Q > 1 ? 2 : 1));      // 4 at H = 512, 2 at H = 256 (FLOW2_Q = 4)
+}
 template <int NTW, int PR, bool CF = false>     // 16-column N tiles (and gathered producer tiles) per wave: H/16/8 = H/128; PR: 0 f32, 1 bf16x3, 2 bf16;
                                                 // CF: the instantiation with the fused CTC head's leader (see lstm_fwd_flow2)
 __global__ __launch_bounds__(512) void lstm_bwd_flow2(FlowBwdArgs a_in) {
@@ -226,7 +230,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_flow2(FlowBwdArgs a_in) {
     // NU/2 KiB out and in.  Ordering of the un-polled loads of the down product: a workgroup stores P[t] only after it has seen its
     // partner's tile X[t], which the partner stored behind ITS B1(t) -- so P[t] from one workgroup of every pair still implies that
     // the rows and Q tiles of ALL workgroups of step t+2 / t+1 have reached the L2 (see "The down product").
-    constexpr int Q = PR != 0 ? 1 : (NTW % FLOW2_Q == 0 ? FLOW2_Q : (NTW % 2 == 0 && FLOW2_Q > 1 ? 2 : 1));      // 4 at H = 512, 2 at H = 256 (FLOW2_Q = 4)
+    constexpr int Q = flow2_q(NTW, PR);
     constexpr int NP = NTW / Q;                                                               // partial tiles a wave stores and gathers per step
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* a_lds = smem;                                                                      // [2 (step parity)][4 m][4 kq][16 i][4 g]: dG tiles as MFMA A fragments

@@ -12,7 +12,7 @@ struct FwdArgs {
     int hoist, l0;   // hoist != 0: ONE layer (l0) per launch at frame t = d; the x half of the product was done by a GEMM
                      // whose result (bias included) waits in gates[l][t] and is replaced there by the activated gates
     DropCfg drop;
-    int dbg;   // dev builds only (-DAMDSPEECH_DEVTRACE): timing experiments selected by AMDSPEECH_DBG
+    int dbg;   // dev builds only (-DAMDSPEECH_DEVTRACE): timing experiments (DEV_DBG); 0 from the host
     unsigned long long* trace; int trace_d;   // dev builds only: per-wave s_memtime stamps for diagonal trace_d
 };
 #ifdef AMDSPEECH_DEVTRACE
