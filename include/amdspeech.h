@@ -307,6 +307,47 @@ int amdspeech_lstm_bwd_ctc(void* stream, const amdspeech_lstm_desc* d, void* ws,
  * checker can run the reference's graph with the very masks the kernels used.                                            */
 int amdspeech_lstm_dropout_multipliers(void* stream, const amdspeech_lstm_desc* d, int which, int layer, float* out);
 
+/* ------------------------------------------------ layer-wise bidirectional stacks ----
+ * tf.contrib.rnn.stack_bidirectional_dynamic_rnn (torch.nn.LSTM(bidirectional=True, num_layers=L)): L layers, each a forward and
+ * a backward BasicLSTMCell (+ DropoutWrapper), where layer l+1 of BOTH directions reads the concatenation [h_fw_l ; h_bw_l].
+ * (amdspeech_lstm_fwd_pair is the other, "top-joined" form: two independent stacks joined only in front of the output layer.)
+ * Semantics:
+ *   - layer 0 of both directions reads Z_0 [T][B][H] (the input Linear's output, region Z0);
+ *   - for l >= 1 the forward cell reads [h_fw_{l-1} ; h_bw_{l-1}] [T][B][2H], fw half first (TF's concat(outputs, 2)); the
+ *     backward cell reads tf.reverse_sequence of that concatenation, each row reversed within its own length; h_bw is stored
+ *     in forward time;
+ *   - cell kernels keep the TF BasicLSTMCell layout [input_depth + H][4H] (rows: x then h; column blocks i|j|f|o), bias [4H],
+ *     forget_bias 1.0 added at run time: (2H, 4H) at layer 0, (3H, 4H) above.  `kernels` / `biases` are HOST arrays of 2L
+ *     device pointers, the forward cells' layers 0..L-1 first, then the backward cells'.  The output layer reads
+ *     [h_fw_top ; h_bw_top] (regions YTOP_FW / YTOP_BW);
+ *   - dropout (desc keep_in / keep_out / seed): DropoutWrapper on each direction's cell -- its own input mask over its whole
+ *     input (2H wide above layer 0) and its own output mask, in the cell's own (step) order: element s*B*W + b*W + k of step s.
+ *     The forward cells draw from `seed`, the backward cells from seed ^ 0x5bd1e995; amdspeech_lstm_bidir_dropout_multipliers
+ *     exports them (dir 0 / 1, which 0 = input mask [T][B][W], 1 = output mask [T][B][H]);
+ *   - frames t >= len_b emit 0 and copy the state through; h0 / c0 ([L][B][H] or NULL) initialise the FORWARD cells, the backward
+ *     cells start from zero; HFINAL / CFINAL are the forward cells' final state, layer l at ptr + l * layer_stride floats.
+ * Exact f32 only (precision != 0: AMDSPEECH_EUNSUPPORTED), H a multiple of 16 up to 1024.  Per layer: the pack of both
+ * directions' inputs, x . W_ih for all frames (one GEMM per direction), then ONE persistent launch for both directions' recurrence
+ * (amdspeech_lstm_bidir_path = 2; 1 = one persistent launch per direction; 0 = one launch per frame: AMDSPEECH_BIDIR_PERSISTENT=0,
+ * or flags & AMDSPEECH_LSTM_PER_DIAGONAL -- the repeat of a mini-batch whose persistent launch timed out).  Its bounded waits
+ * end in AMDSPEECH_ETIMEOUT at amdspeech_lstm_bidir_status; AMDSPEECH_LSTM_INJECT_TIMEOUT (tests) gives up at the first
+ * unsatisfied wait.  bwd reads DYTOP_FW / DYTOP_BW (forward time, filled by the caller), writes DZ0 and ACCUMULATES the cells'
+ * kernel and bias gradients.                                                                                                  */
+enum {
+    AMDSPEECH_BIDIR_WS_Z0 = 0, AMDSPEECH_BIDIR_WS_YTOP_FW = 1, AMDSPEECH_BIDIR_WS_YTOP_BW = 2, AMDSPEECH_BIDIR_WS_DYTOP_FW = 3,
+    AMDSPEECH_BIDIR_WS_DYTOP_BW = 4, AMDSPEECH_BIDIR_WS_DZ0 = 5, AMDSPEECH_BIDIR_WS_HFINAL = 6, AMDSPEECH_BIDIR_WS_CFINAL = 7
+};
+size_t amdspeech_lstm_bidir_workspace_bytes(const amdspeech_lstm_desc* d);
+void* amdspeech_lstm_bidir_ws_ptr(const amdspeech_lstm_desc* d, void* ws, int which);
+long amdspeech_lstm_bidir_layer_stride(const amdspeech_lstm_desc* d);
+int amdspeech_lstm_bidir_path(const amdspeech_lstm_desc* d);
+int amdspeech_lstm_bidir_fwd(void* stream, const amdspeech_lstm_desc* d, void* ws, const float* const* kernels,
+                             const float* const* biases, const int* lengths, const float* h0, const float* c0);
+int amdspeech_lstm_bidir_bwd(void* stream, const amdspeech_lstm_desc* d, void* ws, const float* const* kernels,
+                             float* const* dkernels, float* const* dbiases, const int* lengths);
+int amdspeech_lstm_bidir_status(const amdspeech_lstm_desc* d, void* ws);
+int amdspeech_lstm_bidir_dropout_multipliers(void* stream, const amdspeech_lstm_desc* d, int dir, int which, int layer, float* out);
+
 /* ------------------------------------------------------------------- CTC ----
  * Replaces tf.nn.ctc_loss(sparse_labels, logits, seq_len,
  * ignore_longer_outputs_than_inputs=True) and its gradient,

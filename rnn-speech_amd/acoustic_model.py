@@ -496,6 +496,7 @@ class AcousticModel(object):
         self._last_err = None
         self.precision = "f32"             # "bf16x3": opt-in split-precision MFMA in the recurrence (config key `precision`)
         self.bidirectional = False         # config key `bidirectional` (BASELINE configs[4]; the reference is unidirectional)
+        self.bidirectional_mode = "top"    # config key `bidirectional_mode`: top (two stacks) | layer (stack_bidirectional_dynamic_rnn)
         self.sync_batch_norm = False       # config key `sync_batch_norm`: data-parallel batch-norm moments over ALL ranks (deviation)
         self.save_tf_bundle = False        # also write <stem>.index / .data-00000-of-00001 on save()
         self.save_optimizer_state = True   # native .npz also carries Adam m/v/step and the RNN state
@@ -515,7 +516,8 @@ class AcousticModel(object):
         self.engine = Engine(self.num_layers, self.hidden_size, self.input_dim, self.num_labels,
                              self.batch_size, self.max_input_seq_length, self.max_target_seq_length,
                              normalization=bool(self.normalization), precision=self.precision,
-                             bidirectional=bool(self.bidirectional), sync_batch_norm=bool(self.sync_batch_norm))
+                             bidirectional=bool(self.bidirectional), sync_batch_norm=bool(self.sync_batch_norm),
+                             bidirectional_mode=self.bidirectional_mode)
         self.rnn_created = True
 
     def create_forward_rnn(self):
@@ -583,6 +585,11 @@ class AcousticModel(object):
     def _tf_name(self, name):
         if name in self._TF_NAMES:
             return self._TF_NAMES[name]
+        if getattr(self.engine, "layerwise", False) and name.split("_")[-2] in ("kernel", "bias"):
+            # layer-wise bidirectional stacks: tf.contrib.rnn.stack_bidirectional_dynamic_rnn's scope names
+            d = "bw" if name.startswith("bw_") else "fw"
+            kind, l = name[3:].split("_") if d == "bw" else name.split("_")
+            return "stack_bidirectional_rnn/cell_%s/bidirectional_rnn/%s/basic_lstm_cell/%s" % (l, d, kind)
         if name.startswith("bw_"):       # (bidirectional build only: tf.nn.bidirectional_dynamic_rnn's scope names)
             kind, l = name[3:].split("_")
             return "bidirectional_rnn/bw/multi_rnn_cell/cell_%s/basic_lstm_cell/%s" % (l, kind)

@@ -27,9 +27,12 @@ class ParamLayout(object):
     """Flat fp32 layout [input_w | input_b | (kernel_l | bias_l)*L | output_w | output_b],
     every tensor starting on a 256-byte boundary (pads are zero and stay zero)."""
 
-    def __init__(self, num_layers, hidden, input_dim, num_labels, bidirectional=False):
+    def __init__(self, num_layers, hidden, input_dim, num_labels, bidirectional=False, bidirectional_mode="top"):
         self.L, self.H, self.D, self.C = num_layers, hidden, input_dim, num_labels
         self.bidirectional = bool(bidirectional)
+        # "layer" (stack_bidirectional_dynamic_rnn): the cells above layer 0 read [h_fw ; h_bw], kernels (3H, 4H) there -- the stride
+        # between layers is not uniform (kernel_stride / bias_stride are None)
+        self.layerwise = self.bidirectional and bidirectional_mode == "layer"
         off = 0
         self.slots = {}
 
@@ -43,17 +46,22 @@ class ParamLayout(object):
 
         take("input_w", (input_dim, hidden))
         take("input_b", (hidden,))
+        def rows(l):
+            return (3 if self.layerwise and l > 0 else 2) * hidden
+
         for l in range(num_layers):
-            take("kernel_%d" % l, (2 * hidden, 4 * hidden))
+            take("kernel_%d" % l, (rows(l), 4 * hidden))
             take("bias_%d" % l, (4 * hidden,))
         if self.bidirectional:           # the backward-direction stack: same shapes, same stride between layers
             for l in range(num_layers):
-                take("bw_kernel_%d" % l, (2 * hidden, 4 * hidden))
+                take("bw_kernel_%d" % l, (rows(l), 4 * hidden))
                 take("bw_bias_%d" % l, (4 * hidden,))
         take("output_w", ((2 if self.bidirectional else 1) * hidden, num_labels))
         take("output_b", (num_labels,))
         self.total = off
-        if num_layers > 1:
+        if self.layerwise:
+            self.kernel_stride = self.bias_stride = None
+        elif num_layers > 1:
             self.kernel_stride = self.slots["kernel_1"][0] - self.slots["kernel_0"][0]
             self.bias_stride = self.slots["bias_1"][0] - self.slots["bias_0"][0]
         else:
@@ -94,7 +102,7 @@ PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16": 2}
 class Engine(object):
     def __init__(self, num_layers, hidden, input_dim, num_labels, batch_size, max_T, max_U,
                  device="cuda", seed=1234, normalization=False, precision="f32", bidirectional=False,
-                 sync_batch_norm=False):
+                 sync_batch_norm=False, bidirectional_mode="top"):
         if not torch.cuda.is_available():
             raise RuntimeError("rnn_speech_amd needs a ROCm GPU (MI355X); there is no CPU path")
         self.L, self.H, self.D, self.C = num_layers, hidden, input_dim, num_labels
@@ -104,7 +112,16 @@ class Engine(object):
         # :276-278): a second stack of the same shape reads every utterance reversed in time (tf.reverse_sequence semantics,
         # as tf.nn.bidirectional_dynamic_rnn does), the two top outputs are concatenated in front of the output layer
         self.bidirectional = bool(bidirectional)
-        self.layout = ParamLayout(num_layers, hidden, input_dim, num_labels, bidirectional=self.bidirectional)
+        if bidirectional_mode not in ("top", "layer"):
+            raise ValueError("bidirectional_mode must be 'top' (two stacks joined in front of the output layer) or 'layer' "
+                             "(stack_bidirectional_dynamic_rnn: every layer reads both directions of the layer below)")
+        # layer-wise bidirectional stacks (amdspeech_lstm_bidir_*): only read when bidirectional
+        self.layerwise = self.bidirectional and bidirectional_mode == "layer"
+        if self.layerwise and precision != "f32":
+            raise ValueError("bidirectional_mode 'layer' is exact f32 only (precision %r requested): the layer-wise kernels have no "
+                             "reduced-precision variant" % (precision,))
+        self.layout = ParamLayout(num_layers, hidden, input_dim, num_labels, bidirectional=self.bidirectional,
+                                  bidirectional_mode="layer" if self.layerwise else "top")
         n = self.layout.total
         self.params = torch.zeros(n, device=self.device)
         self.grads = torch.zeros(n, device=self.device)
@@ -116,8 +133,11 @@ class Engine(object):
             raise ValueError("precision must be 'f32' (exact, default), 'bf16x3' (split-precision MFMA) or 'bf16' (plain bf16 "
                              "operands, f32 accumulation and master weights)")
         self.precision = precision
-        self.lstm_ws = ops.LstmWorkspace(max_T, batch_size, hidden, num_layers, device=self.device, precision=PRECISIONS[precision])
-        if self.bidirectional:
+        if self.layerwise:
+            self.lstm_ws = ops.BidirWorkspace(max_T, batch_size, hidden, num_layers, device=self.device)
+        else:
+            self.lstm_ws = ops.LstmWorkspace(max_T, batch_size, hidden, num_layers, device=self.device, precision=PRECISIONS[precision])
+        if self.bidirectional and not self.layerwise:
             self.lstm_ws_b = ops.LstmWorkspace(max_T, batch_size, hidden, num_layers, device=self.device,
                                                precision=PRECISIONS[precision])
             self.ytop_b = torch.empty(max_T, batch_size, hidden, device=self.device)      # backward stack's output, in forward time
@@ -143,7 +163,8 @@ class Engine(object):
         self._ws, self._Tr = self.lstm_ws, max_T
         self._head = None                # ops.CtcHead of the mini-batch in flight, when its CTC stage runs inside the LSTM launches
         self._paired = False             # the last forward ran a bidirectional model's two stacks side by side (ops.lstm_fwd_pair)
-        self._ws_b = self.lstm_ws_b if self.bidirectional else None
+        self._ws_b = self.lstm_ws_b if self.bidirectional and not self.layerwise else None
+        self._layer_path = None          # (layer-wise mode) amdspeech_lstm_bidir_path of the last forward
         # a real (non-NULL) stream for callers that want the overlapped backward pass: see on_stream()
         self.stream = torch.cuda.Stream(device=self.device, priority=-1)      # (ahead of the side stream that prefetches the next batch)
         self._aux_stream = None          # (mini_batch: carries the "beside the forward kernel" ordering point to the caller's hook)
@@ -222,6 +243,8 @@ class Engine(object):
                 ops.batchnorm_fwd_dp(ws.z0, ws.z0, self.bn_xhat, self.bn_inv_std, grp, self.bn_scratch, 1e-3)
             else:
                 ops.batchnorm_fwd(ws.z0, ws.z0, self.bn_xhat[:Tr], self.bn_inv_std[:Tr], 1e-3)
+        if self.layerwise:
+            return self._forward_layerwise(ws, lengths, keep_in, keep_out, seed, use_state, after_lstm, per_diagonal, Tr)
         if self.bidirectional:
             # the backward-direction stack reads the time-reversed input-layer output.  Taken BEFORE the forward stack runs:
             # lstm_fwd applies its layer-0 input-dropout mask to Z_0 in place, and the two stacks' DropoutWrappers are
@@ -274,11 +297,37 @@ class Engine(object):
             self.logits[Tr:] = self.p("output_b")          # broadcast fill of the never-visited tail
         return self.logits
 
+    def _cells(self, flat):
+        """The 2L cell kernels and biases of the layer-wise mode (forward cells first) as views into `flat`."""
+        L = self.L
+        ks = [self.layout.view(flat, "kernel_%d" % l) for l in range(L)] + [self.layout.view(flat, "bw_kernel_%d" % l) for l in range(L)]
+        bs = [self.layout.view(flat, "bias_%d" % l) for l in range(L)] + [self.layout.view(flat, "bw_bias_%d" % l) for l in range(L)]
+        return ks, bs
+
+    def _forward_layerwise(self, ws, lengths, keep_in, keep_out, seed, use_state, after_lstm, per_diagonal, Tr):
+        B, H = self.B, self.H
+        ws.set_dropout(keep_in, keep_out, seed)
+        ks, bs = self._cells(self.params)
+        self._layer_path = 0 if per_diagonal else ws.path()
+        ops.lstm_bidir_fwd(ws, ks, bs, lengths, self.state_h if use_state else None, self.state_c if use_state else None,
+                           per_frame=per_diagonal)
+        if after_lstm is not None:
+            after_lstm()
+        wo = self.p("output_w")
+        ops.linear_fwd(ws.ytop_fw.view(Tr * B, H), wo[:H], self.p("output_b"), out=self.logits[:Tr].view(Tr * B, self.C))
+        ops.gemm(ws.ytop_bw.view(Tr * B, H), wo[H:], out=self.logits[:Tr].view(Tr * B, self.C), accumulate=True)
+        if Tr < self.T:
+            self.logits[Tr:] = self.p("output_b")
+        return self.logits
+
     def kernel_path(self):
         """Which shape-driven choices the LAST forward made -- what a parity test has to assert before it may claim to have checked
         them: `fused_ctc_head` (the CTC stage ran inside the two whole-sequence LSTM launches, ops.CtcHead), `paired` (a
         bidirectional model's two stacks side by side on one-XCD groups, ops.lstm_fwd_pair), `run_length` (frames visited)."""
-        return {"fused_ctc_head": self._head is not None, "paired": self._paired, "run_length": self._Tr}
+        path = {"fused_ctc_head": self._head is not None, "paired": self._paired, "run_length": self._Tr}
+        if self.layerwise:      # the layer-wise recurrence: "persistent" (one launch per layer for both directions, or per direction) or "per_frame"
+            path["layer_recurrence"] = {2: "persistent", 1: "persistent_per_direction", 0: "per_frame"}.get(self._layer_path)
+        return path
 
     def final_state(self):
         """(h [L,B,H], c [L,B,H]) after the last forward."""
@@ -330,6 +379,9 @@ class Engine(object):
         ws, Tr = self._ws, self._Tr
         H = self.H
         dl = self.dlogits[:Tr].view(Tr * B, self.C)
+        if self.layerwise:
+            self._backward_layerwise(x, lengths, wait_for, per_diagonal)
+            return
         head = self._head if not per_diagonal else None
         if self._head is not None and head is None:
             raise _lib.AmdSpeechError("backward(per_diagonal=True) after a forward with the fused CTC head: repeat the forward too")
@@ -393,10 +445,35 @@ class Engine(object):
         ops.linear_bwd(x[:Tr].view(Tr * B, D), self.p("input_w"), ws.dz0.view(Tr * B, self.H), self.g("input_w"),
                        self.g("input_b"), need_dx=False)
 
+    def _backward_layerwise(self, x, lengths, wait_for, per_diagonal):
+        ws, Tr, B, H, D = self._ws, self._Tr, self.B, self.H, self.D
+        dl = self.dlogits[:Tr].view(Tr * B, self.C)
+        wo, gwo = self.p("output_w"), self.g("output_w")
+        ops.linear_bwd(ws.ytop_fw.view(Tr * B, H), wo[:H], dl, gwo[:H], self.g("output_b"), need_dx=True,
+                       dx=ws.dytop_fw.view(Tr * B, H))
+        ops.gemm(ws.ytop_bw.view(Tr * B, H), dl, trans_a=True, out=gwo[H:], accumulate=True)          # dW_o[H:] += y_bw^T . dlogits
+        ops.gemm(dl, wo[H:], trans_b=True, out=ws.dytop_bw.view(Tr * B, H))                            # d y_bw (forward time)
+        if wait_for is not None:
+            torch.cuda.current_stream(self.device).wait_event(wait_for)
+        ks, _ = self._cells(self.params)
+        dks, dbs = self._cells(self.grads)
+        ops.lstm_bidir_bwd(ws, ks, dks, dbs, lengths, per_frame=per_diagonal)
+        if self.normalization:
+            grp = self._dp_group() if self.sync_batch_norm else None
+            if grp is not None and grp.world > 1:
+                ops.batchnorm_bwd_dp(ws.dz0, self.bn_xhat, self.bn_inv_std, ws.dz0, grp, self.bn_scratch)
+            else:
+                ops.batchnorm_bwd(ws.dz0, self.bn_xhat[:Tr], self.bn_inv_std[:Tr], ws.dz0)
+        ops.linear_bwd(x[:Tr].view(Tr * B, D), self.p("input_w"), ws.dz0.view(Tr * B, H), self.g("input_w"),
+                       self.g("input_b"), need_dx=False)
+
     def check(self):
         """Synchronous health check of the dataflow LSTM kernels: their waits are bounded, and a time-out (the
         workgroups of one launch were not all resident -- another kernel held CUs) leaves an error flag behind
         instead of hanging.  Raises AmdSpeechError; results of that step are invalid."""
+        if self.layerwise:
+            ops.lstm_bidir_status(self._ws)
+            return
         ops.lstm_status(self._ws)
         if self.bidirectional:
             ops.lstm_status(self._ws_b)
@@ -444,7 +521,7 @@ class Engine(object):
                 return
             if self._aux_stream is None:
                 self._aux_stream = torch.cuda.Stream(self.device)
-            if ops.lstm_beside_forward(self._ws, self._aux_stream) > 0:
+            if not self.layerwise and ops.lstm_beside_forward(self._ws, self._aux_stream) > 0:
                 after = torch.cuda.Event()
                 after.record(self._aux_stream)
                 placed.append(beside_forward(after))

@@ -11,8 +11,10 @@ _ACOUSTIC, _GENERAL, _TRAINING, _LOGGING = "acoustic_network_params", "general",
 # a change of any of these makes an existing checkpoint unusable (the reference compares the first four,
 # util/hyperparams.py:75-92; n_mfcc / sample_rate are this build's extra keys and change the input layer's
 # shape / the features' meaning)
-_STRUCTURAL = ("num_layers", "hidden_size", "signal_processing", "language", "n_mfcc", "sample_rate", "bidirectional")
-_STRUCTURAL_DEFAULTS = {"signal_processing": "mfcc", "language": "", "n_mfcc": 20, "sample_rate": 22050, "bidirectional": False}
+_STRUCTURAL = ("num_layers", "hidden_size", "signal_processing", "language", "n_mfcc", "sample_rate", "bidirectional",
+               "bidirectional_mode")
+_STRUCTURAL_DEFAULTS = {"signal_processing": "mfcc", "language": "", "n_mfcc": 20, "sample_rate": 22050, "bidirectional": False,
+                        "bidirectional_mode": "top"}
 
 
 def read_config_file(config_file):
@@ -52,6 +54,11 @@ def read_config_file(config_file):
     d["precision"] = cp.get(_ACOUSTIC, "precision", fallback="f32")       # f32 (exact) | bf16x3 (split MFMA) | bf16 (plain bf16 operands)
     d["sample_rate"] = cp.getint(_TRAINING, "sample_rate", fallback=22050)
     d["bidirectional"] = cp.getboolean(_ACOUSTIC, "bidirectional", fallback=False)
+    # top: two stacks joined in front of the output layer; layer: stack_bidirectional_dynamic_rnn (every layer reads both
+    # directions of the layer below).  Only read when bidirectional is True.
+    d["bidirectional_mode"] = cp.get(_ACOUSTIC, "bidirectional_mode", fallback="top")
+    if d["bidirectional_mode"] not in ("top", "layer"):
+        raise ValueError("bidirectional_mode must be 'top' or 'layer', not %r" % d["bidirectional_mode"])
     d["sync_batch_norm"] = cp.getboolean(_TRAINING, "sync_batch_norm", fallback=False)   # DP only; deviation from the reference
     # the decoder behind the per-mini-batch training error rate: greedy (GPU) | beam (default: the reference's width-100 beam
     # decoder, models/AcousticModel.py:312-314,:641, on host threads, reported `train_decoder_lag` mini-batches late; 0 = wait)

@@ -38,6 +38,7 @@ LSTM_ARMED, LSTM_ARM_NEXT, LSTM_SAME_WS, LSTM_PER_DIAGONAL, LSTM_INJECT_TIMEOUT 
 
 COMM_ID_BYTES = 128
 WS_Z0, WS_ZTOP, WS_DZTOP, WS_DZ0, WS_HFINAL, WS_CFINAL = range(6)
+BIDIR_WS_Z0, BIDIR_WS_YTOP_FW, BIDIR_WS_YTOP_BW, BIDIR_WS_DYTOP_FW, BIDIR_WS_DYTOP_BW, BIDIR_WS_DZ0, BIDIR_WS_HFINAL, BIDIR_WS_CFINAL = range(8)
 
 _P = C.c_void_p
 _I = C.c_int
@@ -78,6 +79,14 @@ PROTOTYPES = {
     "amdspeech_lstm_fwd_ctc": (_I, [_P, C.POINTER(LstmDesc), _P, _P, _L, _P, _L, _P, _P, _P, C.POINTER(CtcHead)]),
     "amdspeech_lstm_bwd_ctc": (_I, [_P, C.POINTER(LstmDesc), _P, _P, _L, _P, _P, _L, _P, C.POINTER(CtcHead)]),
     "amdspeech_lstm_dropout_multipliers": (_I, [_P, C.POINTER(LstmDesc), _I, _I, _P]),
+    "amdspeech_lstm_bidir_workspace_bytes": (_SZ, [C.POINTER(LstmDesc)]),
+    "amdspeech_lstm_bidir_ws_ptr": (_P, [C.POINTER(LstmDesc), _P, _I]),
+    "amdspeech_lstm_bidir_layer_stride": (_L, [C.POINTER(LstmDesc)]),
+    "amdspeech_lstm_bidir_path": (_I, [C.POINTER(LstmDesc)]),
+    "amdspeech_lstm_bidir_fwd": (_I, [_P, C.POINTER(LstmDesc), _P, _P, _P, _P, _P, _P]),
+    "amdspeech_lstm_bidir_bwd": (_I, [_P, C.POINTER(LstmDesc), _P, _P, _P, _P, _P]),
+    "amdspeech_lstm_bidir_status": (_I, [C.POINTER(LstmDesc), _P]),
+    "amdspeech_lstm_bidir_dropout_multipliers": (_I, [_P, C.POINTER(LstmDesc), _I, _I, _I, _P]),
     "amdspeech_ctc_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "amdspeech_ctc_loss_fwd_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "amdspeech_ctc_loss_fwd_bwd_staged": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I]),

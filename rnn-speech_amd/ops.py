@@ -409,6 +409,120 @@ def lstm_dropout_multipliers(ws, which, layer):
     return out
 
 
+class BidirWorkspace(object):
+    """Workspace of a layer-wise bidirectional stack (amdspeech.h: amdspeech_lstm_bidir_*): named regions as tensor views."""
+
+    def __init__(self, T, B, H, L, device="cuda", _share=None):
+        self.lib = _l.load()
+        self.desc = _l.LstmDesc(T, B, H, L, 1.0, 1.0, 0, 0)
+        nbytes = self.lib.amdspeech_lstm_bidir_workspace_bytes(C.byref(self.desc))
+        if nbytes == 0:
+            raise _l.AmdSpeechError("lstm bidir workspace: " + self.lib.amdspeech_last_error().decode())
+        self.T, self.B, self.H, self.L = T, B, H, L
+        if _share is None:
+            self.buf = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
+        else:
+            if _share.numel() * 4 < nbytes:
+                raise _l.AmdSpeechError("lstm bidir workspace: T = %d needs %d bytes, the shared allocation has %d"
+                                        % (T, nbytes, _share.numel() * 4))
+            self.buf = _share
+        self._root, self._prefixes = self, {}
+        self.z0 = self._view(_l.BIDIR_WS_Z0, (T, B, H))
+        self.ytop_fw = self._view(_l.BIDIR_WS_YTOP_FW, (T, B, H))
+        self.ytop_bw = self._view(_l.BIDIR_WS_YTOP_BW, (T, B, H))
+        self.dytop_fw = self._view(_l.BIDIR_WS_DYTOP_FW, (T, B, H))
+        self.dytop_bw = self._view(_l.BIDIR_WS_DYTOP_BW, (T, B, H))
+        self.dz0 = self._view(_l.BIDIR_WS_DZ0, (T, B, H))
+
+    def prefix(self, T_run):
+        """The same allocation laid out for a shorter run (the layout is monotone in T)."""
+        if T_run >= self.T:
+            return self
+        ws = self._prefixes.get(T_run)
+        if ws is None:
+            if len(self._prefixes) > 64:
+                self._prefixes.clear()
+            ws = BidirWorkspace(T_run, self.B, self.H, self.L, device=self.buf.device, _share=self.buf)
+            ws._root = self
+            self._prefixes[T_run] = ws
+        return ws
+
+    def _offset(self, which):
+        p = self.lib.amdspeech_lstm_bidir_ws_ptr(C.byref(self.desc), _p(self.buf), which)
+        if not p:
+            raise _l.AmdSpeechError("lstm_bidir_ws_ptr failed")
+        return (p - self.buf.data_ptr()) // 4
+
+    def _view(self, which, shape):
+        off = self._offset(which)
+        n = 1
+        for s in shape:
+            n *= s
+        return self.buf[off:off + n].view(*shape)
+
+    def set_dropout(self, keep_in, keep_out, seed):
+        self.desc.keep_in, self.desc.keep_out, self.desc.seed = keep_in, keep_out, seed
+
+    def path(self):
+        """2: both directions of a layer in one persistent launch, 1: one persistent launch per direction, 0: one launch per frame."""
+        rc = self.lib.amdspeech_lstm_bidir_path(C.byref(self.desc))
+        if rc < 0:
+            _l.check(rc, "lstm_bidir_path")
+        return rc
+
+    def final_state(self):
+        """(h [L,B,H], c [L,B,H]) of the forward cells after the last frame."""
+        stride = self.lib.amdspeech_lstm_bidir_layer_stride(C.byref(self.desc))
+        B, H, L = self.B, self.H, self.L
+        h = torch.as_strided(self.buf, (L, B, H), (stride, H, 1), self._offset(_l.BIDIR_WS_HFINAL))
+        c = torch.as_strided(self.buf, (L, B, H), (stride, H, 1), self._offset(_l.BIDIR_WS_CFINAL))
+        return h, c
+
+
+def _ptr_array(ts):
+    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def lstm_bidir_fwd(ws, kernels, biases, lengths, h0=None, c0=None, per_frame=False, inject_timeout=False):
+    """Layer-wise bidirectional forward (amdspeech_lstm_bidir_fwd): kernels / biases = the 2L cell tensors, forward cells first.
+    Reads ws.z0, writes ws.ytop_fw / ws.ytop_bw (forward time)."""
+    _chk_i32(lengths)
+    _chk_f32(*kernels, *biases)
+    ws.desc.flags = (_l.LSTM_PER_DIAGONAL if per_frame else 0) | (_l.LSTM_INJECT_TIMEOUT if inject_timeout else 0)
+    try:
+        _l.check(ws.lib.amdspeech_lstm_bidir_fwd(_stream(), C.byref(ws.desc), _p(ws.buf), _ptr_array(kernels), _ptr_array(biases),
+                                                 _p(lengths), _p(h0), _p(c0)), "lstm_bidir_fwd")
+    finally:
+        ws.desc.flags = 0
+
+
+def lstm_bidir_bwd(ws, kernels, dkernels, dbiases, lengths, per_frame=False, inject_timeout=False):
+    """Its backward pass: reads ws.dytop_fw / ws.dytop_bw, writes ws.dz0, accumulates into dkernels / dbiases."""
+    _chk_i32(lengths)
+    ws.desc.flags = (_l.LSTM_PER_DIAGONAL if per_frame else 0) | (_l.LSTM_INJECT_TIMEOUT if inject_timeout else 0)
+    try:
+        _l.check(ws.lib.amdspeech_lstm_bidir_bwd(_stream(), C.byref(ws.desc), _p(ws.buf), _ptr_array(kernels), _ptr_array(dkernels),
+                                                 _ptr_array(dbiases), _p(lengths)), "lstm_bidir_bwd")
+    finally:
+        ws.desc.flags = 0
+
+
+def lstm_bidir_status(ws):
+    """Synchronous check that no bounded wait of the persistent per-layer kernels timed out (DataflowTimeout if one did)."""
+    _l.check(ws.lib.amdspeech_lstm_bidir_status(C.byref(ws.desc), _p(ws.buf)), "lstm_bidir_status")
+
+
+def lstm_bidir_dropout_multipliers(ws, direction, which, layer):
+    """The multipliers one cell applies (step order): direction "fw" / "bw", which "in" ([T,B,W], W = H at layer 0, 2H above) or
+    "out" ([T,B,H])."""
+    W = ws.H if (which == "out" or layer == 0) else 2 * ws.H
+    out = torch.empty(ws.T, ws.B, W, device=ws.buf.device, dtype=torch.float32)
+    _l.check(ws.lib.amdspeech_lstm_bidir_dropout_multipliers(_stream(), C.byref(ws.desc), {"fw": 0, "bw": 1}[direction],
+                                                             {"in": 0, "out": 1}[which], int(layer), _p(out)),
+             "lstm_bidir_dropout_multipliers")
+    return out
+
+
 def reverse_sequences(x, lengths, out=None, accumulate=False):
     """Time-major [T,B,H]: out[t,b] = x[len_b-1-t, b] for t < len_b, 0 beyond (tf.reverse_sequence; self-adjoint)."""
     _chk_f32(x, out)

@@ -88,6 +88,7 @@ def build_acoustic_training_rnn(sess, hyper_params, prog_params, train_set, test
                hyper_params["max_target_seq_length"], hyper_params["signal_processing"], hyper_params["char_map"])
     model.precision = hyper_params.get("precision", "f32")
     model.bidirectional = hyper_params.get("bidirectional", False)
+    model.bidirectional_mode = hyper_params.get("bidirectional_mode", "top")
     model.sync_batch_norm = hyper_params.get("sync_batch_norm", False)
     model.train_decoder = hyper_params.get("train_decoder", "beam")
     model.train_decoder_lag = hyper_params.get("train_decoder_lag", 1)
@@ -207,6 +208,7 @@ def _forward_model(hyper_params, batch_size):
                           hyper_params["char_map_length"])
     model.precision = hyper_params.get("precision", "f32")
     model.bidirectional = hyper_params.get("bidirectional", False)
+    model.bidirectional_mode = hyper_params.get("bidirectional_mode", "top")
     model.sync_batch_norm = hyper_params.get("sync_batch_norm", False)
     model.create_forward_rnn()
     model.initialize(None)
