@@ -142,7 +142,8 @@ typedef struct amdspeech_lstm_desc {
                                      (DESIGN.md 4.2d): logits 1.3-2.3e-3 of max (outside north_star's 1e-3), CTC loss
                                      7e-5, gradients 3-5e-3 -- an opt-in throughput mode, never the default.  Shapes outside
                                      the dataflow / per-layer kernels run their RECURRENT products in bf16x3 (a superset
-                                     in accuracy); the batched products (weight gradients, dZ_0) are single bf16 there too */
+                                     in accuracy); the batched products (weight gradients, dZ_0) are single bf16 there too.
+                                  The layer-wise bidirectional entry points (amdspeech_lstm_bidir_*) take 0 and 1 only */
     int flags;                 /* 0, or AMDSPEECH_LSTM_* bits below (training cycles on ONE workspace and shape) */
 } amdspeech_lstm_desc;
 
@@ -326,7 +327,10 @@ int amdspeech_lstm_dropout_multipliers(void* stream, const amdspeech_lstm_desc* 
  *     exports them (dir 0 / 1, which 0 = input mask [T][B][W], 1 = output mask [T][B][H]);
  *   - frames t >= len_b emit 0 and copy the state through; h0 / c0 ([L][B][H] or NULL) initialise the FORWARD cells, the backward
  *     cells start from zero; HFINAL / CFINAL are the forward cells' final state, layer l at ptr + l * layer_stride floats.
- * Exact f32 only (precision != 0: AMDSPEECH_EUNSUPPORTED), H a multiple of 16 up to 1024.  Per layer: the pack of both
+ * Precision 0 (exact f32; H a multiple of 16 up to 1024) or 1 (bf16x3: the recurrent product on the bf16 MFMA and the batched
+ * products through the bf16x3 GEMM; H a multiple of 32 whose H and 4H rows of W_hh split over at most 8 waves in 32 x 1, 2, 4,
+ * 8 or 16 rows: 32 ... 256, 320, 512, 768, 1024 and others -- workspace_bytes returns 0 for the rest); precision 2 (plain bf16):
+ * AMDSPEECH_EUNSUPPORTED.  Per layer: the pack of both
  * directions' inputs, x . W_ih for all frames (one GEMM per direction), then ONE persistent launch for both directions' recurrence
  * (amdspeech_lstm_bidir_path = 2; 1 = one persistent launch per direction; 0 = one launch per frame: AMDSPEECH_BIDIR_PERSISTENT=0,
  * or flags & AMDSPEECH_LSTM_PER_DIAGONAL -- the repeat of a mini-batch whose persistent launch timed out).  Its bounded waits

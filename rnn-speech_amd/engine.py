@@ -117,9 +117,9 @@ class Engine(object):
                              "(stack_bidirectional_dynamic_rnn: every layer reads both directions of the layer below)")
         # layer-wise bidirectional stacks (amdspeech_lstm_bidir_*): only read when bidirectional
         self.layerwise = self.bidirectional and bidirectional_mode == "layer"
-        if self.layerwise and precision != "f32":
-            raise ValueError("bidirectional_mode 'layer' is exact f32 only (precision %r requested): the layer-wise kernels have no "
-                             "reduced-precision variant" % (precision,))
+        if self.layerwise and precision not in ("f32", "bf16x3"):
+            raise ValueError("bidirectional_mode 'layer' runs in exact f32 or bf16x3 (precision %r requested): the layer-wise kernels "
+                             "have no plain-bf16 variant" % (precision,))
         self.layout = ParamLayout(num_layers, hidden, input_dim, num_labels, bidirectional=self.bidirectional,
                                   bidirectional_mode="layer" if self.layerwise else "top")
         n = self.layout.total
@@ -134,7 +134,7 @@ class Engine(object):
                              "operands, f32 accumulation and master weights)")
         self.precision = precision
         if self.layerwise:
-            self.lstm_ws = ops.BidirWorkspace(max_T, batch_size, hidden, num_layers, device=self.device)
+            self.lstm_ws = ops.BidirWorkspace(max_T, batch_size, hidden, num_layers, device=self.device, precision=PRECISIONS[precision])
         else:
             self.lstm_ws = ops.LstmWorkspace(max_T, batch_size, hidden, num_layers, device=self.device, precision=PRECISIONS[precision])
         if self.bidirectional and not self.layerwise:
@@ -327,6 +327,7 @@ class Engine(object):
         path = {"fused_ctc_head": self._head is not None, "paired": self._paired, "run_length": self._Tr}
         if self.layerwise:      # the layer-wise recurrence: "persistent" (one launch per layer for both directions, or per direction) or "per_frame"
             path["layer_recurrence"] = {2: "persistent", 1: "persistent_per_direction", 0: "per_frame"}.get(self._layer_path)
+            path["layer_product"] = self.precision      # its recurrent product: "f32" (vector ALUs) or "bf16x3" (bf16 MFMA)
         return path
 
     def final_state(self):

@@ -410,15 +410,16 @@ def lstm_dropout_multipliers(ws, which, layer):
 
 
 class BidirWorkspace(object):
-    """Workspace of a layer-wise bidirectional stack (amdspeech.h: amdspeech_lstm_bidir_*): named regions as tensor views."""
+    """Workspace of a layer-wise bidirectional stack (amdspeech.h: amdspeech_lstm_bidir_*): named regions as tensor views.
+    precision: 0 = exact f32, 1 = bf16x3 (the recurrent and batched products as three bf16 MFMAs per product)."""
 
-    def __init__(self, T, B, H, L, device="cuda", _share=None):
+    def __init__(self, T, B, H, L, device="cuda", precision=0, _share=None):
         self.lib = _l.load()
-        self.desc = _l.LstmDesc(T, B, H, L, 1.0, 1.0, 0, 0)
+        self.desc = _l.LstmDesc(T, B, H, L, 1.0, 1.0, 0, precision)
         nbytes = self.lib.amdspeech_lstm_bidir_workspace_bytes(C.byref(self.desc))
         if nbytes == 0:
             raise _l.AmdSpeechError("lstm bidir workspace: " + self.lib.amdspeech_last_error().decode())
-        self.T, self.B, self.H, self.L = T, B, H, L
+        self.T, self.B, self.H, self.L, self.precision = T, B, H, L, precision
         if _share is None:
             self.buf = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
         else:
@@ -442,7 +443,7 @@ class BidirWorkspace(object):
         if ws is None:
             if len(self._prefixes) > 64:
                 self._prefixes.clear()
-            ws = BidirWorkspace(T_run, self.B, self.H, self.L, device=self.buf.device, _share=self.buf)
+            ws = BidirWorkspace(T_run, self.B, self.H, self.L, device=self.buf.device, precision=self.precision, _share=self.buf)
             ws._root = self
             self._prefixes[T_run] = ws
         return ws
