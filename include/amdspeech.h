@@ -308,6 +308,29 @@ int amdspeech_lstm_bwd_ctc(void* stream, const amdspeech_lstm_desc* d, void* ws,
  * checker can run the reference's graph with the very masks the kernels used.                                            */
 int amdspeech_lstm_dropout_multipliers(void* stream, const amdspeech_lstm_desc* d, int which, int layer, float* out);
 
+/* The kernel path lstm_fwd / lstm_bwd take for a descriptor, as plain numbers: a READ-ONLY view of the plan both calls make from
+ * (T, B, H, L, precision, flags) and the fused head's (C, U) -- C = U = 0: no head.  Nothing is launched and nothing is decided
+ * here; the query exists so that a test (or a log line) can name the kernel a shape runs instead of inferring it.  The whole-sequence
+ * and per-layer paths ask the device for its CU count: without an MI355X every shape answers DIAG / DIAG_BF3.
+ *   fwd_path, bwd_path  AMDSPEECH_LSTM_PATH_* below
+ *   nmt                 16-row batch tiles;  kb = H / 128 on the FLOW path (K blocks per wave and half), else 0
+ *   uw                  units per workgroup of the forward weight pack (launch-per-diagonal: 4 or 8; 16 elsewhere)
+ *   fwd_mt              16-row M tiles per workgroup of lstm_fwd_step (1 or 2)
+ *   mv, wpx             FLOW forward: x-product workers (K blocks per recurrence wave, 0: none), their workgroups per spare XCD
+ *   xw_parts            ... the tile history the workspace reserves for them (0 or 1)
+ *   nfw                 the fused CTC head's followers per spare XCD (0: no head, or the shape does not take it)
+ *   pair                two stacks of this shape run side by side (amdspeech_lstm_pair_fusable)
+ *   bf16p               the batched products of this call go through bf16 operand copies (precision 2, H = 1024, T * B a multiple
+ *                       of 64 and >= 256);  bf16p_reserved: the workspace holds room for them whatever T
+ *   w_pieces            FLOW backward: chunks of in-kernel weight-gradient work (0: none);  dz0_inkernel: dZ_0 formed in the kernel
+ *   flow2_q             FLOW backward: workgroups that share a K slice of the recurrent product (1, 2 or 4; 0 off that path)    */
+enum { AMDSPEECH_LSTM_PATH_FLOW = 0, AMDSPEECH_LSTM_PATH_BIG1 = 1, AMDSPEECH_LSTM_PATH_BIG = 2, AMDSPEECH_LSTM_PATH_HOIST = 3,
+       AMDSPEECH_LSTM_PATH_DIAG = 4, AMDSPEECH_LSTM_PATH_DIAG_BF3 = 5 };
+typedef struct amdspeech_lstm_plan_info {
+    int fwd_path, bwd_path, nmt, kb, mv, wpx, uw, fwd_mt, pair, bf16p, bf16p_reserved, xw_parts, nfw, w_pieces, dz0_inkernel, flow2_q;
+} amdspeech_lstm_plan_info;
+int amdspeech_lstm_plan(const amdspeech_lstm_desc* d, int C, int U, amdspeech_lstm_plan_info* out);
+
 /* ------------------------------------------------ layer-wise bidirectional stacks ----
  * tf.contrib.rnn.stack_bidirectional_dynamic_rnn (torch.nn.LSTM(bidirectional=True, num_layers=L)): L layers, each a forward and
  * a backward BasicLSTMCell (+ DropoutWrapper), where layer l+1 of BOTH directions reads the concatenation [h_fw_l ; h_bw_l].

@@ -1557,6 +1557,23 @@ extern "C" int amdspeech_lstm_bwd(void* stream, const amdspeech_lstm_desc* d, vo
 }
 
 /* The fused CTC head (ctc_flow.h) */
+// The plan as plain numbers (amdspeech.h: amdspeech_lstm_plan_info): reads lstm_plan, decides nothing
+extern "C" int amdspeech_lstm_plan(const amdspeech_lstm_desc* d, int C, int U, amdspeech_lstm_plan_info* out) {
+    if (int rc = check_desc(d)) return rc;
+    AS_CHECK_ARG(out != nullptr, "lstm_plan: null output");
+    AS_CHECK_ARG((C > 0 && U > 0) || (C == 0 && U == 0), "lstm_plan: head C=%d U=%d (both 0: no head)", C, U);
+    amdspeech_ctc_head h{};
+    h.C = C; h.U = U;
+    const LstmPlan p = lstm_plan(d, C > 0 ? &h : nullptr);
+    const bool flow_bwd = p.bwd == Path::flow;
+    static_assert((int)Path::flow == AMDSPEECH_LSTM_PATH_FLOW && (int)Path::big1 == AMDSPEECH_LSTM_PATH_BIG1 &&
+                  (int)Path::big == AMDSPEECH_LSTM_PATH_BIG && (int)Path::hoist == AMDSPEECH_LSTM_PATH_HOIST &&
+                  (int)Path::diag == AMDSPEECH_LSTM_PATH_DIAG && (int)Path::diag_bf3 == AMDSPEECH_LSTM_PATH_DIAG_BF3, "amdspeech.h");
+    *out = amdspeech_lstm_plan_info{(int)p.fwd, (int)p.bwd, p.nmt, p.fwd == Path::flow ? d->H / 128 : 0, p.mv, p.wpx, p.uw, p.fwd_mt,
+                                    p.pair ? 1 : 0, p.bf16p ? 1 : 0, p.bf16p_reserved ? 1 : 0, p.xw_parts, p.nfw, p.w_pieces,
+                                    p.dz0_inkernel, flow_bwd ? flow2_q(d->H / 128, d->precision) : 0};
+    return AMDSPEECH_OK;
+}
 extern "C" int amdspeech_lstm_ctc_fusable(const amdspeech_lstm_desc* d, int C, int U) {
     if (check_desc(d) != AMDSPEECH_OK) return 0;
     amdspeech_ctc_head h{};

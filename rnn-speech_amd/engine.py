@@ -162,6 +162,7 @@ class Engine(object):
             self.bn_scratch = torch.empty(2, max_T, hidden, device=self.device)       # cross-rank sums under data parallelism
         self._ws, self._Tr = self.lstm_ws, max_T
         self._head = None                # ops.CtcHead of the mini-batch in flight, when its CTC stage runs inside the LSTM launches
+        self._per_diagonal = False       # the last forward ran on the launch-per-diagonal kernels by request
         self._paired = False             # the last forward ran a bidirectional model's two stacks side by side (ops.lstm_fwd_pair)
         self._ws_b = self.lstm_ws_b if self.bidirectional and not self.layerwise else None
         self._layer_path = None          # (layer-wise mode) amdspeech_lstm_bidir_path of the last forward
@@ -254,6 +255,7 @@ class Engine(object):
             ops.reverse_sequences(ws.z0, lengths, out=wb.z0)
         # the CTC head inside the LSTM launches (ops.CtcHead; dense_labels given = a training mini-batch): the output layer, the
         # log-softmax and alpha follow the forward recurrence, beta and the gradient lead the backward one
+        self._per_diagonal = bool(per_diagonal)
         self._head = None
         if (dense_labels is not None and _FUSED_CTC and not self.bidirectional
                 and ops.lstm_ctc_fusable(ws, self.C, dense_labels.shape[1], per_diagonal=per_diagonal)):
@@ -323,8 +325,14 @@ class Engine(object):
     def kernel_path(self):
         """Which shape-driven choices the LAST forward made -- what a parity test has to assert before it may claim to have checked
         them: `fused_ctc_head` (the CTC stage ran inside the two whole-sequence LSTM launches, ops.CtcHead), `paired` (a
-        bidirectional model's two stacks side by side on one-XCD groups, ops.lstm_fwd_pair), `run_length` (frames visited)."""
+        bidirectional model's two stacks side by side on one-XCD groups, ops.lstm_fwd_pair), `run_length` (frames visited), and
+        `lstm_fwd` / `lstm_bwd`: the kernel path of that forward and of the backward that belongs to it ("flow", "big1", "big",
+        "hoist", "diag", "diag_bf3": ops.lstm_plan at the run length, with the head and the per-diagonal request of the call)."""
         path = {"fused_ctc_head": self._head is not None, "paired": self._paired, "run_length": self._Tr}
+        if not self.layerwise:
+            plan = ops.lstm_plan(self._ws, head=self._head, per_diagonal=self._per_diagonal)
+            # (side by side: ops.lstm_fwd_pair runs the one-XCD forward kernel whatever one stack alone would take)
+            path["lstm_fwd"], path["lstm_bwd"] = ("big1" if self._paired else plan["fwd_path"]), plan["bwd_path"]
         if self.layerwise:      # the layer-wise recurrence: "persistent" (one launch per layer for both directions, or per direction) or "per_frame"
             path["layer_recurrence"] = {2: "persistent", 1: "persistent_per_direction", 0: "per_frame"}.get(self._layer_path)
             path["layer_product"] = self.precision      # its recurrent product: "f32" (vector ALUs) or "bf16x3" (bf16 MFMA)

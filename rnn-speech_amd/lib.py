@@ -33,6 +33,12 @@ class CtcHead(C.Structure):          # amdspeech_ctc_head (include/amdspeech.h):
                 ("loss", C.c_void_p), ("dlogits", C.c_void_p), ("ctc_ws", C.c_void_p), ("C", C.c_int), ("U", C.c_int)]
 
 
+class LstmPlanInfo(C.Structure):     # amdspeech_lstm_plan_info (include/amdspeech.h): the kernel path of a descriptor, read-only
+    _fields_ = [(n, C.c_int) for n in ("fwd_path", "bwd_path", "nmt", "kb", "mv", "wpx", "uw", "fwd_mt", "pair", "bf16p", "bf16p_reserved",
+                                       "xw_parts", "nfw", "w_pieces", "dz0_inkernel", "flow2_q")]
+
+
+LSTM_PATHS = ("flow", "big1", "big", "hoist", "diag", "diag_bf3")      # AMDSPEECH_LSTM_PATH_* (include/amdspeech.h)
 LSTM_ARMED, LSTM_ARM_NEXT, LSTM_SAME_WS, LSTM_PER_DIAGONAL, LSTM_INJECT_TIMEOUT = 1, 2, 4, 8, 16      # amdspeech_lstm_desc.flags (include/amdspeech.h)
 
 
@@ -79,6 +85,7 @@ PROTOTYPES = {
     "amdspeech_lstm_fwd_ctc": (_I, [_P, C.POINTER(LstmDesc), _P, _P, _L, _P, _L, _P, _P, _P, C.POINTER(CtcHead)]),
     "amdspeech_lstm_bwd_ctc": (_I, [_P, C.POINTER(LstmDesc), _P, _P, _L, _P, _P, _L, _P, C.POINTER(CtcHead)]),
     "amdspeech_lstm_dropout_multipliers": (_I, [_P, C.POINTER(LstmDesc), _I, _I, _P]),
+    "amdspeech_lstm_plan": (_I, [C.POINTER(LstmDesc), _I, _I, C.POINTER(LstmPlanInfo)]),
     "amdspeech_lstm_bidir_workspace_bytes": (_SZ, [C.POINTER(LstmDesc)]),
     "amdspeech_lstm_bidir_ws_ptr": (_P, [C.POINTER(LstmDesc), _P, _I]),
     "amdspeech_lstm_bidir_layer_stride": (_L, [C.POINTER(LstmDesc)]),

@@ -278,6 +278,20 @@ def lstm_ctc_fusable(ws, C_, U, per_diagonal=False):
     return bool(ws.lib.amdspeech_lstm_ctc_fusable(C.byref(ws.desc), int(C_), int(U)))
 
 
+def lstm_plan(ws, head=None, per_diagonal=False):
+    """The kernel path lstm_fwd / lstm_bwd on this workspace layout take (amdspeech.h: amdspeech_lstm_plan), as a dict of ints with
+    "fwd_path" / "bwd_path" as names ("flow", "big1", "big", "hoist", "diag", "diag_bf3").  head: a CtcHead, or (C, U), or None.
+    Read-only: nothing is launched and the workspace's state is left alone."""
+    c_u = (0, 0) if head is None else ((head.c.C, head.c.U) if isinstance(head, CtcHead) else (int(head[0]), int(head[1])))
+    d = _l.LstmDesc(ws.desc.T, ws.desc.B, ws.desc.H, ws.desc.L, ws.desc.keep_in, ws.desc.keep_out, ws.desc.seed, ws.desc.precision,
+                    _l.LSTM_PER_DIAGONAL if per_diagonal else 0)
+    info = _l.LstmPlanInfo()
+    _l.check(ws.lib.amdspeech_lstm_plan(C.byref(d), c_u[0], c_u[1], C.byref(info)), "lstm_plan")
+    out = {name: int(getattr(info, name)) for name, _ in _l.LstmPlanInfo._fields_}
+    out["fwd_path"], out["bwd_path"] = _l.LSTM_PATHS[out["fwd_path"]], _l.LSTM_PATHS[out["bwd_path"]]
+    return out
+
+
 def lstm_fwd(ws, kernels, kernel_stride, biases, bias_stride, lengths, h0=None, c0=None, training=False, per_diagonal=False, head=None):
     """kernels/biases: tensors whose data_ptr is layer 0's K / bias; strides in elements.
     training: lstm_bwd on the same workspace follows; the call then prepares that call's hand-off panels and the next forward

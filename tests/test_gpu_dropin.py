@@ -82,6 +82,8 @@ def test_data_parallel_equals_mini_batch_accumulation(H):
     for eng, (x, ln, dn) in zip(ranks, batches):
         eng.zero_grads()
         eng.mini_batch(torch.as_tensor(x).cuda(), torch.as_tensor(ln).cuda(), torch.as_tensor(dn).cuda())
+        path, want = eng.kernel_path(), {32: "diag", 128: "flow"}[H]      # (what the ids say: the library's own plan, ops.lstm_plan)
+        assert (path["lstm_fwd"], path["lstm_bwd"]) == (want, want), (want, path)
     reduced = ranks[0].grads + ranks[1].grads                 # all-reduce(SUM)
     single = Engine(L, H, D, C, B, T, U, seed=9)
     single.zero_grads()

@@ -104,7 +104,8 @@ SHAPES = [
     (2, 256, 40, 80, 64, 70, 16, "f32"),       # dataflow kernels, all 8 XCDs carry a group, T >= 64: in-kernel GEMM workers
     (3, 512, 40, 80, 32, 24, 8, "f32"),        # BASELINE configs[1] shape, short in time
     (2, 1024, 120, 80, 40, 14, 6, "f32"),      # per-layer H = 1024 kernels (BASELINE configs[2] family)
-    (3, 128, 40, 80, 20, 40, 12, "bf16x3"),    # split precision inside the dataflow kernels
+    (3, 128, 40, 80, 20, 40, 12, "bf16x3"),    # split precision at H = 128: the bf16x3 step kernels (the dataflow kernels take it at H % 256 == 0)
+    (2, 256, 40, 80, 20, 40, 12, "bf16x3"),    # split precision inside the dataflow kernels
     (2, 1024, 120, 80, 40, 14, 6, "bf16x3"),   # split precision inside the per-layer kernels
     (2, 64, 20, 80, 5, 25, 10, "bf16x3"),      # split precision, launch-per-diagonal kernels
 ]
@@ -128,6 +129,11 @@ def test_dropout_on_training_step_matches_oracle(L, H, D, C, B, T, U, precision)
         eng.mini_batch(dx, dlen, dlab, keep_in, keep_out, seed=seed)
     torch.cuda.synchronize()
     eng.check()
+    # the kernel family the shape's comment names is the one the library planned (Engine.kernel_path: ops.lstm_plan)
+    want = {"f32": {64: "diag", 48: "diag", 128: "flow", 256: "flow", 512: "flow", 1024: "big"},
+            "bf16x3": {64: "diag_bf3", 128: "diag_bf3", 256: "flow", 1024: "big"}}[precision][H]
+    path = eng.kernel_path()
+    assert (path["lstm_fwd"], path["lstm_bwd"]) == (want, want), (want, path)
     in_masks, out_masks = engine_masks(eng._ws, L)          # (the descriptor still holds this step's keep / seed)
 
     p64 = {k: v.astype(np.float64) for k, v in p.items()}
@@ -167,6 +173,9 @@ def test_dropout_on_bidirectional_matches_oracle(L, H, B, T):
         eng.mini_batch(dx, dlen, dlab, 0.8, 0.5, seed=77)
     torch.cuda.synchronize()
     eng.check()
+    want = {128: "flow", 64: "diag", 1024: "big"}[H]      # (what the ids say)
+    path = eng.kernel_path()
+    assert (path["lstm_fwd"], path["lstm_bwd"]) == (want, want), (want, path)
     mf, mb = engine_masks(eng._ws, L), engine_masks(eng._ws_b, L)
     assert not np.array_equal(mf[0][0], mb[0][0])           # two streams
     logits_ref, cache = om.forward_bidirectional(p64, x.astype(np.float64), lengths, L, masks_fw=mf, masks_bw=mb)

@@ -40,6 +40,7 @@ def run():
     # what this module's oracle tests check is the DEFAULT path of the headline shape: the CTC stage inside the two LSTM launches.
     # (At B = 32 the fusable bound is met with equality -- a change of the worker plan must not turn these into tests of the fallback)
     assert eng.kernel_path()["fused_ctc_head"] and eng._head is not None
+    assert (eng.kernel_path()["lstm_fwd"], eng.kernel_path()["lstm_bwd"]) == ("flow", "flow")      # (the library's own plan: ops.lstm_plan)
     return dict(eng=eng, x=x, lengths=lengths, dense=dense, dx=dx, dlen=dlen, dlab=dlab,
                 logits=eng.logits.cpu().numpy().copy(), loss=eng.loss.cpu().numpy().copy(),
                 grads=eng.grads.clone())

@@ -1,6 +1,8 @@
 """GPU tests at BASELINE.json configs[2] full size (5x1024 LSTM, 120-dim fbank+delta+delta-delta, batch 64,
 T = 998 frames = 10 s at 16 kHz): logits, CTC loss and EVERY gradient tensor against the float64 oracle on a
 live pair of utterances, and the fbank front end at B = 64 x 10 s against the oracle."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -121,6 +123,7 @@ def test_cfg5_bidirectional_bf16x3_full_length_matches_oracle():
     torch.cuda.synchronize()
     eng.check()
     assert not eng.kernel_path()["paired"]       # (split precision keeps W_hh on XCD pairs: two calls, lstm_fwd_big<1> / lstm_bwd_big<1>)
+    assert (eng.kernel_path()["lstm_fwd"], eng.kernel_path()["lstm_bwd"]) == ("big", "big")
     assert _rel(eng.logits.cpu().numpy()[:, sel, :], logits_ref) < 1e-3          # north_star's bound; f32 path: 1e-4
     np.testing.assert_allclose(eng.loss.cpu().numpy()[sel], loss_ref, rtol=1e-3)
     g = eng.to_numpy(eng.grads)
@@ -168,6 +171,11 @@ def test_cfg5_plain_bf16_error_over_998_frames_is_what_the_study_says(bidirectio
     # the kernels this test is about: both stacks' layers side by side on one-XCD groups (lstm_fwd_big1 / lstm_bwd_big1<4> through
     # amdspeech_lstm_fwd_pair / _bwd_pair) when bidirectional, never for one stack
     assert eng.kernel_path()["paired"] == bidirectional
+    # ... by the library's own plan (ops.lstm_plan).  One stack alone runs forward on the XCD pairs; its backward recurrence takes
+    # the one-XCD kernel whenever the bf16 operand copies are used (the switch test below runs this case without them)
+    copies = os.environ.get("AMDSPEECH_BF16_PACKED", "1") != "0"
+    assert eng.kernel_path()["lstm_fwd"] == ("big1" if bidirectional else "big")
+    assert eng.kernel_path()["lstm_bwd"] == ("big1" if copies else "big")
     e_logits = _rel(eng.logits.cpu().numpy()[:, sel, :], logits_ref)
     assert 2e-4 < e_logits < 5e-3, e_logits            # (really bf16: the split-precision mode sits at 3e-6)
     np.testing.assert_allclose(eng.loss.cpu().numpy()[sel], loss_ref, rtol=1e-3)
