@@ -396,6 +396,20 @@ int amdspeech_ctc_loss_fwd_bwd_staged(void* stream, const float* logits, const i
                                       const int* lengths, int T, int B, int C, int U, float* loss,
                                       float* dlogits, void* ws, int stage);
 
+/* The recursion kernel the call above takes for a shape, as plain numbers: a READ-ONLY view of the choice the launch itself reads
+ * (one function decides for both).  Nothing is launched; the arguments are checked as the call checks them (C in 2 .. 4096,
+ * U in 1 .. 2559: anything else is AMDSPEECH_EINVAL with a message, here and there).  Honours AMDSPEECH_CTC_SHIFT / AMDSPEECH_CTC_PAIR.
+ *   kernel   AMDSPEECH_CTC_KERNEL_* below: WAVE one wavefront per (utterance, direction), up to 128 extended states; SHIFT the
+ *            DPP-shift kernel with the float64 state (129 .. 384 states); PAIR two frames per LDS exchange (.. 512 states; the
+ *            default from 385, and from 129 with AMDSPEECH_CTC_SHIFT=0); EDGE one LDS edge exchange per frame, `rmax` states per
+ *            thread (2 only with AMDSPEECH_CTC_PAIR=0, 4 to 1024 states, 8 to 2048, 20 to 5119)
+ *   threads  per (utterance, direction): 64 or 256;  rmax: states a thread can hold;  smax = 2 U + 1: pitch of the extended targets */
+enum { AMDSPEECH_CTC_KERNEL_WAVE = 0, AMDSPEECH_CTC_KERNEL_SHIFT = 1, AMDSPEECH_CTC_KERNEL_PAIR = 2, AMDSPEECH_CTC_KERNEL_EDGE = 3 };
+typedef struct amdspeech_ctc_plan_info {
+    int kernel, threads, rmax, smax;
+} amdspeech_ctc_plan_info;
+int amdspeech_ctc_plan(int T, int B, int C, int U, amdspeech_ctc_plan_info* out);
+
 /* Greedy decode: per-frame argmax (first maximum), collapse repeats, drop the
  * blank C-1.  Stands where tf.nn.ctc_beam_search_decoder sits at
  * models/AcousticModel.py:312.  ids [B,T] is padded with C (the

@@ -86,8 +86,9 @@ __global__ __launch_bounds__(NW * 64) void ctc_alpha_beta_kernel(const float* __
                                                                  float* __restrict__ beta, float* __restrict__ ll) {
     static_assert(RMAX >= 2, "RMAX >= 2");
     constexpr int NT = NW * 64;
-    __shared__ float2 edge[2][NT + 4];       // [parity][2 + thread]: pads of NEG_INF at both ends
-    __shared__ float fin[NT];
+    __shared__ double2 edge[2][NT + 4];      // [parity][2 + thread]: pads of -inf at both ends
+    __shared__ double fin[NT];
+    constexpr double NEG_INF_D = -__builtin_inf();
     const int b = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x;
     if (!valid[b]) { if (dir == 0 && tid == 0) ll[b] = 0.f; return; }
     const int S = slen[b];
@@ -106,21 +107,24 @@ __global__ __launch_bounds__(NW * 64) void ctc_alpha_beta_kernel(const float* __
     }
     if (tid < 4) {
         const int slot = tid < 2 ? tid : NT + tid;            // 0, 1, NT+2, NT+3
-        edge[0][slot] = make_float2(NEG_INF, NEG_INF);
-        edge[1][slot] = make_float2(NEG_INF, NEG_INF);
+        edge[0][slot] = make_double2(NEG_INF_D, NEG_INF_D);
+        edge[1][slot] = make_double2(NEG_INF_D, NEG_INF_D);
     }
     const size_t rowstride = (size_t)B * C;
     const float* lp = logp + (size_t)b * C;
     float* out = (dir == 0 ? alpha : beta) + (size_t)b * T * smax;
 
-    float cur[RMAX];
+    // The recursion STATE is float64, the transcendentals float32 on the differences to the maximum (lse3_2d, ctc_core.h): a float32
+    // state rounds every log-sum-exp at the state's magnitude -- 2e-4 .. 5e-4 once |alpha| passes 2^11 log2 units, i.e. after a few
+    // hundred frames -- and dlogits then sits 3e-3 .. 7e-3 from float64 at T >= 1000 (tests/ctc_ref.py).  What is stored is rounded once.
+    double cur[RMAX];
     // ---- step 0
 #pragma unroll
     for (int r = 0; r < RMAX; ++r) {
         const int s = tid * R + r;
-        if (dir == 0) cur[r] = (act[r] && s < 2) ? lp[lab[r]] * LOG2E : NEG_INF;          // alpha_0
-        else cur[r] = (act[r] && (s == S - 1 || s == S - 2)) ? 0.f : NEG_INF;               // beta_{Tb-1} (excludes y_t)
-        if (act[r]) out[(size_t)(dir == 0 ? 0 : Tb - 1) * smax + s] = cur[r] * LN2;
+        if (dir == 0) cur[r] = (act[r] && s < 2) ? (double)(lp[lab[r]] * LOG2E) : NEG_INF_D;   // alpha_0
+        else cur[r] = (act[r] && (s == S - 1 || s == S - 2)) ? 0.0 : NEG_INF_D;             // beta_{Tb-1} (excludes y_t)
+        if (act[r]) out[(size_t)(dir == 0 ? 0 : Tb - 1) * smax + s] = (float)cur[r] * LN2;
     }
 
     auto load_block = [&](int i0, float (&buf)[PF][RMAX]) {
@@ -133,52 +137,52 @@ __global__ __launch_bounds__(NW * 64) void ctc_alpha_beta_kernel(const float* __
         }
     };
     auto step = [&](int i, const float (&lpv)[RMAX]) {
-        float newv[RMAX];
-        float2* ed = edge[i & 1] + 2;                           // ed[thread]
+        double newv[RMAX];
+        double2* ed = edge[i & 1] + 2;                          // ed[thread]
         if (dir == 0) {
             // publish this thread's last two states of the previous frame: (s_last, s_last - 1)
-            float last1 = cur[0], last2 = NEG_INF;
+            double last1 = cur[0], last2 = NEG_INF_D;
 #pragma unroll
             for (int r = 1; r < RMAX; ++r) if (r < R) { last2 = last1; last1 = cur[r]; }
-            ed[tid] = make_float2(last1, last2);
+            ed[tid] = make_double2(last1, last2);
             ctc_frame_barrier();
-            const float2 n1 = ed[tid - 1];
-            float p1 = n1.x;                                      // alpha_{t-1}(s-1) for r = 0
-            float p2 = (R == 1) ? ed[tid - 2].x : n1.y;           // alpha_{t-1}(s-2) for r = 0
+            const double2 n1 = ed[tid - 1];
+            double p1 = n1.x;                                     // alpha_{t-1}(s-1) for r = 0
+            double p2 = (R == 1) ? ed[tid - 2].x : n1.y;          // alpha_{t-1}(s-2) for r = 0
 #pragma unroll
             for (int r = 0; r < RMAX; ++r) {
                 if (r < R) {
-                    const float v = lse3_2(cur[r], p1, skip[r] ? p2 : NEG_INF) + lpv[r];
-                    newv[r] = act[r] ? v : NEG_INF;
+                    const double v = lse3_2d(cur[r], p1, skip[r] ? p2 : NEG_INF_D) + (double)lpv[r];
+                    newv[r] = act[r] ? v : NEG_INF_D;
                     p2 = p1; p1 = cur[r];
-                } else newv[r] = NEG_INF;
+                } else newv[r] = NEG_INF_D;
             }
         } else {
-            float nb[RMAX];   // beta_{t+1}(s) + logp_{t+1}(l'_s)
+            double nb[RMAX];  // beta_{t+1}(s) + logp_{t+1}(l'_s)
 #pragma unroll
-            for (int r = 0; r < RMAX; ++r) nb[r] = act[r] ? cur[r] + lpv[r] : NEG_INF;
+            for (int r = 0; r < RMAX; ++r) nb[r] = act[r] ? cur[r] + (double)lpv[r] : NEG_INF_D;
             // publish this thread's first two states: (s_first, s_first + 1)
-            ed[tid] = make_float2(nb[0], R >= 2 ? nb[1] : NEG_INF);
+            ed[tid] = make_double2(nb[0], R >= 2 ? nb[1] : NEG_INF_D);
             ctc_frame_barrier();
-            const float2 m1 = ed[tid + 1];
-            const float dn1 = m1.x;
-            const float dn2 = (R == 1) ? ed[tid + 2].x : m1.y;
+            const double2 m1 = ed[tid + 1];
+            const double dn1 = m1.x;
+            const double dn2 = (R == 1) ? ed[tid + 2].x : m1.y;
 #pragma unroll
             for (int r = 0; r < RMAX; ++r) {
                 if (r < R) {
                     // neighbours s+1, s+2: in-thread while r+1 / r+2 < R, else thread+1's states 0 / 1
-                    const float in1 = nb[(r + 1 < RMAX) ? r + 1 : 0];
-                    const float in2 = nb[(r + 2 < RMAX) ? r + 2 : 0];
-                    const float n1 = (r + 1 < R) ? in1 : dn1;
-                    const float n2 = (r + 2 < R) ? in2 : ((r + 1 < R) ? dn1 : dn2);
-                    const float v = lse3_2(nb[r], n1, skip[r] ? n2 : NEG_INF);
-                    newv[r] = act[r] ? v : NEG_INF;
-                } else newv[r] = NEG_INF;
+                    const double in1 = nb[(r + 1 < RMAX) ? r + 1 : 0];
+                    const double in2 = nb[(r + 2 < RMAX) ? r + 2 : 0];
+                    const double n1 = (r + 1 < R) ? in1 : dn1;
+                    const double n2 = (r + 2 < R) ? in2 : ((r + 1 < R) ? dn1 : dn2);
+                    const double v = lse3_2d(nb[r], n1, skip[r] ? n2 : NEG_INF_D);
+                    newv[r] = act[r] ? v : NEG_INF_D;
+                } else newv[r] = NEG_INF_D;
             }
         }
         float* o = out + (size_t)(dir == 0 ? i : Tb - 1 - i) * smax;
 #pragma unroll
-        for (int r = 0; r < RMAX; ++r) { cur[r] = newv[r]; if (act[r]) o[tid * R + r] = cur[r] * LN2; }
+        for (int r = 0; r < RMAX; ++r) { cur[r] = newv[r]; if (act[r]) o[tid * R + r] = (float)(cur[r] * (double)LN2); }
     };
 
     if (Tb > 1) {
@@ -195,21 +199,21 @@ __global__ __launch_bounds__(NW * 64) void ctc_alpha_beta_kernel(const float* __
     }
     if (dir == 0) {
         // log p(l|x) = lse(alpha_{Tb-1}(S-1), alpha_{Tb-1}(S-2))
-        float mine = NEG_INF;
+        double mine = NEG_INF_D;
 #pragma unroll
         for (int r = 0; r < RMAX; ++r) {
             const int s = tid * R + r;
-            if (act[r] && (s == S - 1 || s == S - 2)) mine = lse3_2(mine, cur[r], NEG_INF);
+            if (act[r] && (s == S - 1 || s == S - 2)) mine = lse2_2d(mine, cur[r]);
         }
         fin[tid] = mine;
         __syncthreads();
         if (tid < 64) {
-            float tot = NEG_INF;
+            double tot = NEG_INF_D;
 #pragma unroll
-            for (int w = 0; w < NW; ++w) tot = lse3_2(tot, fin[w * 64 + tid], NEG_INF);
+            for (int w = 0; w < NW; ++w) tot = lse2_2d(tot, fin[w * 64 + tid]);
 #pragma unroll
-            for (int o2 = 32; o2 > 0; o2 >>= 1) tot = lse3_2(tot, __shfl_xor(tot, o2), NEG_INF);
-            if (tid == 0) ll[b] = tot * LN2;
+            for (int o2 = 32; o2 > 0; o2 >>= 1) tot = lse2_2d(tot, __shfl_xor(tot, o2));
+            if (tid == 0) ll[b] = (float)(tot * (double)LN2);
         }
     }
 }
@@ -230,8 +234,9 @@ __global__ __launch_bounds__(256) void ctc_alpha_beta2_kernel(const float* __res
                                                               float* __restrict__ beta, float* __restrict__ ll) {
     static_assert(PF % 2 == 0, "PF even");
     constexpr int NT = 256;
-    __shared__ float2 edge[2][NT + 2];       // [parity][2 + thread]: two pads of NEG_INF in front
-    __shared__ float fin[NT];
+    __shared__ double2 edge[2][NT + 2];      // [parity][2 + thread]: two pads of -inf in front
+    __shared__ double fin[NT];
+    constexpr double NEG_INF_D = -__builtin_inf();
     const int b = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x;
     if (!valid[b]) { if (dir == 0 && tid == 0) ll[b] = 0.f; return; }
     const int S = slen[b];
@@ -248,21 +253,21 @@ __global__ __launch_bounds__(256) void ctc_alpha_beta2_kernel(const float* __res
         lab[k] = act[k] ? e[sidx[k]] : blank;
         skip[k] = act[k] && r >= 2 && lab[k] != blank && lab[k] != e[dir == 0 ? r - 2 : S + 1 - r];
     }
-    if (tid < 2) { edge[0][tid] = make_float2(NEG_INF, NEG_INF); edge[1][tid] = make_float2(NEG_INF, NEG_INF); }
+    if (tid < 2) { edge[0][tid] = make_double2(NEG_INF_D, NEG_INF_D); edge[1][tid] = make_double2(NEG_INF_D, NEG_INF_D); }
     const size_t rowstride = (size_t)B * C;
     const float* lp = logp + (size_t)b * C;
     float* out = (dir == 0 ? alpha : beta) + (size_t)b * T * smax;
     auto frame = [&](int i) { return dir == 0 ? i : Tb - 1 - i; };   // recursion step -> frame
 
     // ---- step 0
-    float cur0, cur1;
+    double cur0, cur1;      // the state is float64 (see ctc_alpha_beta_kernel); what is stored is rounded once
     {
         const float* l0 = lp + (size_t)frame(0) * rowstride;
-        cur0 = (act[2] && 2 * tid < 2) ? l0[lab[2]] * LOG2E : NEG_INF;
-        cur1 = (act[3] && 2 * tid + 1 < 2) ? l0[lab[3]] * LOG2E : NEG_INF;
+        cur0 = (act[2] && 2 * tid < 2) ? (double)(l0[lab[2]] * LOG2E) : NEG_INF_D;
+        cur1 = (act[3] && 2 * tid + 1 < 2) ? (double)(l0[lab[3]] * LOG2E) : NEG_INF_D;
         float* o = out + (size_t)frame(0) * smax;
-        if (act[2]) o[sidx[2]] = dir == 0 ? cur0 * LN2 : (2 * tid < 2 ? 0.f : NEG_INF);
-        if (act[3]) o[sidx[3]] = dir == 0 ? cur1 * LN2 : (2 * tid + 1 < 2 ? 0.f : NEG_INF);
+        if (act[2]) o[sidx[2]] = dir == 0 ? (float)cur0 * LN2 : (2 * tid < 2 ? 0.f : NEG_INF);
+        if (act[3]) o[sidx[3]] = dir == 0 ? (float)cur1 * LN2 : (2 * tid + 1 < 2 ? 0.f : NEG_INF);
     }
     // emissions of a block of PF steps: own two states every step, the halo's two for the first step of every pair
     auto load_block = [&](int i0, float (&own)[PF][2], float (&halo)[PF / 2][2]) {
@@ -283,39 +288,39 @@ __global__ __launch_bounds__(256) void ctc_alpha_beta2_kernel(const float* __res
     // steps i and i+1 (the second only if it exists)
     auto pair = [&](int i, const float (&o0)[2], const float (&o1)[2], const float (&h)[2]) {
 #if CTC_DIAG == 3
-        const float2 e1 = make_float2(cur1 - 1.f, cur0 - 2.f), e2 = make_float2(cur0 - 3.f, cur1 - 1.5f);
+        const double2 e1 = make_double2(cur1 - 1., cur0 - 2.), e2 = make_double2(cur0 - 3., cur1 - 1.5);
 #else
-        edge[par][2 + tid] = make_float2(cur0, cur1);
+        edge[par][2 + tid] = make_double2(cur0, cur1);
         ctc_frame_barrier();
-        const float2 e1 = edge[par][2 + tid - 1], e2 = edge[par][2 + tid - 2];      // states 2tid-2, 2tid-1 and 2tid-4, 2tid-3
+        const double2 e1 = edge[par][2 + tid - 1], e2 = edge[par][2 + tid - 2];      // states 2tid-2, 2tid-1 and 2tid-4, 2tid-3
 #endif
         par ^= 1;
         // step i: the halo's two states and this thread's two
-        const float vh0 = lse3_2(e1.x, e2.y, skip[0] ? e2.x : NEG_INF);
-        const float vh1 = lse3_2(e1.y, e1.x, skip[1] ? e2.y : NEG_INF);
-        const float v0 = lse3_2(cur0, e1.y, skip[2] ? e1.x : NEG_INF);
-        const float v1 = lse3_2(cur1, cur0, skip[3] ? e1.y : NEG_INF);
-        const float hn0 = act[0] ? vh0 + h[0] * LOG2E : NEG_INF;
-        const float hn1 = act[1] ? vh1 + h[1] * LOG2E : NEG_INF;
-        const float n0 = act[2] ? v0 + o0[0] * LOG2E : NEG_INF;
-        const float n1 = act[3] ? v1 + o0[1] * LOG2E : NEG_INF;
+        const double vh0 = lse3_2d(e1.x, e2.y, skip[0] ? e2.x : NEG_INF_D);
+        const double vh1 = lse3_2d(e1.y, e1.x, skip[1] ? e2.y : NEG_INF_D);
+        const double v0 = lse3_2d(cur0, e1.y, skip[2] ? e1.x : NEG_INF_D);
+        const double v1 = lse3_2d(cur1, cur0, skip[3] ? e1.y : NEG_INF_D);
+        const double hn0 = act[0] ? vh0 + (double)(h[0] * LOG2E) : NEG_INF_D;
+        const double hn1 = act[1] ? vh1 + (double)(h[1] * LOG2E) : NEG_INF_D;
+        const double n0 = act[2] ? v0 + (double)(o0[0] * LOG2E) : NEG_INF_D;
+        const double n1 = act[3] ? v1 + (double)(o0[1] * LOG2E) : NEG_INF_D;
 #if CTC_DIAG != 1
         {
             float* o = out + (size_t)frame(i) * smax;
-            if (act[2]) o[sidx[2]] = (dir == 0 ? n0 : v0) * LN2;
-            if (act[3]) o[sidx[3]] = (dir == 0 ? n1 : v1) * LN2;
+            if (act[2]) o[sidx[2]] = (float)((dir == 0 ? n0 : v0) * (double)LN2);
+            if (act[3]) o[sidx[3]] = (float)((dir == 0 ? n1 : v1) * (double)LN2);
         }
 #endif
         cur0 = n0; cur1 = n1;
         if (i + 1 < Tb) {
-            const float w0 = lse3_2(n0, hn1, skip[2] ? hn0 : NEG_INF);
-            const float w1 = lse3_2(n1, n0, skip[3] ? hn1 : NEG_INF);
-            const float m0 = act[2] ? w0 + o1[0] * LOG2E : NEG_INF;
-            const float m1 = act[3] ? w1 + o1[1] * LOG2E : NEG_INF;
+            const double w0 = lse3_2d(n0, hn1, skip[2] ? hn0 : NEG_INF_D);
+            const double w1 = lse3_2d(n1, n0, skip[3] ? hn1 : NEG_INF_D);
+            const double m0 = act[2] ? w0 + (double)(o1[0] * LOG2E) : NEG_INF_D;
+            const double m1 = act[3] ? w1 + (double)(o1[1] * LOG2E) : NEG_INF_D;
 #if CTC_DIAG != 1
             float* o = out + (size_t)frame(i + 1) * smax;
-            if (act[2]) o[sidx[2]] = (dir == 0 ? m0 : w0) * LN2;
-            if (act[3]) o[sidx[3]] = (dir == 0 ? m1 : w1) * LN2;
+            if (act[2]) o[sidx[2]] = (float)((dir == 0 ? m0 : w0) * (double)LN2);
+            if (act[3]) o[sidx[3]] = (float)((dir == 0 ? m1 : w1) * (double)LN2);
 #endif
             cur0 = m0; cur1 = m1;
         }
@@ -334,18 +339,18 @@ __global__ __launch_bounds__(256) void ctc_alpha_beta2_kernel(const float* __res
     }
     if (dir == 0) {
         // log p(l|x) = lse(alpha_{Tb-1}(S-1), alpha_{Tb-1}(S-2))
-        float mine = NEG_INF;
-        if (act[2] && (2 * tid == S - 1 || 2 * tid == S - 2)) mine = lse3_2(mine, cur0, NEG_INF);
-        if (act[3] && (2 * tid + 1 == S - 1 || 2 * tid + 1 == S - 2)) mine = lse3_2(mine, cur1, NEG_INF);
+        double mine = NEG_INF_D;
+        if (act[2] && (2 * tid == S - 1 || 2 * tid == S - 2)) mine = lse2_2d(mine, cur0);
+        if (act[3] && (2 * tid + 1 == S - 1 || 2 * tid + 1 == S - 2)) mine = lse2_2d(mine, cur1);
         fin[tid] = mine;
         __syncthreads();
         if (tid < 64) {
-            float tot = NEG_INF;
+            double tot = NEG_INF_D;
 #pragma unroll
-            for (int w = 0; w < 4; ++w) tot = lse3_2(tot, fin[w * 64 + tid], NEG_INF);
+            for (int w = 0; w < 4; ++w) tot = lse2_2d(tot, fin[w * 64 + tid]);
 #pragma unroll
-            for (int o2 = 32; o2 > 0; o2 >>= 1) tot = lse3_2(tot, __shfl_xor(tot, o2), NEG_INF);
-            if (tid == 0) ll[b] = tot * LN2;
+            for (int o2 = 32; o2 > 0; o2 >>= 1) tot = lse2_2d(tot, __shfl_xor(tot, o2));
+            if (tid == 0) ll[b] = (float)(tot * (double)LN2);
         }
     }
 }
@@ -689,6 +694,36 @@ extern "C" size_t amdspeech_ctc_workspace_bytes(int T, int B, int C, int U) {
     return ctc_layout(T, B, C, U).total;
 }
 
+// ---- which recursion kernel a shape takes: the ONE place that decides (the launch below and amdspeech_ctc_plan read it) ----
+namespace amdspeech {
+struct CtcPlan { int kernel, threads, rmax, smax; };      // amdspeech_ctc_plan_info (amdspeech.h)
+static int ctc_plan(int T, int B, int C, int U, CtcPlan* p) {
+    AS_CHECK_ARG(T > 0 && B > 0 && C > 1 && U > 0, "ctc: bad shape T=%d B=%d C=%d U=%d", T, B, C, U);
+    AS_CHECK_ARG(C <= 4096, "ctc: C=%d too large", C);
+    const int smax = 2 * U + 1;
+    AS_CHECK_ARG(U <= 2559 && smax <= 256 * 20, "ctc: label width U=%d exceeds the supported 2559", U);
+    // 4 waves per (utterance, direction) once the targets are long enough to feed them
+    const bool wide = smax > 128;
+    const int rneed = ceil_div(smax, wide ? 256 : 64);
+    if (!wide) { *p = CtcPlan{AMDSPEECH_CTC_KERNEL_WAVE, 64, 2, smax}; return AMDSPEECH_OK; }
+    static const int two = runtime_switch("AMDSPEECH_CTC_PAIR", 1);      // 0: one frame per exchange
+    static const int shift = runtime_switch("AMDSPEECH_CTC_SHIFT", 1);   // 0: the LDS-exchange kernels
+    if (smax <= 384 && shift) *p = CtcPlan{AMDSPEECH_CTC_KERNEL_SHIFT, 256, 2, smax};
+    else if (rneed <= 2 && two) *p = CtcPlan{AMDSPEECH_CTC_KERNEL_PAIR, 256, 2, smax};
+    else *p = CtcPlan{AMDSPEECH_CTC_KERNEL_EDGE, 256, rneed <= 2 ? 2 : rneed <= 4 ? 4 : rneed <= 8 ? 8 : 20, smax};
+    return AMDSPEECH_OK;
+}
+}  // namespace amdspeech
+
+// The plan as plain numbers (amdspeech.h: amdspeech_ctc_plan_info): reads ctc_plan, launches nothing
+extern "C" int amdspeech_ctc_plan(int T, int B, int C, int U, amdspeech_ctc_plan_info* out) {
+    AS_CHECK_ARG(out != nullptr, "ctc_plan: null output");
+    CtcPlan p;
+    if (int rc = ctc_plan(T, B, C, U, &p)) return rc;
+    *out = amdspeech_ctc_plan_info{p.kernel, p.threads, p.rmax, p.smax};
+    return AMDSPEECH_OK;
+}
+
 extern "C" int amdspeech_ctc_loss_fwd_bwd(void* stream, const float* logits, const int* dense_labels,
                                           const int* lengths, int T, int B, int C, int U, float* loss,
                                           float* dlogits, void* ws) {
@@ -699,12 +734,11 @@ extern "C" int amdspeech_ctc_loss_fwd_bwd_staged(void* stream, const float* logi
                                                  const int* lengths, int T, int B, int C, int U, float* loss,
                                                  float* dlogits, void* ws, int stage) {
     AS_CHECK_ARG(stage >= 0 && stage <= 2, "ctc: stage %d", stage);
-    AS_CHECK_ARG(T > 0 && B > 0 && C > 1 && U > 0, "ctc: bad shape T=%d B=%d C=%d U=%d", T, B, C, U);
+    CtcPlan plan;
+    if (int rc = ctc_plan(T, B, C, U, &plan)) return rc;
     AS_CHECK_ARG(logits && dense_labels && lengths && loss && dlogits && ws, "ctc: null pointer");
-    AS_CHECK_ARG(C <= 4096, "ctc: C=%d too large", C);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const CtcLayout lo = ctc_layout(T, B, C, U);
-    AS_CHECK_ARG(lo.smax <= 256 * 20, "ctc: label width U=%d exceeds the supported 2559", U);
     char* w = static_cast<char*>(ws);
     float* logp = reinterpret_cast<float*>(w + lo.logp);
     float* alpha = reinterpret_cast<float*>(w + lo.alpha);
@@ -720,23 +754,17 @@ extern "C" int amdspeech_ctc_loss_fwd_bwd_staged(void* stream, const float* logi
         AS_CHECK_LAUNCH();
         if (stage == 1) return AMDSPEECH_OK;
     }
-    // 4 waves per (utterance, direction) once the targets are long enough to feed them
-    const bool wide = lo.smax > 128;
-    const int rneed = ceil_div(lo.smax, wide ? 256 : 64);
     dim3 grid(B, 2);
 #define LAUNCH_AB(R, PF, NW) hipLaunchKernelGGL((ctc_alpha_beta_kernel<R, PF, NW>), grid, dim3(NW * 64), 0, s, logp, ext, slen, valid, lengths, T, B, C, lo.smax, alpha, beta, ll)
-    if (wide) {
-        static const int two = runtime_switch("AMDSPEECH_CTC_PAIR", 1);      // 0: one frame per exchange
-        static const int shift = runtime_switch("AMDSPEECH_CTC_SHIFT", 1);   // 0: the LDS-exchange kernels
-        if (lo.smax <= 384 && shift)
-            hipLaunchKernelGGL((ctc_alpha_beta3_kernel<8>), grid, dim3(256), 0, s, logp, ext, slen, valid, lengths, T, B, C, lo.smax, alpha, beta, ll);
-        else if (rneed <= 2 && two)
-            hipLaunchKernelGGL((ctc_alpha_beta2_kernel<8>), grid, dim3(256), 0, s, logp, ext, slen, valid, lengths, T, B, C, lo.smax, alpha, beta, ll);
-        else if (rneed <= 2) LAUNCH_AB(2, 8, 4);
-        else if (rneed <= 4) LAUNCH_AB(4, 8, 4);
-        else if (rneed <= 8) LAUNCH_AB(8, 4, 4);
-        else LAUNCH_AB(20, 4, 4);
-    } else LAUNCH_AB(2, 8, 1);
+    if (plan.kernel == AMDSPEECH_CTC_KERNEL_SHIFT)
+        hipLaunchKernelGGL((ctc_alpha_beta3_kernel<8>), grid, dim3(256), 0, s, logp, ext, slen, valid, lengths, T, B, C, lo.smax, alpha, beta, ll);
+    else if (plan.kernel == AMDSPEECH_CTC_KERNEL_PAIR)
+        hipLaunchKernelGGL((ctc_alpha_beta2_kernel<8>), grid, dim3(256), 0, s, logp, ext, slen, valid, lengths, T, B, C, lo.smax, alpha, beta, ll);
+    else if (plan.kernel == AMDSPEECH_CTC_KERNEL_EDGE && plan.rmax == 2) LAUNCH_AB(2, 8, 4);
+    else if (plan.kernel == AMDSPEECH_CTC_KERNEL_EDGE && plan.rmax == 4) LAUNCH_AB(4, 8, 4);
+    else if (plan.kernel == AMDSPEECH_CTC_KERNEL_EDGE && plan.rmax == 8) LAUNCH_AB(8, 4, 4);
+    else if (plan.kernel == AMDSPEECH_CTC_KERNEL_EDGE) LAUNCH_AB(20, 4, 4);
+    else LAUNCH_AB(2, 8, 1);
 #undef LAUNCH_AB
     hipLaunchKernelGGL(ctc_grad_kernel, dim3(ceil_div(rows, 4)), dim3(256), 4 * C * sizeof(float), s, logp, alpha, beta,
                        ext, slen, valid, lengths, ll, T, B, C, lo.smax, dlogits, loss);

@@ -38,6 +38,11 @@ class LstmPlanInfo(C.Structure):     # amdspeech_lstm_plan_info (include/amdspee
                                        "xw_parts", "nfw", "w_pieces", "dz0_inkernel", "flow2_q")]
 
 
+class CtcPlanInfo(C.Structure):      # amdspeech_ctc_plan_info (include/amdspeech.h): the recursion kernel of a CTC shape, read-only
+    _fields_ = [(n, C.c_int) for n in ("kernel", "threads", "rmax", "smax")]
+
+
+CTC_KERNELS = ("wave", "shift", "pair", "edge")      # AMDSPEECH_CTC_KERNEL_* (include/amdspeech.h)
 LSTM_PATHS = ("flow", "big1", "big", "hoist", "diag", "diag_bf3")      # AMDSPEECH_LSTM_PATH_* (include/amdspeech.h)
 LSTM_ARMED, LSTM_ARM_NEXT, LSTM_SAME_WS, LSTM_PER_DIAGONAL, LSTM_INJECT_TIMEOUT = 1, 2, 4, 8, 16      # amdspeech_lstm_desc.flags (include/amdspeech.h)
 
@@ -95,6 +100,7 @@ PROTOTYPES = {
     "amdspeech_lstm_bidir_status": (_I, [C.POINTER(LstmDesc), _P]),
     "amdspeech_lstm_bidir_dropout_multipliers": (_I, [_P, C.POINTER(LstmDesc), _I, _I, _I, _P]),
     "amdspeech_ctc_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "amdspeech_ctc_plan": (_I, [_I, _I, _I, _I, C.POINTER(CtcPlanInfo)]),
     "amdspeech_ctc_loss_fwd_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "amdspeech_ctc_loss_fwd_bwd_staged": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I]),
     "amdspeech_ctc_greedy_decode": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),

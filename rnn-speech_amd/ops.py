@@ -562,6 +562,16 @@ class CtcWorkspace(object):
         self.greedy_ws = torch.empty(T * B, device=device, dtype=torch.int32)
 
 
+def ctc_plan(T, B, C_, U):
+    """The recursion kernel ctc_loss_fwd_bwd takes for a shape (amdspeech.h: amdspeech_ctc_plan), as a dict of ints with "kernel" as a
+    name ("wave", "shift", "pair", "edge").  Read-only: nothing is launched.  A shape the call refuses raises here too."""
+    info = _l.CtcPlanInfo()
+    _l.check(_l.load().amdspeech_ctc_plan(int(T), int(B), int(C_), int(U), C.byref(info)), "ctc_plan")
+    out = {name: int(getattr(info, name)) for name, _ in _l.CtcPlanInfo._fields_}
+    out["kernel"] = _l.CTC_KERNELS[out["kernel"]]
+    return out
+
+
 def ctc_loss_fwd_bwd(logits, dense_labels, lengths, ws=None, loss=None, dlogits=None, stage=0):
     """logits [T,B,C]; dense_labels int32 [B,U] (0-padded, reference labels_ph);
     returns (loss [B], dlogits [T,B,C]).  stage 1 / 2: the two halves of the call (amdspeech.h), same arguments."""

@@ -38,6 +38,15 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     assert handle.amdspeech_frontend_num_frames(0, 220500, 22050) == 1003
     assert handle.amdspeech_frontend_num_frames(1, 220500, 22050) == 1000
     assert handle.amdspeech_ctc_workspace_bytes(1001, 32, 80, 161) > 0
+    assert "amdspeech_ctc_plan" in declared
+    # the CTC plan query: a struct of four ints as the header declares it, the headline shape on the DPP-shift kernel, U = 2560 refused
+    decl = header.split("typedef struct amdspeech_ctc_plan_info {")[1].split("}")[0]
+    assert [n.strip() for n in decl.replace("int", "").replace(";", "").split(",")] == [n for n, _ in lib.CtcPlanInfo._fields_]
+    info = lib.CtcPlanInfo()
+    assert handle.amdspeech_ctc_plan(1001, 32, 80, 161, ctypes.byref(info)) == 0
+    assert (lib.CTC_KERNELS[info.kernel], info.threads, info.rmax, info.smax) == ("shift", 256, 2, 323)
+    assert handle.amdspeech_ctc_plan(1001, 32, 80, 2560, ctypes.byref(info)) != 0 and b"2559" in handle.amdspeech_last_error()
+    assert handle.amdspeech_ctc_plan(1001, 32, 80, 161, None) != 0
 
 
 def test_product_path_fails_loudly_without_the_library(tmp_path, monkeypatch):

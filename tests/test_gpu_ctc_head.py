@@ -4,9 +4,15 @@ against the staged CTC call on the fused path's own logits (the loss must be BIT
 Reference semantics: /root/reference/models/AcousticModel.py:241-247 (output layer), :356-357 (tf.nn.ctc_loss,
 ignore_longer_outputs_than_inputs) -- the oracle parity of the whole step is test_gpu_model.py / test_gpu_fullsize.py, which run the
 fused path wherever the shape takes it."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ctc_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -28,12 +34,12 @@ def make_batch(T, B, D, C, U, seed, full=False):
     return x, lengths, dense
 
 
-def run(fused, L, H, D, C, B, T, U, seed, keep=(1.0, 1.0), full=False, max_len=None):
+def run(fused, L, H, D, C, B, T, U, seed, keep=(1.0, 1.0), full=False, max_len=None, batch=None):
     from rnn_speech_amd import engine as E
     old, E._FUSED_CTC = E._FUSED_CTC, fused
     try:
         eng = E.Engine(L, H, D, C, B, T, U, seed=21)
-        x, lengths, dense = make_batch(T, B, D, C, U, seed, full=full)
+        x, lengths, dense = make_batch(T, B, D, C, U, seed, full=full) if batch is None else batch
         if max_len is not None:
             lengths = np.minimum(lengths, max_len).astype(np.int32)
         dx, dl, dd = torch.as_tensor(x).cuda(), torch.as_tensor(lengths).cuda(), torch.as_tensor(dense).cuda()
@@ -73,7 +79,8 @@ SHAPES = [
 
 def same_recursion(U):
     """The staged call picks ctc_alpha_beta3_kernel (float64 state, DPP shift) for 129 .. 384 extended states; the fused head always runs
-    that recursion.  Only there are the two losses the same bits; with shorter targets the staged call keeps a float32 state."""
+    that recursion.  Only there are the two losses the same bits; with shorter targets the staged call runs the one-wave kernel (float64
+    state too, another layout and order of the final log-sum-exp)."""
     return 128 < 2 * U + 1 <= 384
 
 
@@ -101,7 +108,7 @@ def test_fused_head_matches_the_separate_launches(L, H, D, C, B, T, U):
     np.testing.assert_allclose(a["loss"], b["loss"], rtol=3e-6, atol=1e-5)
     # dlogits: the staged call's, up to the order LDS atomics meet in
     Tr = a["Tr"]
-    # (short targets: the staged call's float32 recursion state is the less accurate side -- DESIGN.md 4.3, round 4)
+    # (short targets: the staged call runs the one-wave kernel -- DESIGN.md 4.3)
     assert np.abs(a["dlogits"][:Tr] - a["staged_dlogits"]).max() < (2e-6 if same_recursion(U) else 2e-4)
     assert np.abs(a["dlogits"] - b["dlogits"]).max() < 2e-4      # (the other path's logits differ in the last bits; T frames of recursion later ...)
     # ... and everything behind it: dZ_0 and every parameter gradient
@@ -116,6 +123,58 @@ def test_fused_head_matches_the_separate_launches(L, H, D, C, B, T, U):
             assert a["loss"][3] == 0.0 and not a["dlogits"][:, 3].any()
     for bb in range(B):
         assert not a["dlogits"][a["lengths"][bb]:, bb].any()
+
+
+def full_width_batch(T, B, D, C, U, seed):
+    """Every row uses all U label slots (S = 2 U + 1 = smax, no EOS) but two: one row ends in an EOS (S = smax - 2), one is short.
+    Adjacent labels differ except at one repeat per row, placed on a wave boundary of the recursion (state 97, 193 or 289)."""
+    rng = np.random.RandomState(seed)
+    x = rng.randn(T, B, D).astype(np.float32)
+    lengths = np.full(B, T, np.int32)
+    lengths[1::3] = T - 1 - np.arange(len(lengths[1::3])) % 7
+    dense = np.zeros((B, U), np.int32)
+    for b in range(B):
+        n = U if b != 2 else U - 1
+        if b == 4:
+            n = U // 3
+        rep = (97, 193, 289)[b % 3]
+        dense[b, :n] = R._labels(rng, n, C, (rep,) if rep < 2 * n else ())
+        if n < U:
+            dense[b, n] = C - 1
+    return x, lengths, dense
+
+
+# L, H, D, C, B, T, U: two utterances per follower team (B = 32), 383 extended states -- what the head is built for -- and 323
+FULL_WIDTH = [(3, 512, 40, 80, 32, 203, 191), (3, 512, 40, 80, 32, 1003, 161)]
+
+
+@pytest.mark.parametrize("L,H,D,C,B,T,U", FULL_WIDTH)
+def test_fused_head_at_full_width_against_the_float64_oracle_on_its_own_logits(L, H, D, C, B, T, U):
+    """The head's recursion (ctc_flow.h restates ctc_alpha_beta3_kernel) with every one of its 4 x 96 states live, judged on its own:
+    loss and dlogits of the fused path against oracle.model.ctc_loss_and_grad in float64 on the FUSED path's logits, slice by slice,
+    within 8 x the error of the emulated float64-state arithmetic (tests/ctc_ref.py) -- beside the bit-identical loss of the staged
+    call, which shares the head's arithmetic and so cannot see a mistake they have in common."""
+    from rnn_speech_amd import ops
+    batch = full_width_batch(T, B, D, C, U, seed=T + U)
+    a = run(True, L, H, D, C, B, T, U, seed=0, batch=batch)
+    assert a["took"] and a["Tr"] == T
+    x, lengths, dense = batch
+    assert ops.ctc_plan(T, B, C, U)["kernel"] == "shift"
+    assert np.array_equal(a["loss"], a["staged_loss"])
+    assert np.abs(a["dlogits"][:T] - a["staged_dlogits"]).max() < 2e-6
+    logits = a["logits"][:T]
+    ref_loss, ref_d = R.reference(logits, dense, lengths)
+    assert np.isfinite(ref_loss).all() and (ref_loss > 0).all()
+    assert (2 * (dense != 0).sum(1) + 1 >= 2 * U - 1).sum() >= B - 1      # (full width: all rows but the short one)
+    with np.errstate(all="ignore"):
+        emu_loss, emu_d = R.emulate(logits, dense, lengths, ("shift", 2, 256), fam="head")
+    valid, inf = [True] * B, [False] * B
+    ev = dict(ref_loss=ref_loss, ref_d=ref_d, lengths=lengths, valid=valid, inf=inf, case=dict(C=C),
+              emu_err=R.slice_errors(emu_loss, emu_d, ref_loss, ref_d, lengths), emu_rowsum=R.invariants(emu_loss, emu_d, lengths, valid, inf)[0])
+    ev["bounds"] = R.bounds(ev["emu_err"], "head", ref_d)
+    fails, worst = R.judge(ev, a["loss"], a["dlogits"][:T])
+    print("CTCPATH fused-head T%d-U%d head worst error/bound %.3f" % (T, U, worst))
+    assert not fails, "\n  ".join(fails[:12])
 
 
 def test_fused_head_with_dropout_and_a_shorter_run_length():

@@ -203,7 +203,14 @@ def make_ctc_case(T, B, C, U, seed, lengths=None):
 @pytest.mark.parametrize("T,B,C,U", [(30, 4, 80, 12), (101, 7, 80, 40), (257, 3, 80, 161), (64, 2, 29, 70),
                                       (300, 2, 80, 600), (600, 2, 80, 1100)])
 def test_ctc_loss_and_grad(ops, T, B, C, U):
+    import os
     logits, dense, lengths = make_ctc_case(T, B, C, U, seed=T + B)
+    # the recursion kernel each shape is here for, under the switches of this process (the fallback test below runs this in a child)
+    shift, pair = os.environ.get("AMDSPEECH_CTC_SHIFT", "1") != "0", os.environ.get("AMDSPEECH_CTC_PAIR", "1") != "0"
+    mid = ("shift", 2) if shift else ("pair", 2) if pair else ("edge", 2)
+    expect = {12: ("wave", 2), 40: ("wave", 2), 161: mid, 70: mid, 600: ("edge", 8), 1100: ("edge", 20)}[U]
+    plan = ops.ctc_plan(T, B, C, U)
+    assert (plan["kernel"], plan["rmax"]) == expect, plan
     loss, dl = ops.ctc_loss_fwd_bwd(dev(logits), dev(dense, torch.int32), dev(lengths, torch.int32))
     rows = om.sparsify_labels(dense, C)
     ref_loss, ref_dl = om.ctc_loss_and_grad(logits.astype(np.float64), rows, lengths)
@@ -225,6 +232,7 @@ def test_ctc_fallback_recursion_kernels_keep_parity(env):
     out = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-k", "test_ctc_loss_and_grad"],
                          env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
+    assert "6 passed" in out.stdout, out.stdout[-1000:]      # (each asserts the kernel the switches select: ops.ctc_plan)
 
 
 def test_ctc_reference_label_conventions(ops):
