@@ -188,7 +188,8 @@ enum {
     AMDSPEECH_LSTM_WS_DZTOP = 2,   /* float [T][B][H]  in : dLoss/d(top output)    */
     AMDSPEECH_LSTM_WS_DZ0 = 3,     /* float [T][B][H]  out: dLoss/d(layer-0 input) */
     AMDSPEECH_LSTM_WS_HFINAL = 4,  /* float [L][B][H] slices of the h history at T */
-    AMDSPEECH_LSTM_WS_CFINAL = 5
+    AMDSPEECH_LSTM_WS_CFINAL = 5,
+    AMDSPEECH_LSTM_WS_GATES = 6    /* float [L][T][B][4][H] out: the activated gates i, j, f, o of every frame (the BPTT stash) */
 };
 size_t amdspeech_lstm_workspace_bytes(const amdspeech_lstm_desc* d);
 /* Pointer of a named region inside `ws` (NULL on bad arguments). For
@@ -330,6 +331,12 @@ typedef struct amdspeech_lstm_plan_info {
     int fwd_path, bwd_path, nmt, kb, mv, wpx, uw, fwd_mt, pair, bf16p, bf16p_reserved, xw_parts, nfw, w_pieces, dz0_inkernel, flow2_q;
 } amdspeech_lstm_plan_info;
 int amdspeech_lstm_plan(const amdspeech_lstm_desc* d, int C, int U, amdspeech_lstm_plan_info* out);
+/* The x-product workers' share of the FLOW forward launch in HALF K blocks per recurrence wave, which the 16 ints above cannot say
+ * (`mv` counts whole blocks): 0 none, 2 one block (full roles on the spare XCDs), 3 a block and a half (half roles on waves 4-7 of
+ * the worker workgroups too: gates f and o of a second K block -- exact f32, H = 512, one full role per SIMD fits); -1: bad
+ * descriptor.  Read-only like amdspeech_lstm_plan.  The environment switch AMDSPEECH_FLOW_FWD_WORKERS (read once per process)
+ * picks among the kernels a shape can take: 0 = no workers, 1 = full roles only, unset or 2 = half roles where they fit.     */
+int amdspeech_lstm_plan_xw_halves(const amdspeech_lstm_desc* d, int C, int U);
 
 /* ------------------------------------------------ layer-wise bidirectional stacks ----
  * tf.contrib.rnn.stack_bidirectional_dynamic_rnn (torch.nn.LSTM(bidirectional=True, num_layers=L)): L layers, each a forward and

@@ -69,6 +69,24 @@ static bool fwd_workers_fit(const amdspeech_lstm_desc* d) {
     const long groups = (long)d->L * ((d->B + 15) / 16);
     return d->precision == 0 && d->H == 512 && groups < 8 && (size_t)d->T * groups * (d->H / 16) * 4096 < (1ull << 32);
 }
+// FWD2_WORKER_RESERVE workgroups of every spare XCD exit at once: their CUs are what work ordered behind
+// amdspeech_lstm_beside_forward (the next mini-batch's front end, the side-stream fills) runs on.
+#ifndef FWD2_WORKER_RESERVE
+#define FWD2_WORKER_RESERVE 8
+#endif
+// worker workgroups per spare XCD when `waves` waves of each take a full role (callers: fwd_workers_fit holds)
+static int fwd_worker_wgs_per_xcd(const amdspeech_lstm_desc* d, int waves) {
+    const int groups = d->L * ((d->B + 15) / 16), spare = 8 - groups;
+    const int wgs = (groups * (d->H / 16) + waves - 1) / waves;
+    return (wgs + spare - 1) / spare;
+}
+// ... and the half roles (lstm_flow_fwd.h): where the full roles fit one per SIMD -- waves 0-3, so waves 4-7 are free -- and a
+// frame of a tile and a half per role keeps the history inside its 32-bit buffer resource
+static bool fwd_half_roles_fit(const amdspeech_lstm_desc* d) {
+    const long groups = (long)d->L * ((d->B + 15) / 16);
+    return fwd_workers_fit(d) && fwd_worker_wgs_per_xcd(d, 4) <= 32 - FWD2_WORKER_RESERVE &&
+           (size_t)d->T * groups * (d->H / 16) * 6144 < (1ull << 32);
+}
 // ---- the batched products of the H = 1024 path through bf16 copies (precision = 2; gemm_bf16p.hip) ----------------------------------
 // One region of the workspace: Z as bf16 [TB][H] (x . W_ih), W_ih^T [4H][H]; dG as bf16 [TB][4H] and W_ih [H][4H] (dX);
 // [Z ; Hprev]^T [2H][TB] and dG^T [4H][TB] (dK, both halves of a layer's kernel gradient as ONE product); the partial tiles of dK.
@@ -413,13 +431,13 @@ static bool use_flow(const amdspeech_lstm_desc* d) {
 // The instantiations of the two dataflow kernels, by K blocks per wave and half (H / 128) and precision; CF: with the fused CTC
 // head's role (flow_shape_ok: reduced precision only at H = 256, 512; x-product workers only in exact f32 at H = 512)
 template <bool CF>
-static void (*flow_fwd_kernel(int kb, int pr, int mv))(FlowArgs) {
+static void (*flow_fwd_kernel(int kb, int pr, int mv, int mh))(FlowArgs) {
     switch (kb) {
         case 1: return lstm_fwd_flow2<1, 0, 0, CF>;
         case 2: return pr == 2 ? lstm_fwd_flow2<2, 2, 0, CF> : (pr == 1 ? lstm_fwd_flow2<2, 1, 0, CF> : lstm_fwd_flow2<2, 0, 0, CF>);
         case 3: return lstm_fwd_flow2<3, 0, 0, CF>;
         default:
-            if (pr == 0 && mv == 1) return lstm_fwd_flow2<4, 0, 1, CF>;
+            if (pr == 0 && mv == 1) return mh == 1 ? lstm_fwd_flow2<4, 0, 1, CF, 1> : lstm_fwd_flow2<4, 0, 1, CF>;
             return pr == 2 ? lstm_fwd_flow2<4, 2, 0, CF> : (pr == 1 ? lstm_fwd_flow2<4, 1, 0, CF> : lstm_fwd_flow2<4, 0, 0, CF>);
     }
 }
@@ -429,12 +447,6 @@ static void (*flow_bwd_kernel(int kb, int pr))(FlowBwdArgs) {
     if (pr == 1) return kb == 2 ? lstm_bwd_flow2<2, 1, CF> : lstm_bwd_flow2<4, 1, CF>;
     return kb == 1 ? lstm_bwd_flow2<1, 0, CF> : (kb == 2 ? lstm_bwd_flow2<2, 0, CF> : (kb == 3 ? lstm_bwd_flow2<3, 0, CF> : lstm_bwd_flow2<4, 0, CF>));
 }
-// FWD2_WORKER_RESERVE workgroups of every spare XCD exit at once: their CUs are what work ordered behind
-// amdspeech_lstm_beside_forward (the next mini-batch's front end, the side-stream fills) runs on.
-#ifndef FWD2_WORKER_RESERVE
-#define FWD2_WORKER_RESERVE 8
-#endif
-
 // ---- the panels the dataflow kernels poll (amdspeech.h: AMDSPEECH_LSTM_ARMED / ARM_NEXT)
 // forward: sentinel in every slot the kernel will write (each exactly once; layer 0 reads xp0, not xph[0])
 static int flow_fill_fwd_panels(hipStream_t s, const amdspeech_lstm_desc* d, float* ws, const LstmLayout& lo, int set) {
@@ -607,6 +619,7 @@ struct LstmPlan {
     // what the workspace reserves
     bool flow_shape;                      // the panels and rings of the dataflow kernels
     int xw_parts;                         // ... and the x-product workers' tile history: K blocks per recurrence wave (0 or 1)
+    int xw_half;                          // ... and the half roles' tiles in every frame of it (0 or 1: fwd_half_roles_fit)
     bool big_ring;                        // the rings of lstm_bwd_big / lstm_bwd_big1
     bool bf16p_reserved;                  // the bf16 operand copies of the batched products (gemm_bf16p.hip) ...
     bool bf16p;                           // ... and whether this T uses them
@@ -621,6 +634,7 @@ struct LstmPlan {
     void (*fwd_flow)(FlowArgs); void (*bwd_flow)(FlowBwdArgs);
     size_t fwd_lds, bwd_lds;              // their dynamic LDS
     int mv, wpx, wpw;                     // x-product workers: K blocks per recurrence wave (0: none), workgroups per spare XCD, waves per role
+    int mh;                               // ... half roles on waves 4-7 of those workgroups (0 or 1; wpw = 4 then)
     int nfw;                              // the fused CTC head's followers per spare XCD (0: no head, or the shape does not take it)
     int dz0_inkernel;                     // lstm_bwd_flow2: dZ_0 formed by the layer-0 groups
     int w_pieces, w_t0, w_dz0;            // ... its in-kernel weight gradients: chunks (0: none), first frame, dZ_0 too
@@ -658,6 +672,7 @@ static LstmPlan lstm_plan(const amdspeech_lstm_desc* d, const amdspeech_ctc_head
     p.nmt = (d->B + 15) / 16;
     p.flow_shape = flow_shape_ok(d);
     p.xw_parts = p.flow_shape && fwd_workers_fit(d) ? 1 : 0;
+    p.xw_half = p.xw_parts > 0 && fwd_half_roles_fit(d) ? 1 : 0;
     p.big_ring = !p.flow_shape && pr >= 0 && pr <= 2 && H == 1024 && p.nmt <= 4;
     p.bf16p_reserved = bf16p_layout_reserved(d);
     p.bf16p = bf16p_layout_on(d);
@@ -695,19 +710,21 @@ static LstmPlan lstm_plan(const amdspeech_lstm_desc* d, const amdspeech_ctc_head
     p.bwd_big = pr == 2 ? lstm_bwd_big<2> : (pr == 1 ? lstm_bwd_big<1> : lstm_bwd_big<0>);
     if (!flow) return p;
 
-    // ---- the dataflow kernels.  x-product workers (lstm_fwd_flow2<., ., 1>): one role per SIMD where that fits, else two
-    // (AMDSPEECH_FLOW_FWD_WORKERS=0: the kernel of rounds 2 - 4, every recurrence wave multiplies its whole x half)
-    static const int workers_env = runtime_switch("AMDSPEECH_FLOW_FWD_WORKERS", 1);
+    // ---- the dataflow kernels.  x-product workers (lstm_fwd_flow2<., ., 1>): one role per SIMD where that fits, else two; where one
+    // fits, waves 4-7 of the worker workgroups take half roles (lstm_fwd_flow2<., ., 1, ., 1>: a block and a half per recurrence wave)
+    // (AMDSPEECH_FLOW_FWD_WORKERS=0: the kernel of rounds 2 - 4, every recurrence wave multiplies its whole x half; 1: full roles only)
+    static const int workers_env = runtime_switch("AMDSPEECH_FLOW_FWD_WORKERS", 2);
     const int groups = L * p.nmt, spare = 8 - groups;
     p.wpw = 8;
     if (workers_env != 0 && p.xw_parts > 0)
         for (int waves = 4; waves <= 8 && p.mv == 0; waves += 4) {
-            const int wgs = (groups * (H / 16) + waves - 1) / waves, per = (wgs + spare - 1) / spare;
+            const int per = fwd_worker_wgs_per_xcd(d, waves);
             if (per <= 32 - FWD2_WORKER_RESERVE) { p.mv = 1; p.wpx = per; p.wpw = waves; }
         }
+    p.mh = (workers_env != 1 && p.mv == 1 && p.wpw == 4 && p.xw_half > 0) ? 1 : 0;
     if (head != nullptr) p.nfw = ctc_head_nfw(d, head->C, head->U, p.wpx);
     const int kb = H / 128;
-    p.fwd_flow = head != nullptr ? flow_fwd_kernel<true>(kb, pr, p.mv) : flow_fwd_kernel<false>(kb, pr, p.mv);
+    p.fwd_flow = head != nullptr ? flow_fwd_kernel<true>(kb, pr, p.mv, p.mh) : flow_fwd_kernel<false>(kb, pr, p.mv, p.mh);
     p.bwd_flow = head != nullptr ? flow_bwd_kernel<true>(kb, pr) : flow_bwd_kernel<false>(kb, pr);
     p.fwd_lds = head != nullptr ? (size_t)2 * CF_FOLLOW_TEAM_FLOATS * sizeof(float) : 0;      // (ctc_follower's two teams)
     // two dG tiles, the dh reduction buffer, the stash, the down product's per-wave tiles (double-buffered), the partners' dG tiles
@@ -747,12 +764,13 @@ static LstmLayout lstm_layout(const LstmPlan& p) {
     LstmLayout o;
     size_t off = 0;
     auto take = [&](size_t n) { size_t r = off; off += (n + 63) / 64 * 64; return r; };
-    // lstm_fwd_flow2's x-product workers: pre-multiplied gate tiles, [T][L][batch tiles][H/16][parts][256][4], written once per
+    // lstm_fwd_flow2's x-product workers: pre-multiplied gate tiles, [T][L][batch tiles][H/16][parts][256][4] (xw_half: and, behind
+    // them in every frame, the half roles' [L][batch tiles][H/16][256][2] -- reserved by the shape, whatever the launch uses), written once per
     // launch and tagged with the launch's parity.  FIRST and time-major: frame t lives at the same address whatever T the
     // descriptor names (ops.LstmWorkspace.prefix lays ONE allocation out for every sequence length of a training run), so the
     // tags survive from one launch to the next with another T (AMDSPEECH_LSTM_SAME_WS)
     o.xwp = 0;
-    if (p.xw_parts > 0) o.xwp = take(T * L * ((B + 15) / 16) * (H / 16) * p.xw_parts * 1024);
+    if (p.xw_parts > 0) o.xwp = take(T * L * ((B + 15) / 16) * (H / 16) * (p.xw_parts * 1024 + p.xw_half * 512));
     o.wp = take(L * 2 * H * 4 * H);
     o.wq = take(L * 2 * H * 4 * H);
     o.z = take((L + 1) * tbh);
@@ -921,7 +939,8 @@ static int fwd_flow(hipStream_t s, const FwdCall& c) {
     fa.xwp = ws + lo.xwp; fa.xw_par = 0u; fa.w_wpx = p.wpx; fa.w_wpw = p.wpw;
     if (p.mv > 0)
         if (int rc = flow_xw_parity(s, ws, (d->flags & (AMDSPEECH_LSTM_ARMED | AMDSPEECH_LSTM_SAME_WS)) != 0,
-                                    (((long)B * 4096 + H) * 64 + L) * 8 + p.mv, fa.xwp, (size_t)L * (bp / 16) * (H / 16) * p.mv * 1024, T,
+                                    (((long)B * 4096 + H) * 64 + L) * 8 + p.mv * 2 + p.mh, fa.xwp,
+                                    (size_t)L * (bp / 16) * (H / 16) * (p.mv * 1024 + p.mh * 512), T,
                                     &fa.xw_par)) return rc;
     fa.cf = CtcFlow{}; fa.cf_on = 0; fa.cf_nfw = 0;
     if (c.head != nullptr) {
@@ -1403,9 +1422,10 @@ extern "C" int amdspeech_profile_get_flops(int which, double* recurrence_flops, 
 
 // The bytes a workspace for sequences of UP TO d->T frames needs.  ops.LstmWorkspace.prefix lays one allocation out again for every
 // shorter run length.  Of the regions lstm_plan reserves, two exist only below a sequence length (the 32-bit buffer resources of the
-// whole-sequence kernels): the dataflow panels (flow_shape) and the x-product workers' tile history (xw_parts, 0 or 1 -- one size);
-// big_ring and bf16p_reserved do not depend on T.  A prefix just below either threshold can need MORE than the full length above it;
-// with the set of regions fixed the size is monotone in T, so the maximum over T' <= T is taken at T or at the last T' of either set.
+// whole-sequence kernels): the dataflow panels (flow_shape) and the x-product workers' tile history (xw_parts, 0 or 1 -- one size --
+// and the half tiles in its frames, xw_half, which end at a shorter length); big_ring and bf16p_reserved do not depend on T.  A prefix
+// just below a threshold can need MORE than the full length above it; with the set of regions fixed the size is monotone in T, so
+// the maximum over T' <= T is taken at T or at the last T' of one of the sets.
 extern "C" size_t amdspeech_lstm_workspace_bytes(const amdspeech_lstm_desc* d) {
     if (check_desc(d)) return 0;
     size_t need = lstm_layout(lstm_plan(d, nullptr)).total;
@@ -1417,8 +1437,9 @@ extern "C" size_t amdspeech_lstm_workspace_bytes(const amdspeech_lstm_desc* d) {
         while (hi - lo > 1) { q.T = lo + (hi - lo) / 2; if (pred(lstm_plan(&q, nullptr))) lo = q.T; else hi = q.T; }
         return lo;
     };
-    const int cand[2] = {last_with([](const LstmPlan& p) { return p.flow_shape; }),
-                         last_with([](const LstmPlan& p) { return p.xw_parts > 0; })};
+    const int cand[3] = {last_with([](const LstmPlan& p) { return p.flow_shape; }),
+                         last_with([](const LstmPlan& p) { return p.xw_parts > 0; }),
+                         last_with([](const LstmPlan& p) { return p.xw_half > 0; })};
     for (int c : cand)
         if (c > 0 && c < d->T) { q.T = c; const size_t n = lstm_layout(lstm_plan(&q, nullptr)).total; if (n > need) need = n; }
     return need * sizeof(float);
@@ -1436,6 +1457,7 @@ extern "C" void* amdspeech_lstm_ws_ptr(const amdspeech_lstm_desc* d, void* ws, i
         case AMDSPEECH_LSTM_WS_DZ0: return w + lo.dz0;
         case AMDSPEECH_LSTM_WS_HFINAL: return w + lo.hs + (size_t)d->T * d->B * d->H;
         case AMDSPEECH_LSTM_WS_CFINAL: return w + lo.cs + (size_t)d->T * d->B * d->H;
+        case AMDSPEECH_LSTM_WS_GATES: return w + lo.gates;
         default: set_error("lstm_ws_ptr: unknown region %d", which); return nullptr;
     }
 }
@@ -1573,6 +1595,14 @@ extern "C" int amdspeech_lstm_plan(const amdspeech_lstm_desc* d, int C, int U, a
                                     p.pair ? 1 : 0, p.bf16p ? 1 : 0, p.bf16p_reserved ? 1 : 0, p.xw_parts, p.nfw, p.w_pieces,
                                     p.dz0_inkernel, flow_bwd ? flow2_q(d->H / 128, d->precision) : 0};
     return AMDSPEECH_OK;
+}
+// ... and what the 16 ints do not say of the forward dataflow launch: the x-product workers' share in HALF K blocks per recurrence wave
+extern "C" int amdspeech_lstm_plan_xw_halves(const amdspeech_lstm_desc* d, int C, int U) {
+    if (check_desc(d) != AMDSPEECH_OK) return -1;
+    amdspeech_ctc_head h{};
+    h.C = C; h.U = U;
+    const LstmPlan p = lstm_plan(d, C > 0 ? &h : nullptr);
+    return 2 * p.mv + p.mh;
 }
 extern "C" int amdspeech_lstm_ctc_fusable(const amdspeech_lstm_desc* d, int C, int U) {
     if (check_desc(d) != AMDSPEECH_OK) return 0;

@@ -71,10 +71,12 @@ struct FlowArgs {
     unsigned long long* trace;     // dev builds (-DAMDSPEECH_DEVTRACE): wall-clock stamps of layer 1, unit block 3
     // x-product workers (lstm_fwd_flow2<., ., MV > 0>): the workgroups of the XCDs without a recurrence group form MV of every
     // recurrence wave's KB K blocks of x_t . W_ih and hand the groups pre-multiplied gate tiles through `xwp`
-    float* xwp;                    // [T][L][nmt][H/16][MV][256][4 gates], every word tagged with xw_par (write-once per launch)
+    float* xwp;                    // [T] frames of [L][nmt][H/16][MV][256][4 gates] (+ half roles: [L][nmt][H/16][256][2 gates f, o] behind
+                                   // them), every word tagged with xw_par (write-once per launch)
     unsigned xw_par;               // this launch's tag: the least significant mantissa bit of every word of xwp written by it
     int w_wpx;                     // worker workgroups per spare XCD (the others exit at once: room for amdspeech_lstm_beside_forward work)
-    int w_wpw;                     // waves of a worker workgroup that take a role: 4 (waves 0-3, one per SIMD) or 8
+    int w_wpw;                     // waves of a worker workgroup that take a full role: 4 (waves 0-3, one per SIMD; with half roles
+                                   // waves 4-7 take those) or 8
     int trace_layer;               // dev builds only
     int cf_on, cf_nfw;             // the fused CTC head (ctc_flow.h): 0 = none; follower workgroups per spare XCD
     CtcFlow cf;                    // LAST, 64-byte aligned, and everything its role reads is INSIDE it (see CtcFlow)

@@ -30,39 +30,50 @@
 // mantissa bit (the panel is written exactly once per launch: the previous launch left the other parity, nothing is re-filled);
 // the epilogue threads of the recurrence group fetch their 16 bytes two steps ahead and add them to the bias in front of B1.
 // Nothing throttles a worker but its operand: the layer above then trails the layer below by the few frames the hand-off takes.
-template <int KB, int MV>
+// HALF ROLES (MH = 1, NTW = 2; the planner's split "a block and a half"): where the full roles take one wave per SIMD (waves 0-3 of
+// a worker workgroup), waves 4-7 take one more K block of the x half, {w*KB + KB-1-MV}, but only its N tiles 2 and 3 (gates f, o):
+// 64 VGPRs of weights, 64 MFMAs per frame, a [16 rows x 32 gate columns] tile as two 1 KiB stores (element lane*4 + i: its two
+// gates as 8 bytes) behind the full tiles of the frame.  Two full roles on one SIMD cost more than a recurrence step (round 5,
+// MV = 2); a role and a half, 192 MFMAs per frame, stays under it.
+// NTW: the N tiles of this role (4: a full role, 2: a half role); MH: whether the launch has half roles (the frame of xwp holds them)
+template <int KB, int MV, int MH, int NTW>
 __device__ __forceinline__ void fwd_x_worker(const FlowArgs& a, const int role, const int lane, const unsigned long long t_begin) {
     constexpr int H = 128 * KB, NKBX = H / 16, NU = H / 16, NT = 4;
+    constexpr bool HALF = NTW != NT;
+    constexpr int J0 = NT - NTW;             // the first N tile of the role
+    static_assert(NTW == 4 || (NTW == 2 && MH == 1), "x-product workers: full roles, or half roles of a launch that carries them");
     const int T = a.T, nmt = (a.B + 15) / 16;
     int r = __builtin_amdgcn_readfirstlane(role);
-    const int part = r % MV; r /= MV;
+    const int part = HALF ? MV : r % MV;     // (the K block KB-1-part: a half role takes the one below the full roles')
+    if (!HALF) r /= MV;
     const int ub = r % NU; r /= NU;
     const int mb = r % nmt;
     const int l = r / nmt;
     if (l >= a.L) return;
     const size_t bph = (size_t)nmt * 16 * H;
-    float4 w[8][NT];
+    float4 w[8][NTW];
     {
         const float* wp = a.wp + ((size_t)(l * NU + ub) * (2 * NKBX)) * (NT * 256) + lane * 4;
 #pragma unroll
         for (int wv = 0; wv < 8; ++wv)
 #pragma unroll
-            for (int j = 0; j < NT; ++j) w[wv][j] = *reinterpret_cast<const float4*>(wp + (size_t)((wv * KB + KB - 1 - part) * NT + j) * 256);
+            for (int j = 0; j < NTW; ++j) w[wv][j] = *reinterpret_cast<const float4*>(wp + (size_t)((wv * KB + KB - 1 - part) * NT + J0 + j) * 256);
     }
     const float* xsrc = l == 0 ? a.xp0 : a.xph + (size_t)l * T * bph;
     const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xsrc), 0, (unsigned)((size_t)T * bph * 4), 0x00020000);
-    const size_t fs = (size_t)a.L * nmt * NU * MV * 1024;                              // floats per frame of xwp
+    const size_t fs = (size_t)a.L * nmt * NU * (MV * 1024 + MH * 512);                 // floats per frame of xwp: the full tiles, then the half tiles
     const auto ro = __builtin_amdgcn_make_buffer_rsrc(a.xwp, 0, (unsigned)((size_t)T * fs * 4), 0x00020000);
     const unsigned lane_off = (unsigned)((((size_t)mb * NKBX + (KB - 1 - part)) * 256 + lane * 4) * 4);      // + wv*KB KiB: K block of recurrence wave wv
-    const unsigned out_off = (unsigned)((((((size_t)l * nmt + mb) * NU + ub) * MV + part) * 1024 + lane * 4) * 4);
+    const unsigned out_off = HALF ? (unsigned)(((size_t)a.L * nmt * NU * MV * 1024 + (((size_t)l * nmt + mb) * NU + ub) * 512 + lane * 4) * 4)
+                                  : (unsigned)((((((size_t)l * nmt + mb) * NU + ub) * MV + part) * 1024 + lane * 4) * 4);
     const unsigned par = a.xw_par & 1u;
     bool dead = false;
     u32x4_f xa[8] = {}, xb[8] = {};
     // EVERY load of the frame loop is inline assembly and every wait an explicit s_waitcnt (the pattern of gemm_tile_tn_direct):
     // left to hipcc, the retry paths below turn the waits in front of the MFMAs into vmcnt(0) -- a wait for
     // the probe issued a moment earlier, i.e. a round trip to memory in series with every frame's MFMAs (first version: 5.6 us per
-    // step).  The frame loop issues, per frame and in this order: 1 probe, 4 tile stores, 8 panel loads -- always, with clamped frame
-    // indices at the end of the sequence -- so "this frame's panel and probe have landed" is vmcnt(12) everywhere.
+    // step).  The frame loop issues, per frame and in this order: 1 probe, NTW tile stores (a half role: 2), 8 panel loads -- always,
+    // with clamped frame indices at the end of the sequence -- so "this frame's panel and probe have landed" is vmcnt(8 + NTW) everywhere.
     // (plain lambdas: clang does not capture a variable that a GENERIC lambda names only in an asm operand)
     auto load_l2 = [&](u32x4_f& dst, unsigned vo, unsigned so) { asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "+v"(dst) : "v"(vo), "s"(rx), "s"(so)); };
     auto load_mem = [&](u32x4_f& dst, unsigned vo, unsigned so) { asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen sc1" : "+v"(dst) : "v"(vo), "s"(rx), "s"(so)); };
@@ -86,9 +97,9 @@ __device__ __forceinline__ void fwd_x_worker(const FlowArgs& a, const int role, 
         const int tp = t + FWD2_WORKER_LAG < T ? t + FWD2_WORKER_LAG : T - 1;
         load_mem(pr, lane_off, (unsigned)((size_t)tp * bph * 4));
     };
-    // at most 12 / 0 younger operations may still be in flight: the probe and the panel have landed
+    // at most 8 + NTW / 0 younger operations may still be in flight: the probe and the panel have landed
     auto landed12 = [&](u32x4_f (&buf)[8]) {
-        asm volatile("s_waitcnt vmcnt(12)" : "+v"(pr), "+v"(buf[0]), "+v"(buf[1]), "+v"(buf[2]), "+v"(buf[3]), "+v"(buf[4]), "+v"(buf[5]), "+v"(buf[6]), "+v"(buf[7]));
+        asm volatile("s_waitcnt vmcnt(%9)" : "+v"(pr), "+v"(buf[0]), "+v"(buf[1]), "+v"(buf[2]), "+v"(buf[3]), "+v"(buf[4]), "+v"(buf[5]), "+v"(buf[6]), "+v"(buf[7]) : "n"(8 + NTW));
     };
     auto landed0 = [&](u32x4_f (&buf)[8]) {
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(pr), "+v"(buf[0]), "+v"(buf[1]), "+v"(buf[2]), "+v"(buf[3]), "+v"(buf[4]), "+v"(buf[5]), "+v"(buf[6]), "+v"(buf[7]));
@@ -123,13 +134,13 @@ __device__ __forceinline__ void fwd_x_worker(const FlowArgs& a, const int role, 
         }
         FXWSTAMP(2);
         probe(t + 1);            // (the bottom layer's workers too: one order of operations, one wait count)
-        f32x4 acc[NT];
+        f32x4 acc[NTW];
 #pragma unroll
-        for (int j = 0; j < NT; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < NTW; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int wv = 0; wv < 8; ++wv)
 #pragma unroll
-            for (int j = 0; j < NT; ++j) {
+            for (int j = 0; j < NTW; ++j) {
                 acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(buf[wv][0]), w[wv][j].x, acc[j], 0, 0, 0);
                 acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(buf[wv][1]), w[wv][j].y, acc[j], 0, 0, 0);
                 acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(buf[wv][2]), w[wv][j].z, acc[j], 0, 0, 0);
@@ -138,10 +149,14 @@ __device__ __forceinline__ void fwd_x_worker(const FlowArgs& a, const int role, 
         // element lane*4 + i of the 16x16 tile: its four gates as one 16-byte word at slot i*64 + lane (a 1 KiB run per store)
         // (the frame offset in voffset, not in an SGPR soffset: the gfx950 store hazard noted at lstm_bwd_flow2's store_tiles)
         const unsigned fo = out_off + (unsigned)((size_t)t * fs * 4);
+        // (a half role: elements lane*4 + 2i and + 2i+1, two gates each, as one 16-byte word at slot i*64 + lane)
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_raw_buffer_store_b128(flow_tag((f32x4){acc[0][i], acc[1][i], acc[2][i], acc[3][i]}, par), ro,
-                                                   fo + (unsigned)(i * 1024), 0, 16);      // sc1: through to memory
+        for (int i = 0; i < NTW; ++i) {
+            f32x4 v;
+            if constexpr (HALF) v = (f32x4){acc[0][2 * i], acc[1][2 * i], acc[0][2 * i + 1], acc[1][2 * i + 1]};
+            else v = (f32x4){acc[0][i], acc[1][i], acc[2][i], acc[3][i]};
+            __builtin_amdgcn_raw_buffer_store_b128(flow_tag(v, par), ro, fo + (unsigned)(i * 1024), 0, 16);      // sc1: through to memory
+        }
         __builtin_amdgcn_sched_barrier(0);
         FXWSTAMP(3);
         issue(bottom, buf, t + 2);      // (two register sets: the operand panels are requested two frames ahead; past the end: the last frame again)
@@ -199,15 +214,19 @@ __device__ __forceinline__ void ctc_follower_call(const CtcFlow& c, int wg, int 
     else ctc_follower<H, 2>(c, cf_lds, wg, nwg);
 }
 
-template <int KB, int PR, int MV, bool CF = false>   // KB: 16-row K blocks per wave and half (H / 128); PR: 0 exact f32, 1 bf16x3, 2 bf16 products (KB even);
+template <int KB, int PR, int MV, bool CF = false, int MH = 0>   // KB: 16-row K blocks per wave and half (H / 128); PR: 0 exact f32, 1 bf16x3, 2 bf16 products (KB even);
                                     // MV: K blocks per wave of the x half that the x-product workers of the spare XCDs form (0: none)
+                                    // MH: 1 = half roles too (fwd_x_worker): of the wave's K block KB-1-MV the workers form N tiles 2 and 3
+                                    // (gates f, o) and the wave multiplies N tiles 0 and 1 only -- "a block and a half" with MV = 1
                                     // CF: the instantiation that carries the fused CTC head's follower (ctc_flow.h).  A separate one: the
                                     // role's scalar-register pressure costs the recurrence loops of the SAME function lane moves per
                                     // step (register allocation is per function), which launches without a head must not pay
 __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
     constexpr bool BF3 = PR != 0;
     static_assert(MV >= 0 && MV < KB && (MV == 0 || PR == 0), "x-product workers: exact f32 only, and one K block of the x half stays");
-    constexpr int KX = KB - MV;       // K blocks of the x half this wave multiplies itself
+    static_assert(MH == 0 || (MH == 1 && MV > 0 && KB - MV >= 2), "half roles: beside full roles, and one whole K block of the x half stays");
+    constexpr int KX = KB - MV;       // K blocks of the x half this wave multiplies itself (MH: the last of them for N tiles 0 and 1 only)
+    constexpr int NTL = MH ? 2 : 4;   // ... the N tiles of that last block
     constexpr int MVA = MV > 0 ? MV : 1;
     constexpr int UW = 16, NT = 4, H = 128 * KB, NKBX = H / 16, NW = 8;
     __shared__ __attribute__((aligned(16))) float red_[1][NW][256][NT];   // K-split partial sums (x + h halves together), the four gates of an element adjacent
@@ -223,7 +242,10 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
     if (grp >= a_in.L * ((a_in.B + 15) / 16)) {             // an XCD without a recurrence group
         const int first = a_in.L * ((a_in.B + 15) / 16);
         if (MV > 0 && ub < a_in.w_wpx && wave < a_in.w_wpw)
-            fwd_x_worker<KB, MVA>(a_in, (((grp - first) * a_in.w_wpx + ub) * a_in.w_wpw + wave), lane, wall_clock64());
+            fwd_x_worker<KB, MVA, MH, 4>(a_in, (((grp - first) * a_in.w_wpx + ub) * a_in.w_wpw + wave), lane, wall_clock64());
+        else if (MH > 0 && ub < a_in.w_wpx) {      // (w_wpw = 4: wave 4 + w takes the half role of the units of wave w's full role)
+            if constexpr (MH > 0) fwd_x_worker<KB, MVA, MH, 2>(a_in, (((grp - first) * a_in.w_wpx + ub) * 4 + wave - 4), lane, wall_clock64());
+        }
         else if (CF && a_in.cf_on && ub >= a_in.w_wpx && ub < a_in.w_wpx + a_in.cf_nfw) {
             // the CTC head's forward half (ctc_flow.h): output Linear + log-softmax + alpha, 16 frames behind the top layer
             if constexpr (CF) ctc_follower_call<H>(a_in.cf, (grp - first) * a_in.cf_nfw + (ub - a_in.w_wpx), (8 - first) * a_in.cf_nfw);
@@ -249,7 +271,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
         for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                if (kb < KX) { const f32x4 v = *(const f32x4 __attribute__((address_space(1)))*)(wp + (size_t)((wave * KB + kb) * NT + j) * 256); wx[kb][j] = make_float4(v[0], v[1], v[2], v[3]); }
+                if (kb < KX && (kb < KX - 1 || j < NTL)) { const f32x4 v = *(const f32x4 __attribute__((address_space(1)))*)(wp + (size_t)((wave * KB + kb) * NT + j) * 256); wx[kb][j] = make_float4(v[0], v[1], v[2], v[3]); }
                 { const f32x4 v = *(const f32x4 __attribute__((address_space(1)))*)(wp + (size_t)((NKBX + wave * KB + kb) * NT + j) * 256); wh[kb][j] = make_float4(v[0], v[1], v[2], v[3]); }
             }
     }
@@ -300,8 +322,8 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
     // for the x panel (and now the workers' tiles) requested from MEMORY right behind the gather -- and kept a second ladder inside
     // the h MFMA stream (the h phase ran 2.16 us where the x phase ran 1.76).  A step now issues, in this order and unconditionally
     // (clamped frame indices at the end of the sequence): the KB loads of h_t part-way through the x half, the KX loads of the x
-    // panel three steps ahead, the MV loads of the workers' tiles two steps ahead; the ONE wait of the step is vmcnt(KX + MV) at its
-    // top -- h_t has landed, whatever was requested behind it is still in flight.  Everything else the step reads was requested
+    // panel three steps ahead, the MV (+ MH: the half roles' 8 bytes) loads of the workers' tiles two steps ahead; the ONE wait of the step is
+    // vmcnt(KX + MV + MH) at its top -- h_t has landed, whatever was requested behind it is still in flight.  Everything else the step reads was requested
     // before h_t.  A retry (sentinel / old tag seen) re-requests and waits for vmcnt(0): fewer operations in flight than the count
     // assumes is always safe.  (Plain lambdas: clang does not capture a variable a generic lambda names only in an asm operand.)
     // (H = 512 WITHOUT workers -- AMDSPEECH_FLOW_FWD_WORKERS=0, the split precisions, no spare XCD -- keeps the loop of rounds 2 - 4:
@@ -317,6 +339,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
         asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen sc1" : "+v"(dst) : "v"(vo), "s"(rsrc), "s"(so));
     };
     auto pin = [&](u32x4_f& r) __attribute__((always_inline)) { asm volatile("" : "+v"(r)); };      // orders the uses of r behind the asm statements in front of it
+    auto pin2 = [&](u32x2_f& r) __attribute__((always_inline)) { asm volatile("" : "+v"(r)); };
     auto issue = [&](auto pol, auto& buf, decltype(rx) rsrc, unsigned base) __attribute__((always_inline)) {
         constexpr int NB = (int)(sizeof(buf) / sizeof(buf[0]));
 #pragma unroll
@@ -358,13 +381,17 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
     // ---- the x-product workers' tiles: this thread's element (its four gates) of frame t, MV parts, fetched two steps ahead
     // by EVERY wave (waves 4-7 never use theirs: a load in one role only would make hipcc's wait counts inexact at the merge,
     // and the wait for h_t would then cover it -- DESIGN.md 4.2 item 3); tagged with the launch's parity
-    const size_t wfs = (size_t)a.L * nmt * (H / UW) * MVA * 1024;                       // floats per frame of xwp
+    const size_t wfs = (size_t)a.L * nmt * (H / UW) * (MVA * 1024 + MH * 512);          // floats per frame of xwp
     const auto rw = __builtin_amdgcn_make_buffer_rsrc(a.xwp, 0, MV > 0 ? (unsigned)((size_t)T * wfs * 4) : 0u, 0x00020000);
     const unsigned w_off = (unsigned)((((((size_t)l * nmt + mb) * (H / UW) + ub) * MVA) * 1024 +
                                        ((pbl & 3) * 64 + (pbl >> 2) * 16 + pu) * 4) * 4);      // + part KiB*4
     const unsigned w_par = a.xw_par & 1u;
     u32x4_f wa[MVA] = {}, wb[MVA] = {};            // frames of even (wa) and odd (wb) index
-    auto wissue = [&](u32x4_f (&buf)[MVA], int sidx) __attribute__((always_inline)) {
+    // the half roles' tile: gates f and o of this thread's element, 8 bytes behind the frame's full tiles; the last word(s) of the set
+    u32x2_f wha = {}, whb = {};
+    const unsigned wh_off = (unsigned)(((size_t)a.L * nmt * (H / UW) * MVA * 1024 + (((size_t)l * nmt + mb) * (H / UW) + ub) * 512) * 4 +
+                                       (((pbl & 3) >> 1) * 64 + (pbl >> 2) * 16 + pu) * 16 + (pbl & 1) * 8);
+    auto wissue = [&](u32x4_f (&buf)[MVA], u32x2_f& hbuf, int sidx) __attribute__((always_inline)) {
         if (MV > 0) {
 #pragma unroll
             for (int p = 0; p < MVA; ++p) {
@@ -372,28 +399,40 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
                 else buf[p] = __builtin_amdgcn_raw_buffer_load_b128(rw, w_off + (unsigned)(p * 4096), (unsigned)((size_t)sidx * wfs * 4), 16);
             }
         }
+        if constexpr (MH > 0) {
+            static_assert(MH == 0 || ASM, "half roles: the assembly-pinned time loop only");
+            asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen sc1" : "+v"(hbuf) : "v"(wh_off), "s"(rw), "s"((unsigned)((size_t)sidx * wfs * 4)));
+        }
+    };
+    auto wuntagged = [&](const u32x4_f (&buf)[MVA], const u32x2_f& hbuf) __attribute__((always_inline)) -> unsigned {
+        unsigned again = 0u;
+#pragma unroll
+        for (int p = 0; p < MVA; ++p) again |= (unsigned)flow_untagged(buf[p], w_par);
+        if (MH > 0) again |= ((hbuf[0] ^ w_par) | (hbuf[1] ^ w_par)) & 1u;
+        return again;
     };
     // bias + the workers' share of the x half, checked (first check straight-line, like settle); in front of B1, off the epilogue
-    auto wsettle = [&](u32x4_f (&buf)[MVA], int sidx) __attribute__((always_inline)) -> f32x4 {
+    auto wsettle = [&](u32x4_f (&buf)[MVA], u32x2_f& hbuf, int sidx) __attribute__((always_inline)) -> f32x4 {
         f32x4 pre = (f32x4){e_bias[0], e_bias[1], e_bias[2], e_bias[3]};      // gate g of unit pu is column g*16 + pu: N tile g
         if (MV > 0) {
-            unsigned again = 0u;
-#pragma unroll
-            for (int p = 0; p < MVA; ++p) again |= (unsigned)flow_untagged(buf[p], w_par);
+            unsigned again = wuntagged(buf, hbuf);
             if (__any(again != 0u) && !dead) {
                 while (true) {
                     if (wall_clock64() - t_begin > a.limit) { dead = true; if (lane == 0) __hip_atomic_fetch_or(FLOW_G(unsigned, a.err), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-                    wissue(buf, sidx);
+                    wissue(buf, hbuf, sidx);
                     wait_all(buf);
-                    again = 0u;
-#pragma unroll
-                    for (int p = 0; p < MVA; ++p) again |= (unsigned)flow_untagged(buf[p], w_par);
+                    if (MH > 0) pin2(hbuf);
+                    again = wuntagged(buf, hbuf);
                     if (!__any(again != 0u)) break;
                 }
             }
+            // (the tag bit is cleared before the sum: the value must not depend on the launch's parity -- the same mini-batch gives
+            //  the same bits in consecutive launches, tests/test_gpu_fullsize.py's 40 steps)
 #pragma unroll
             for (int p = 0; p < MVA; ++p)
-                pre += (f32x4){__uint_as_float(buf[p][0]), __uint_as_float(buf[p][1]), __uint_as_float(buf[p][2]), __uint_as_float(buf[p][3])};
+                pre += (f32x4){__uint_as_float(buf[p][0] & ~1u), __uint_as_float(buf[p][1] & ~1u), __uint_as_float(buf[p][2] & ~1u),
+                               __uint_as_float(buf[p][3] & ~1u)};
+            if (MH > 0) { pre[2] += __uint_as_float(hbuf[0] & ~1u); pre[3] += __uint_as_float(hbuf[1] & ~1u); }      // (the half roles' tile: gates f and o)
         }
         return pre;
     };
@@ -410,20 +449,21 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
 #ifndef FWD2_RR_ACC
 #define FWD2_RR_ACC 0             // 1: the four accumulators take turns (no MFMA depends on the one in front of it)
 #endif
-    auto mma_block = [&](const u32x4_f& v, const float4 (&w)[NT]) __attribute__((always_inline)) {
+    auto mma_block = [&](const u32x4_f& v, const float4 (&w)[NT], auto ntiles) __attribute__((always_inline)) {      // ntiles: N tiles 0 .. ntiles-1
+        constexpr int NJ = decltype(ntiles)::value;
 #if FWD2_RR_ACC
 #pragma unroll
-        for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[0]), w[j].x, acc[j], 0, 0, 0);
+        for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[0]), w[j].x, acc[j], 0, 0, 0);
 #pragma unroll
-        for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[1]), w[j].y, acc[j], 0, 0, 0);
+        for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[1]), w[j].y, acc[j], 0, 0, 0);
 #pragma unroll
-        for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[2]), w[j].z, acc[j], 0, 0, 0);
+        for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[2]), w[j].z, acc[j], 0, 0, 0);
 #pragma unroll
-        for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[3]), w[j].w, acc[j], 0, 0, 0);
+        for (int j = 0; j < NJ; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[3]), w[j].w, acc[j], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
 #else
 #pragma unroll
-        for (int j = 0; j < NT; ++j) {
+        for (int j = 0; j < NJ; ++j) {
             acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[0]), w[j].x, acc[j], 0, 0, 0);
             acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[1]), w[j].y, acc[j], 0, 0, 0);
             acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[2]), w[j].z, acc[j], 0, 0, 0);
@@ -432,8 +472,9 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
 #endif
     };
     // one half of the product: the wave's KB blocks of operand `v` against the matching weight fragments
+    // (last_tiles: the N tiles of the LAST block -- NTL for the x half, whose other tiles the half roles form)
     auto half_product = [&](const auto& v, const auto& w, const u32x4_f (&wh_)[KP][NT], const u32x4_f (&wl_)[KP][NT],
-                            auto between) __attribute__((always_inline)) {
+                            auto between, auto last_tiles) __attribute__((always_inline)) {
         constexpr int NB = (int)(sizeof(v) / sizeof(v[0]));       // KB for the h half, KX for the x half
         if constexpr (BF3) {
 #pragma unroll
@@ -452,7 +493,8 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
 #pragma unroll
             for (int kb = 0; kb < NB; ++kb) {
                 between(kb);
-                mma_block(v[kb], w[kb]);
+                if (kb == NB - 1) mma_block(v[kb], w[kb], last_tiles);
+                else mma_block(v[kb], w[kb], std::integral_constant<int, NT>{});
             }
         }
     };
@@ -528,7 +570,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
                     issue(Local{}, hv, rh, (unsigned)((size_t)(t + 1) * bph * 4));
                     __builtin_amdgcn_sched_barrier(0);
                 }
-            });
+            }, std::integral_constant<int, NTL>{});
         }
     };
 #ifndef FWD2_ISSUE_AT_TOP
@@ -537,7 +579,8 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
     constexpr bool TOP = ASM && FWD2_ISSUE_AT_TOP != 0;
     // xnext / wcur: the x panel of step t+1 (its products end this step) and the workers' tiles of step t; xfree / wfree: the register sets
     // of step t-1's, free now (TOP: they take the requests for step t+2 / t+1)
-    auto step = [&](auto xpol, int t, u32x4_f (&xnext)[KX], u32x4_f (&xfree)[KX], u32x4_f (&wcur)[MVA], u32x4_f (&wfree)[MVA]) __attribute__((always_inline)) {
+    auto step = [&](auto xpol, int t, u32x4_f (&xnext)[KX], u32x4_f (&xfree)[KX], u32x4_f (&wcur)[MVA], u32x4_f (&wfree)[MVA],
+                    u32x2_f& hcur, u32x2_f& hfree) __attribute__((always_inline)) {
         // ---- h half of step t on top of the x half already in the accumulators
         F2STAMP(0);
         if constexpr (TOP) {
@@ -550,31 +593,33 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
             for (int kb = 0; kb < KX; ++kb) pin(xnext[kb]);
 #pragma unroll
             for (int p = 0; p < MVA; ++p) pin(wcur[p]);
+            if (MH > 0) pin2(hcur);
         } else if constexpr (ASM) {
             // THE wait of the step: h_{t-1} has landed (and with it everything requested before it: this step's x panel and tiles);
-            // the KX + MV loads requested behind it stay in flight
-            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(KX + MV) : "memory");
+            // the KX + MV + MH loads requested behind it stay in flight
+            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(KX + MV + MH) : "memory");
 #pragma unroll
             for (int kb = 0; kb < KB; ++kb) pin(hv[kb]);
 #pragma unroll
             for (int kb = 0; kb < KX; ++kb) pin(xnext[kb]);
 #pragma unroll
             for (int p = 0; p < MVA; ++p) pin(wcur[p]);
+            if (MH > 0) pin2(hcur);
         }
         settle(Local{}, hv, rh, (unsigned)((size_t)t * bph * 4));
         if constexpr (TOP) {
             __builtin_amdgcn_sched_barrier(0);
             if (t + 2 < T) xissue(xpol, xfree, t + 2);       // (from memory: 1.6 steps until the x half of step t+1 reads it)
-            if (t + 1 < T) wissue(wfree, t + 1);
+            if (t + 1 < T) wissue(wfree, hfree, t + 1);
             __builtin_amdgcn_sched_barrier(0);
         }
         F2STAMP(1);
-        half_product(hv, wh, whh, whl, [](int) {});
+        half_product(hv, wh, whh, whl, [](int) {}, std::integral_constant<int, NT>{});
         float (&rd)[NW][256][NT] = red_[0];
 #pragma unroll
         for (int i = 0; i < 4; ++i)          // element lane*4 + i of the 16x16 tile: its four gates (N tiles) as one 16-byte word
             *reinterpret_cast<f32x4*>(&rd[wave][lane * 4 + i][0]) = (f32x4){acc[0][i], acc[1][i], acc[2][i], acc[3][i]};
-        const f32x4 pre = wsettle(wcur, t);                                  // bias + the x-product workers' tiles of frame t
+        const f32x4 pre = wsettle(wcur, hcur, t);                                  // bias + the x-product workers' tiles of frame t
         // (the panel of the x half behind B2 is checked HERE: it landed a step ago, and behind B2 its dozen compares sat in front
         //  of the x MFMAs of every step -- the layers above the bottom one ran 0.25 us per step behind it)
         if (ASM && FWD2_EARLY_XCHECK && decltype(xpol)::value != 2 && t + 1 < T) settle(Remote{}, xnext, rx, (unsigned)((size_t)(t + 1) * bph * 4));
@@ -597,13 +642,13 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
         } else if constexpr (ASM) {
             __builtin_amdgcn_sched_barrier(0);
             xissue(xpol, xnext, t + 3 < T ? t + 3 : T - 1);      // (past the end: the last frame again -- one order of operations, one wait count)
-            wissue(wcur, t + 2 < T ? t + 2 : T - 1);
+            wissue(wcur, hcur, t + 2 < T ? t + 2 : T - 1);
             __builtin_amdgcn_sched_barrier(0);
         } else {
             if (t + 1 < T) {
                 if (t + 3 < T) xissue(xpol, xnext, t + 3);
             }
-            if (t + 2 < T) wissue(wcur, t + 2);
+            if (t + 2 < T) wissue(wcur, hcur, t + 2);
         }
     };
 #undef F2STAMP
@@ -614,19 +659,21 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
         if (decltype(xpol)::value != 2) settle(Remote{}, xa, rx, 0u);
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        half_product(xa, wx, wxh, wxl, [](int) {});
+        half_product(xa, wx, wxh, wxl, [](int) {}, std::integral_constant<int, NTL>{});
         xissue(xpol, xb, T > 1 ? 1 : 0);               // (clamped: a short sequence re-reads its last frame)
         if constexpr (!TOP) xissue(xpol, xa, T > 2 ? 2 : T - 1);
         issue(Local{}, hv, rh, 0u);                                              // slot 0: the packed initial state
-        wissue(wa, 0);
-        if constexpr (!TOP) wissue(wb, T > 1 ? 1 : 0);
-        wait_all(xa); wait_all(xb); wait_all(hv); wait_all(wa); wait_all(wb);   // (once: the loop's own wait assumes its own order of requests)
+        wissue(wa, wha, 0);
+        if constexpr (!TOP) wissue(wb, whb, T > 1 ? 1 : 0);
+        wait_all(xa); wait_all(xb); wait_all(hv); wait_all(wa); wait_all(wb);
+        if (MH > 0) { pin2(wha); pin2(whb); }   // (once: the loop's own wait assumes its own order of requests)
         __syncthreads();
         for (int t = 0; t < T; t += 2) {
-            step(xpol, t, xb, xa, wa, wb);                         // consumes x[t+1] (odd) at its end
-            if (t + 1 < T) step(xpol, t + 1, xa, xb, wb, wa);      // consumes x[t+2] (even)
+            step(xpol, t, xb, xa, wa, wb, wha, whb);                       // consumes x[t+1] (odd) at its end
+            if (t + 1 < T) step(xpol, t + 1, xa, xb, wb, wa, whb, wha);     // consumes x[t+2] (even)
         }
-        wait_all(xa); wait_all(xb); wait_all(wa); wait_all(wb);      // (the last steps' requests: nothing may land in a register after its last use)
+        wait_all(xa); wait_all(xb); wait_all(wa); wait_all(wb);
+        if (MH > 0) { pin2(wha); pin2(whb); }                        // (the last steps' requests: nothing may land in a register after its last use)
     };
     if (l == 0) run(Local{}); else run(Remote{});
     __syncthreads();

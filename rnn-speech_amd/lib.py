@@ -48,7 +48,7 @@ LSTM_ARMED, LSTM_ARM_NEXT, LSTM_SAME_WS, LSTM_PER_DIAGONAL, LSTM_INJECT_TIMEOUT 
 
 
 COMM_ID_BYTES = 128
-WS_Z0, WS_ZTOP, WS_DZTOP, WS_DZ0, WS_HFINAL, WS_CFINAL = range(6)
+WS_Z0, WS_ZTOP, WS_DZTOP, WS_DZ0, WS_HFINAL, WS_CFINAL, WS_GATES = range(7)
 BIDIR_WS_Z0, BIDIR_WS_YTOP_FW, BIDIR_WS_YTOP_BW, BIDIR_WS_DYTOP_FW, BIDIR_WS_DYTOP_BW, BIDIR_WS_DZ0, BIDIR_WS_HFINAL, BIDIR_WS_CFINAL = range(8)
 
 _P = C.c_void_p
@@ -91,6 +91,7 @@ PROTOTYPES = {
     "amdspeech_lstm_bwd_ctc": (_I, [_P, C.POINTER(LstmDesc), _P, _P, _L, _P, _P, _L, _P, C.POINTER(CtcHead)]),
     "amdspeech_lstm_dropout_multipliers": (_I, [_P, C.POINTER(LstmDesc), _I, _I, _P]),
     "amdspeech_lstm_plan": (_I, [C.POINTER(LstmDesc), _I, _I, C.POINTER(LstmPlanInfo)]),
+    "amdspeech_lstm_plan_xw_halves": (_I, [C.POINTER(LstmDesc), _I, _I]),
     "amdspeech_lstm_bidir_workspace_bytes": (_SZ, [C.POINTER(LstmDesc)]),
     "amdspeech_lstm_bidir_ws_ptr": (_P, [C.POINTER(LstmDesc), _P, _I]),
     "amdspeech_lstm_bidir_layer_stride": (_L, [C.POINTER(LstmDesc)]),
