@@ -417,6 +417,32 @@ typedef struct amdspeech_ctc_plan_info {
 } amdspeech_ctc_plan_info;
 int amdspeech_ctc_plan(int T, int B, int C, int U, amdspeech_ctc_plan_info* out);
 
+/* Forced alignment: the best CTC alignment (Viterbi path) of a KNOWN transcript to the frames.  Same arguments, same label
+ * sparsification, same limits and messages as amdspeech_ctc_loss_fwd_bwd; a workspace of its own (the loss's is untouched, so a
+ * loss call and an alignment of the same logits may be queued back to back).
+ *   v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2) where the skip is legal) + log p_t(ext[s])   over the S = 2 n + 1
+ * extended states, the state in float64 over the float32 log-softmax.  TIES go to the SMALLEST step (stay, then +1, then +2), and
+ * at the last frame state S-1 wins over S-2: this rule is part of the contract.
+ * Outputs, all DEVICE:
+ *   frame_label [B][T]   the label emitted at each frame (C-1: blank), -1 for t >= lengths[b]
+ *   frame_state [B][T]   the extended-state index at each frame, -1 for t >= lengths[b]
+ *   spans       [B][U][2] first and last frame of every kept target label, in target order; -1 in unused slots
+ *   score       [B]      natural-log probability of the best path; -inf where the target cannot be aligned (the loss is inf there);
+ *                        0 for the rows the loss ignores (lengths[b] == 0 or required_time > lengths[b])
+ *   confidence  [B][U]   exp(mean log p over the label's frames); 0 in unused slots
+ * Rows with score 0 (ignored) or -inf have -1 in every frame and span.
+ * Workspace (amdspeech_ctc_align_workspace_bytes; 256-byte aligned; each region rounded up to 256 bytes), in this order:
+ *   log p  T*B*C*4 | extended targets  B*(2U+1)*4 | S  B*4 | valid  B*4 | final state  B*4 | best score  B*4 |
+ *   back-pointers  B*T*pitch,  pitch = ceil((2U+1)/4) rounded up to 4: two bits per (frame, state)
+ * amdspeech_ctc_align_plan: the recursion kernel a shape takes (one function decides for it and for the launch): WAVE, one
+ * wavefront of two states per lane, up to 128 extended states; above that EDGE, 256 threads of `rmax` = 2 / 4 / 8 / 12 / 16 / 20 states
+ * each (512 / 1024 / 2048 / 3072 / 4096 / 5119 states) with one LDS edge exchange per frame.  No run-time switch.                    */
+size_t amdspeech_ctc_align_workspace_bytes(int T, int B, int C, int U);
+int amdspeech_ctc_align_plan(int T, int B, int C, int U, amdspeech_ctc_plan_info* out);
+int amdspeech_ctc_align(void* stream, const float* logits, const int* dense_labels, const int* lengths,
+                        int T, int B, int C, int U, int* frame_label, int* frame_state, int* spans,
+                        float* score, float* confidence, void* ws);
+
 /* Greedy decode: per-frame argmax (first maximum), collapse repeats, drop the
  * blank C-1.  Stands where tf.nn.ctc_beam_search_decoder sits at
  * models/AcousticModel.py:312.  ids [B,T] is padded with C (the

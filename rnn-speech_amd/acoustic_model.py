@@ -1039,6 +1039,28 @@ class AcousticModel(object):
         self.engine.check()                # a bounded-wait time-out of the dataflow kernels invalidates the logits
         return pred
 
+    @_engine_stream
+    def align(self, session, inputs, input_seq_lengths, labels):
+        """Forced alignment: inputs [T_max, B, D], lengths [B], labels the transcripts' token ids (a 0-padded dense matrix
+        [B, U] as the labels placeholder takes it, or one id list per utterance; an EOS ends a transcript).  Returns per utterance
+        a list of (token, first_frame, last_frame, confidence) in transcript order, confidence = exp(mean log p of the token over
+        its frames); the list is empty for an utterance the CTC loss would ignore or whose transcript cannot be aligned."""
+        U = self.max_target_seq_length
+        dense = np.zeros((self.batch_size, U), np.int32)
+        for b, row in enumerate(labels):
+            row = np.asarray(row, np.int64).reshape(-1)[:U]
+            dense[b, :len(row)] = row
+        x, dlen, ddense = self._to_device(inputs, input_seq_lengths, dense)
+        al = self.engine.align(x, dlen, ddense)
+        spans, conf = al.spans.cpu().numpy(), al.confidence.cpu().numpy()      # (reads the result back: the stream is drained)
+        self.engine.check()                # a bounded-wait time-out of the dataflow kernels invalidates the logits
+        out = []
+        for b in range(self.batch_size):
+            target = [int(v) for v in dense[b] if v != 0]
+            out.append([(target[u], int(spans[b, u, 0]), int(spans[b, u, 1]), float(conf[b, u]))
+                        for u in range(U) if spans[b, u, 0] >= 0])
+        return out
+
     def _decode(self, dlen):
         """Dense int32 prediction matrix [B, width] padded with num_labels."""
         if self.decoder == "beam":

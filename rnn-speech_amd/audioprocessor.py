@@ -32,6 +32,9 @@ class AudioProcessor(object):
             raise ValueError("{0} is not a valid extraction function, only fbank and mfcc are accepted."
                              .format(feature_type))
         self.n_mfcc = int(n_mfcc)
+        # samples between the starts of two frames (csrc/frontend.hip: 10 ms, rounded half to even, in both modes): frame t of a
+        # file starts t * hop_samples / load_sr seconds in
+        self.hop_samples = int(round(self.load_sr * 0.01))
 
     @staticmethod
     def get_mfcc_length_from_duration(duration):

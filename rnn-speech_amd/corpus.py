@@ -251,6 +251,7 @@ class DataProcessor(object):
     clean_label = staticmethod(_labels.clean_label)
     get_str_labels = staticmethod(_labels.get_str_labels)
     get_labels_str = staticmethod(_labels.get_labels_str)
+    group_words = staticmethod(_labels.group_words)      # (this build's own: aligned tokens -> aligned words, stt.py --align)
     get_str_to_one_hot_encoded = staticmethod(_labels.get_str_to_one_hot_encoded)
     find_files = staticmethod(find_files)
     extract_wav_from_sph = staticmethod(cut_sphere_segment)

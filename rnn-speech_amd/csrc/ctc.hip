@@ -697,11 +697,16 @@ extern "C" size_t amdspeech_ctc_workspace_bytes(int T, int B, int C, int U) {
 // ---- which recursion kernel a shape takes: the ONE place that decides (the launch below and amdspeech_ctc_plan read it) ----
 namespace amdspeech {
 struct CtcPlan { int kernel, threads, rmax, smax; };      // amdspeech_ctc_plan_info (amdspeech.h)
-static int ctc_plan(int T, int B, int C, int U, CtcPlan* p) {
+// the shapes every CTC call takes (the loss and the aligner of ctc_align.h: one set of limits, one set of messages)
+static int ctc_check_shape(int T, int B, int C, int U) {
     AS_CHECK_ARG(T > 0 && B > 0 && C > 1 && U > 0, "ctc: bad shape T=%d B=%d C=%d U=%d", T, B, C, U);
     AS_CHECK_ARG(C <= 4096, "ctc: C=%d too large", C);
+    AS_CHECK_ARG(U <= 2559 && 2 * U + 1 <= 256 * 20, "ctc: label width U=%d exceeds the supported 2559", U);
+    return AMDSPEECH_OK;
+}
+static int ctc_plan(int T, int B, int C, int U, CtcPlan* p) {
+    if (int rc = ctc_check_shape(T, B, C, U)) return rc;
     const int smax = 2 * U + 1;
-    AS_CHECK_ARG(U <= 2559 && smax <= 256 * 20, "ctc: label width U=%d exceeds the supported 2559", U);
     // 4 waves per (utterance, direction) once the targets are long enough to feed them
     const bool wide = smax > 128;
     const int rneed = ceil_div(smax, wide ? 256 : 64);
@@ -723,6 +728,9 @@ extern "C" int amdspeech_ctc_plan(int T, int B, int C, int U, amdspeech_ctc_plan
     *out = amdspeech_ctc_plan_info{p.kernel, p.threads, p.rmax, p.smax};
     return AMDSPEECH_OK;
 }
+
+// ---- forced alignment: the Viterbi recursion, the walk back and their entry points (amdspeech_ctc_align*) ----
+#include "ctc_align.h"
 
 extern "C" int amdspeech_ctc_loss_fwd_bwd(void* stream, const float* logits, const int* dense_labels,
                                           const int* lengths, int T, int B, int C, int U, float* loss,

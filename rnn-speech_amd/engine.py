@@ -364,6 +364,17 @@ class Engine(object):
             self.dlogits[Tr:].zero_()
         return self.loss
 
+    def align(self, x, lengths, dense_labels):
+        """Forced alignment of known transcripts: a forward pass in inference mode (no dropout) and the best CTC alignment of
+        `dense_labels` (int32 [B,U], 0-padded as mini_batch takes them) to the frames of its logits.  Returns an ops.CtcAlignment
+        (frame_label / frame_state [B,T], spans [B,U,2], score [B], confidence [B,U]).  Reads the logits only: every stack the
+        engine builds (uni-directional, top-joined and layer-wise bidirectional) takes it."""
+        self.forward(x, lengths)
+        shape = (self.T, self.B, self.C, dense_labels.shape[1])
+        if getattr(self, "_align_ws", None) is None or self._align_ws.shape != shape:
+            self._align_ws = ops.CtcAlignWorkspace(*shape, device=self.device)
+        return ops.ctc_align(self.logits, dense_labels.contiguous(), lengths, ws=self._align_ws)
+
     @contextlib.contextmanager
     def on_stream(self):
         """Run the enclosed engine calls on the engine's own (non-default) stream, ordered after the

@@ -87,3 +87,24 @@ def get_str_to_one_hot_encoded(char_map, text, add_eos=True):
     ids = get_str_labels(char_map, text, add_eos=add_eos)
     eye = np.eye(len(char_map))
     return [eye[i].copy() for i in ids]
+
+
+def group_words(char_map, tokens):
+    """Aligned tokens -> aligned words.  tokens: (token id, first_frame, last_frame, confidence) in transcript order (what
+    AcousticModel.align returns for one utterance).  The codec CamelCases its text (get_str_labels), so a capitalised token starts
+    a word -- the inverse of get_labels_str -- and so does the first token.  Returns (word, first_frame, last_frame, confidence)
+    per word: lower-cased text, from the first frame of its first token to the last frame of its last, the confidence the
+    MINIMUM over its tokens."""
+    words = []
+    for tok_id, first, last, conf in tokens:
+        if not 0 <= int(tok_id) < len(char_map) - 1:      # (out of range, or the EOS: not part of any word)
+            continue
+        tok = char_map[int(tok_id)]
+        if not words or tok.isupper():
+            words.append([tok.lower(), int(first), int(last), float(conf)])
+        else:
+            w = words[-1]
+            w[0] += tok.lower()
+            w[2] = int(last)
+            w[3] = min(w[3], float(conf))
+    return [tuple(w) for w in words]

@@ -602,6 +602,54 @@ def ctc_loss_fwd_bwd(logits, dense_labels, lengths, ws=None, loss=None, dlogits=
     return loss, dlogits
 
 
+class CtcAlignWorkspace(object):
+    """The aligner's own workspace (amdspeech.h: amdspeech_ctc_align_workspace_bytes): log p, extended targets, back-pointers."""
+
+    def __init__(self, T, B, C_, U, device="cuda"):
+        self.lib = _l.load()
+        n = self.lib.amdspeech_ctc_align_workspace_bytes(T, B, C_, U)
+        if n == 0:
+            raise _l.AmdSpeechError("ctc align workspace: bad shape")
+        self.shape = (T, B, C_, U)
+        self.buf = torch.empty(n, device=device, dtype=torch.uint8)
+
+
+class CtcAlignment(object):
+    """What ctc_align returns, all device tensors (amdspeech.h: amdspeech_ctc_align): frame_label [B,T], frame_state [B,T],
+    spans [B,U,2] int32; score [B], confidence [B,U] float32."""
+    __slots__ = ("frame_label", "frame_state", "spans", "score", "confidence")
+
+    def __init__(self, frame_label, frame_state, spans, score, confidence):
+        self.frame_label, self.frame_state, self.spans, self.score, self.confidence = frame_label, frame_state, spans, score, confidence
+
+
+def ctc_align_plan(T, B, C_, U):
+    """The recursion kernel ctc_align takes for a shape (amdspeech.h: amdspeech_ctc_align_plan), as ctc_plan reports the loss's."""
+    info = _l.CtcPlanInfo()
+    _l.check(_l.load().amdspeech_ctc_align_plan(int(T), int(B), int(C_), int(U), C.byref(info)), "ctc_align_plan")
+    out = {name: int(getattr(info, name)) for name, _ in _l.CtcPlanInfo._fields_}
+    out["kernel"] = _l.CTC_KERNELS[out["kernel"]]
+    return out
+
+
+def ctc_align(logits, dense_labels, lengths, ws=None):
+    """The best CTC alignment of the transcripts to the frames: logits [T,B,C]; dense_labels int32 [B,U] (0-padded, as
+    ctc_loss_fwd_bwd takes them); lengths int32 [B].  Returns a CtcAlignment."""
+    _chk_f32(logits)
+    _chk_i32(dense_labels, lengths)
+    T, B, C_ = logits.shape
+    U = dense_labels.shape[1]
+    if ws is None or ws.shape != (T, B, C_, U):      # (the back-pointer rows are laid out by T: no prefix use)
+        ws = CtcAlignWorkspace(T, B, C_, U, logits.device)
+    dev = logits.device
+    out = CtcAlignment(torch.empty(B, T, device=dev, dtype=torch.int32), torch.empty(B, T, device=dev, dtype=torch.int32),
+                       torch.empty(B, U, 2, device=dev, dtype=torch.int32), torch.empty(B, device=dev, dtype=torch.float32),
+                       torch.empty(B, U, device=dev, dtype=torch.float32))
+    _l.check(ws.lib.amdspeech_ctc_align(_stream(), _p(logits), _p(dense_labels), _p(lengths), T, B, C_, U, _p(out.frame_label),
+                                        _p(out.frame_state), _p(out.spans), _p(out.score), _p(out.confidence), _p(ws.buf)), "ctc_align")
+    return out
+
+
 def ctc_greedy_decode(logits, lengths, ws=None):
     """Returns (ids int32 [B,T] padded with C, out_len int32 [B])."""
     _chk_f32(logits)

@@ -1,7 +1,8 @@
 # coding=utf-8
 """Command line of the speech recogniser -- same flags and loop semantics as the reference's
 stt.py (argument parser :360-404, train loop + LR plateau rule :171-236, file / evaluate modes
-:239-324), driving the MI355X-native AcousticModel instead of a TensorFlow session.
+:239-324), driving the MI355X-native AcousticModel instead of a TensorFlow session.  One mode is this build's own:
+--align AUDIO --transcript "text" prints when each word of a known transcript was spoken (forced CTC alignment).
 
 Not kept (out of the hot-path scope): --train_language / --generate_text (the
 reference's language model is an unfinished stub), --record (pyaudio), --XLA (no tracing
@@ -75,6 +76,8 @@ def main():
         process_file(audio_processor, hyper_params, prog_params["file"])
     elif prog_params["evaluate"]:
         evaluate(hyper_params)
+    elif prog_params["align"] is not None:
+        align_file(audio_processor, hyper_params, prog_params["align"], _transcript(prog_params))
     else:
         sys.exit("mode not supported by the MI355X build (see module docstring)")
 
@@ -230,6 +233,41 @@ def process_file(audio_processor, hyper_params, file):
     return transcribed_text
 
 
+def _transcript(prog_params):
+    if prog_params["transcript_file"] is not None:
+        with open(prog_params["transcript_file"]) as fh:
+            return fh.read()
+    if prog_params["transcript"] is None:
+        sys.exit("--align needs --transcript TEXT or --transcript_file PATH")
+    return prog_params["transcript"]
+
+
+def align_file(audio_processor, hyper_params, file, transcript):
+    """--align: when was each word of a known transcript spoken?  The restored model at batch 1, the best CTC alignment of the
+    transcript's tokens to the frames (AcousticModel.align), tokens grouped into words.  Prints one line per word:
+    start_s end_s confidence word -- the times of the word's first and last frame, frame t being t * hop / sample_rate into the
+    file (the front end's 10 ms hop)."""
+    feat_vec, original_length = audio_processor.process_audio_file(file)
+    T = hyper_params["max_input_seq_length"]
+    if original_length > T:
+        logging.warning("File too long: %d frames, truncated to %d", original_length, T)
+    padded = np.zeros((T, 1, feat_vec.shape[1]), np.float32)
+    padded[:len(feat_vec), 0] = feat_vec
+    char_map = hyper_params["char_map"]
+    ids = dataprocessor.DataProcessor.get_str_labels(char_map, dataprocessor.DataProcessor.clean_label(transcript), add_eos=False)
+    if len(ids) > hyper_params["max_target_seq_length"]:
+        sys.exit("transcript too long: %d tokens, max_target_seq_length is %d" % (len(ids), hyper_params["max_target_seq_length"]))
+    model = _forward_model(hyper_params, 1)
+    tokens = model.align(None, padded, [min(original_length, T)], [ids])[0]
+    if not tokens:
+        sys.exit("the transcript cannot be aligned to this recording (more tokens than frames?)")
+    frame_s = audio_processor.hop_samples / float(audio_processor.load_sr)
+    words = dataprocessor.DataProcessor.group_words(char_map, tokens)
+    for word, first, last, conf in words:
+        print("%.3f %.3f %.3f %s" % (first * frame_s, last * frame_s, conf, word))
+    return words
+
+
 def evaluate(hyper_params):
     if hyper_params["test_dataset_dirs"] is None:
         logging.fatal("Setting test_dataset_dirs in config file is mandatory for evaluation mode")
@@ -258,7 +296,8 @@ _MODES = (("train_acoustic", "store_true", "train the acoustic model"),
           ("file", str, "transcribe one wav file"),
           ("record", "store_true", "live microphone mode -- not supported here"),
           ("evaluate", "store_true", "WER / CER of the restored model on the test manifest"),
-          ("generate_text", "store_true", "reference stub -- not supported here"))
+          ("generate_text", "store_true", "reference stub -- not supported here"),
+          ("align", str, "align a known transcript (--transcript / --transcript_file) to one audio file: a line per word"))
 
 
 def parse_args():
@@ -276,10 +315,12 @@ def parse_args():
     parser.add_argument("--learn_rate", type=float, default=None, help="override the stored learning rate")
     parser.add_argument("--timeline", action="store_true", help="log per-step timings")
     parser.add_argument("--XLA", action="store_true", help="kept for compatibility, ignored")
+    parser.add_argument("--transcript", default=None, help="--align: the text spoken in the file")
+    parser.add_argument("--transcript_file", default=None, help="--align: a file holding that text")
     ns = parser.parse_args()
     out = {name: getattr(ns, name) for name, _, _ in _MODES}
     out.update(config_file=ns.config, tb_name=ns.tb_name, max_epoch=ns.max_epoch, learn_rate=ns.learn_rate,
-               timeline=ns.timeline, XLA=ns.XLA)
+               timeline=ns.timeline, XLA=ns.XLA, transcript=ns.transcript, transcript_file=ns.transcript_file)
     return out
 
 
