@@ -80,6 +80,46 @@ int amdspeech_gemm_bf16x3(void* stream, int transA, int transB, int M, int N, in
 int amdspeech_gemm_bf16(void* stream, int transA, int transB, int M, int N, int K,
                         const float* A, int lda, const float* B, int ldb,
                         float* C, int ldc, const float* bias, int accumulate);
+
+/* Which kernel one of the three products above takes for a shape, and its launch geometry, as plain numbers: a READ-ONLY view of
+ * the plan every product is launched from (one function plans for both).  Nothing is launched and no device is touched; the
+ * pointers are inspected for null and alignment only, never dereferenced.  Arguments are checked as the call checks them, with
+ * the call's own message.
+ *   precision  0 amdspeech_gemm_f32, 1 amdspeech_gemm_bf16x3, 2 amdspeech_gemm_bf16 (as amdspeech_lstm_desc.precision): 1 and 2 report
+ *              family BF3 or, where that kernel's addressing does not fit, what the f32 ladder takes instead
+ *   colsum     != 0: with the fused column sums of B (amdspeech_linear_bwd's weight-gradient product)
+ *   count      1: the single product; 2 .. AMDSPEECH_GEMM_GROUP_MAX: amdspeech_gemm_f32_tn_group (A, B, C: problem 0's operands)
+ * The struct:
+ *   family     AMDSPEECH_GEMM_* below
+ *   variant    the kernel's template arguments as the launch switches on them: SKINNY_N NT (1 .. 6); SKINNY_K KT * 2 + transB
+ *              (KT 3 or 5); SKINNY_TN FULL * 8 + RT; TN_DIRECT the number of problems; KC_DIRECT transB; LDS A_KC * 2 + B_KC
+ *              (A_KC = !transA, B_KC = transB); BF3 single * 4 + A_KC * 2 + B_KC
+ *   splits, k_chunk   K ranges and their length (SKINNY_TN: row chunks, those that start past K add nothing);  atomic: the result
+ *              leaves through f32 atomics;  zero_fill: a fill launch precedes;  grid: workgroups of the main launch
+ *   tiles_m, tiles_n  output tiles (SKINNY_*: row blocks / 64-column slices)
+ *   map        workgroup -> tile: AMDSPEECH_GEMM_MAP_* below;  bm, bn: the block of MAP_XCD_BLOCKS;  col_slices: SKINNY_K's slices of N
+ *   a_vec, b_vec      16-byte loads on that operand (0: the scalar loads of the LDS kernel)                                     */
+enum { AMDSPEECH_GEMM_SKINNY_N = 0, AMDSPEECH_GEMM_SKINNY_K = 1, AMDSPEECH_GEMM_SKINNY_TN = 2, AMDSPEECH_GEMM_TN_DIRECT = 3,
+       AMDSPEECH_GEMM_KC_DIRECT = 4, AMDSPEECH_GEMM_LDS = 5, AMDSPEECH_GEMM_BF3 = 6 };
+enum { AMDSPEECH_GEMM_MAP_LINEAR = 0, AMDSPEECH_GEMM_MAP_XCD = 1, AMDSPEECH_GEMM_MAP_XCD_BLOCKS = 2, AMDSPEECH_GEMM_MAP_KC_BAND = 3 };
+enum { AMDSPEECH_GEMM_GROUP_MAX = 10 };
+typedef struct amdspeech_gemm_plan_info {
+    int family, variant, splits, k_chunk, atomic, zero_fill, grid, tiles_m, tiles_n, map, bm, bn, col_slices, a_vec, b_vec;
+} amdspeech_gemm_plan_info;
+int amdspeech_gemm_plan(int precision, int transA, int transB, int M, int N, int K,
+                        const void* A, int lda, const void* B, int ldb, const void* C, int ldc,
+                        const void* bias, int accumulate, int colsum, int count,
+                        amdspeech_gemm_plan_info* out);
+
+/* Exposed for tests / bench: `count` (1 .. AMDSPEECH_GEMM_GROUP_MAX) products C_i[M,N] (+)= A_i^T . B_i of ONE shape in one launch (the
+ * weight gradients of an LSTM backward pass); A_i [K][M], B_i [K][N], rows 16-byte aligned.  A, B, C, colsum: HOST arrays of `count`
+ * device pointers; colsum (or single entries of it) may be NULL, else colsum_i[N] += column sums of B_i.  A shape or an operand
+ * the kernel does not take is AMDSPEECH_EINVAL (no other kernel is tried).  Bytes between the width and the stride of an
+ * operand row are read and must be readable (their values reach no result).                                                     */
+int amdspeech_gemm_f32_tn_group(void* stream, int count, int M, int N, int K, const float* const* A, int lda,
+                                const float* const* B, int ldb, float* const* C, int ldc, float* const* colsum, int accumulate);
+/* out[c] += sum over rows of x[r * ld + c]: the bias gradients of the reduced-precision path. */
+int amdspeech_colsum_accumulate(void* stream, const float* x, int rows, int cols, int ld, float* out);
 /* ... the same product through bf16 COPIES of the operands (round 5; what lstm_fwd / lstm_bwd run at H = 1024 with precision = 2):
  * each operand is copied once as bf16 with the contraction index contiguous (a 64 x 64 transpose where it is not), a 256 x 256 x 64
  * kernel streams the copies into LDS with global_load_lds, split K goes through f32 partial tiles (no atomics).  Same values

@@ -80,18 +80,31 @@ int gemm_f32(hipStream_t s, bool transA, bool transB, int M, int N, int K, const
              float* colsum = nullptr,    // colsum[n] += sum_k B[k][n] (needs !transB), fused bias gradient
              const int* gate = nullptr, int gate_need = 0,    // device word counted down by a concurrent producer
              unsigned* gate_err = nullptr);                  // error word: bit 2 = the gate wait timed out
-// gemm_skinny.hip: 1 = taken (N <= 96 or K <= 80 with M >= 256, 16-byte aligned rows), 0 = not this shape, < 0 = error
-int gemm_skinny(hipStream_t s, bool transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                const float* bias, bool accumulate);
+// Which kernel a product takes and its launch geometry (amdspeech.h: amdspeech_gemm_plan_info).  Every GEMM entry point plans first
+// (no pointer is dereferenced, nothing is launched) and launches from the struct; amdspeech_gemm_plan returns the same struct.
+typedef amdspeech_gemm_plan_info GemmPlan;
+int gemm_f32_plan(bool transA, bool transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, const float* C,
+                  int ldc, const float* bias, bool accumulate, bool colsum, bool gate, GemmPlan* out);
+int gemm_f32_launch(hipStream_t s, const GemmPlan& p, bool transA, bool transB, int M, int N, int K, const float* A, int lda,
+                    const float* B, int ldb, float* C, int ldc, const float* bias, bool accumulate, float* colsum = nullptr,
+                    const int* gate = nullptr, int gate_need = 0, unsigned* gate_err = nullptr);
+// gemm_skinny.hip: true = taken (N <= 96 or K <= 80 with M >= 256, 16-byte aligned rows), false = not this shape
+bool gemm_skinny_plan(bool transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, const float* C, int ldc,
+                      const float* bias, GemmPlan* out);
+int gemm_skinny_launch(hipStream_t s, const GemmPlan& p, bool transB, int M, int N, int K, const float* A, int lda, const float* B,
+                       int ldb, float* C, int ldc, const float* bias, bool accumulate);
 // the same file's 32k-row reduction onto a narrow output, C (+)= A^T . B with min(M, N) <= 124 (the dense layers' weight gradients)
-int gemm_skinny_tn(hipStream_t s, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                   bool accumulate, float* colsum);
-constexpr int GEMM_GROUP_MAX = 10;
+bool gemm_skinny_tn_plan(int M, int N, int K, const float* A, int lda, const float* B, int ldb, bool accumulate, bool colsum, GemmPlan* out);
+int gemm_skinny_tn_launch(hipStream_t s, const GemmPlan& p, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
+                          float* C, int ldc, bool accumulate, float* colsum);
+constexpr int GEMM_GROUP_MAX = AMDSPEECH_GEMM_GROUP_MAX;
 // `count` products C_i (+)= A_i^T . B_i of ONE shape (A_i [K][M], B_i [K][N], 16-byte aligned rows) in one launch
 int gemm_f32_tn_group(hipStream_t s, int count, int M, int N, int K, const float* const* A, int lda, const float* const* B,
                       int ldb, float* const* C, int ldc, float* const* colsum, bool accumulate,
                       const int* gate = nullptr, int gate_need = 0, unsigned* gate_err = nullptr);
 bool gemm_f32_tn_group_ok(int M, int N, int K, const float* A, int lda, const float* B, int ldb);   // alignment / 32-bit offsets
+int gemm_f32_tn_group_plan(int count, int M, int N, int K, const float* A, int lda, const float* B, int ldb, const float* C,
+                           bool accumulate, GemmPlan* out);      // (problem 0's operands stand for all)
 int colsum_accumulate(hipStream_t s, const float* x, int rows, int cols, int ld, float* out);
 // The same product in split precision (gemm_bf3.hip): bf16 hi / lo pairs of every f32 value, hi.hi + hi.lo + lo.hi on the bf16
 // MFMA, f32 accumulation and f32 operands / result in memory.  No fused column sum, no gate.
@@ -100,6 +113,9 @@ int gemm_bf3(hipStream_t s, bool transA, bool transB, int M, int N, int K, const
 // ... and with plain bf16 operands (precision = bf16): ONE bf16 per value, one MFMA per product, f32 accumulation and f32 in memory.
 int gemm_bf16(hipStream_t s, bool transA, bool transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
               float* C, int ldc, const float* bias, bool accumulate);
+// the plan of either: family BF3 (variant = single * 4 + A_KC * 2 + B_KC), or what gemm_f32 plans where the kernel's addressing does not fit
+int gemm_bf_plan(bool single, bool transA, bool transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
+                 const float* C, int ldc, const float* bias, bool accumulate, GemmPlan* out);
 
 // gemm_bf16p.hip (round 5): ... through bf16 COPIES of the operands (k contiguous) and a 256 x 256 x 64 global_load_lds kernel.
 // The two steps separately -- lstm.hip shares copies between products -- and the one-call form with caller scratch.

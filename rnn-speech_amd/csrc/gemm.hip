@@ -10,6 +10,7 @@
 // one K-tile ahead of the MFMAs; split-K (+ f32 atomics) fills the 256 CUs when
 // M*N is small and K is the 32k-frame axis.
 #include "gemm_core.h"
+#include <string.h>
 
 namespace amdspeech {
 
@@ -123,8 +124,18 @@ __global__ void fill_strided_kernel(float* C, int M, int N, int ldc, float v) {
     if (i < (long)M * N) C[(i / N) * ldc + (i % N)] = v;
 }
 
+// ---- the plan: which kernel a product takes and its launch geometry, as plain numbers (amdspeech.h: amdspeech_gemm_plan_info).
+// Every entry point below first PLANS (shape, strides, alignment -> GemmPlan; no pointer is dereferenced, nothing is launched) and
+// then LAUNCHES from that struct; amdspeech_gemm_plan returns the same struct to the caller.  The conditions exist once.
+static GemmPlan plan_blank() {
+    GemmPlan p;
+    memset(&p, 0, sizeof(p));
+    p.splits = 1; p.col_slices = 1;
+    return p;
+}
+
 // C_i [M,N] (+)= A_i^T . B_i for `count` problems of one shape, both operands row contiguous ([K][M], [K][N]); see
-// gemm_tile_tn_direct.  Returns AMDSPEECH_OK, or -1 when the shape / alignment does not qualify (nothing launched).
+// gemm_tile_tn_direct.
 static bool tn_direct_ok(int M, int N, int K, const float* A, int lda, const float* B, int ldb) {
     static const bool enabled = runtime_switch("AMDSPEECH_GEMM_DIRECT", 1) != 0;
     return enabled && M >= 2 && N >= 2 && (uintptr_t)A % 16 == 0 && lda % 4 == 0 && (uintptr_t)B % 16 == 0 && ldb % 4 == 0 &&
@@ -133,17 +144,15 @@ static bool tn_direct_ok(int M, int N, int K, const float* A, int lda, const flo
 bool gemm_f32_tn_group_ok(int M, int N, int K, const float* A, int lda, const float* B, int ldb) {
     return tn_direct_ok(M, N, K, A, lda, B, ldb);
 }
-int gemm_f32_tn_group(hipStream_t s, int count, int M, int N, int K, const float* const* A, int lda, const float* const* B,
-                      int ldb, float* const* C, int ldc, float* const* colsum, bool accumulate,
-                      const int* gate, int gate_need, unsigned* gate_err) {
+// (A, B, C: problem 0's operands -- the launch checks the others the same way)
+int gemm_f32_tn_group_plan(int count, int M, int N, int K, const float* A, int lda, const float* B, int ldb, const float* C,
+                           bool accumulate, GemmPlan* out) {
     AS_CHECK_ARG(count >= 1 && count <= GEMM_GROUP_MAX && M > 0 && N > 0 && K > 0, "gemm group: bad shape");
-    GemmGroupArgs a;
-    GemmArgs& g = a.g;
-    g.A = nullptr; g.B = nullptr; g.C = nullptr; g.bias = nullptr; g.colsum = nullptr;
-    g.gate = gate; g.gate_need = gate_need; g.gate_limit = 300000000ull; g.gate_err = gate_err;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.tiles_m = ceil_div(M, BM); g.tiles_n = ceil_div(N, BN);
-    const int tiles = g.tiles_m * g.tiles_n;
+    AS_CHECK_ARG(A && B && C && tn_direct_ok(M, N, K, A, lda, B, ldb), "gemm group: operand %d does not qualify", 0);
+    GemmPlan p = plan_blank();
+    p.family = AMDSPEECH_GEMM_TN_DIRECT; p.variant = count;
+    p.tiles_m = ceil_div(M, BM); p.tiles_n = ceil_div(N, BN);
+    const int tiles = p.tiles_m * p.tiles_n;
     // one workgroup (one wave per SIMD) per CU keeps the MFMA pipe full here: split K up to 256 workgroups per problem,
     // no further (every split ends in a tile of f32 atomics)
     static const int target_wgs = dev_knob("AMDSPEECH_GEMM_TN_WGS", 256);
@@ -153,37 +162,57 @@ int gemm_f32_tn_group(hipStream_t s, int count, int M, int N, int K, const float
         const int max_splits = K / 256 > 0 ? K / 256 : 1;
         if (splits > max_splits) splits = max_splits;
     }
-    g.k_chunk = ceil_div(ceil_div(K, splits), 2) * 2;
-    splits = ceil_div(K, g.k_chunk);
-    g.atomic = (accumulate || splits > 1) ? 1 : 0;
-    g.a_vec = g.b_vec = 1; g.xcd_remap = 0;
-    a.count = count; a.pairs = tiles * splits;
+    p.k_chunk = ceil_div(ceil_div(K, splits), 2) * 2;
+    splits = ceil_div(K, p.k_chunk);
+    p.splits = splits;
+    p.atomic = (accumulate || splits > 1) ? 1 : 0;
+    p.zero_fill = (!accumulate && splits > 1) ? 1 : 0;
+    p.a_vec = p.b_vec = 1;
+    const int pairs = tiles * splits;      // (split, tile) pairs per problem
+    p.grid = count * pairs;
     // What an XCD's 32 CUs work on at one time (`per` pairs of one split of one problem) decides what crosses the fabric into its L2:
     // a row of `per` tiles streams 1 A strip and `per` B strips, a bm x bn block bm + bn.  The block must tile the output.
-    a.bm = a.bn = 0;
 #ifndef GEMM_TN_BLOCKED
 #define GEMM_TN_BLOCKED 1         // (dev: -DGEMM_TN_BLOCKED=0 = rows of tiles, rounds 2-5)
 #endif
     static const int blocked = dev_knob("AMDSPEECH_GEMM_TN_BLOCKED", GEMM_TN_BLOCKED);
-    if (blocked && (a.pairs & 7) == 0) {
-        const int per = a.pairs >> 3;
+    if (blocked && (pairs & 7) == 0) {
+        const int per = pairs >> 3;
         if (per > 1 && tiles % per == 0) {
             int best = 0;
             for (int bm = 1; bm <= per; ++bm) {
-                if (per % bm != 0 || g.tiles_m % bm != 0 || g.tiles_n % (per / bm) != 0) continue;
+                if (per % bm != 0 || p.tiles_m % bm != 0 || p.tiles_n % (per / bm) != 0) continue;
                 if (best == 0 || bm + per / bm < best + per / best) best = bm;
             }
-            if (best > 1) { a.bm = best; a.bn = per / best; }
+            if (best > 1) { p.bm = best; p.bn = per / best; }
         }
     }
+    p.map = (pairs & 7) != 0 ? AMDSPEECH_GEMM_MAP_LINEAR : (p.bm > 0 ? AMDSPEECH_GEMM_MAP_XCD_BLOCKS : AMDSPEECH_GEMM_MAP_XCD);
+    *out = p;
+    return AMDSPEECH_OK;
+}
+static int tn_group_launch(hipStream_t s, const GemmPlan& p, int count, int M, int N, int K, const float* const* A, int lda,
+                           const float* const* B, int ldb, float* const* C, int ldc, float* const* colsum,
+                           const int* gate, int gate_need, unsigned* gate_err) {
+    GemmGroupArgs a;
+    GemmArgs& g = a.g;
+    g.A = nullptr; g.B = nullptr; g.C = nullptr; g.bias = nullptr; g.colsum = nullptr;
+    g.gate = gate; g.gate_need = gate_need; g.gate_limit = 300000000ull; g.gate_err = gate_err;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n;
+    g.k_chunk = p.k_chunk; g.atomic = p.atomic;
+    g.a_vec = g.b_vec = 1; g.xcd_remap = 0;
+    a.count = count; a.pairs = p.grid / count;
+    a.bm = p.bm; a.bn = p.bn;
     for (int i = 0; i < GEMM_GROUP_MAX; ++i) {
         const int j = i < count ? i : 0;
         AS_CHECK_ARG(A[j] && B[j] && C[j] && tn_direct_ok(M, N, K, A[j], lda, B[j], ldb), "gemm group: operand %d does not qualify", j);
         a.A[i] = A[j]; a.B[i] = B[j]; a.C[i] = C[j]; a.colsum[i] = colsum ? colsum[j] : nullptr;
-        if (i < count && !accumulate && splits > 1) {
-            const long n = (long)M * N;
-            hipLaunchKernelGGL(fill_strided_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, C[j], M, N, ldc, 0.0f);
-        }
+    }
+    if (p.zero_fill) {
+        const long n = (long)M * N;
+        for (int i = 0; i < count; ++i)
+            hipLaunchKernelGGL(fill_strided_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, C[i], M, N, ldc, 0.0f);
     }
     // occupancy: an (unused) LDS request caps the workgroups per CU
     // one workgroup = one wave per SIMD per CU: a second streaming wave on a SIMD slows both (8.5 -> 7.3 ms for the two
@@ -194,88 +223,106 @@ int gemm_f32_tn_group(hipStream_t s, int count, int M, int N, int K, const float
         AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_tn_group_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         once.done();
     }
-    hipLaunchKernelGGL(gemm_f32_tn_group_kernel, dim3(count * a.pairs), dim3(256), (size_t)occ_lds, s, a);
+    hipLaunchKernelGGL(gemm_f32_tn_group_kernel, dim3(p.grid), dim3(256), (size_t)occ_lds, s, a);
     AS_CHECK_LAUNCH();
     return AMDSPEECH_OK;
 }
+// Returns AMDSPEECH_OK, or an error when the shape / alignment does not qualify (nothing launched).
+int gemm_f32_tn_group(hipStream_t s, int count, int M, int N, int K, const float* const* A, int lda, const float* const* B,
+                      int ldb, float* const* C, int ldc, float* const* colsum, bool accumulate,
+                      const int* gate, int gate_need, unsigned* gate_err) {
+    AS_CHECK_ARG(count >= 1 && count <= GEMM_GROUP_MAX && M > 0 && N > 0 && K > 0, "gemm group: bad shape");
+    GemmPlan p;
+    if (int rc = gemm_f32_tn_group_plan(count, M, N, K, A[0], lda, B[0], ldb, C[0], accumulate, &p)) return rc;
+    return tn_group_launch(s, p, count, M, N, K, A, lda, B, ldb, C, ldc, colsum, gate, gate_need, gate_err);
+}
 
-int gemm_f32(hipStream_t s, bool transA, bool transB, int M, int N, int K, const float* A, int lda,
-             const float* B, int ldb, float* C, int ldc, const float* bias, bool accumulate, float* colsum,
-             const int* gate, int gate_need, unsigned* gate_err) {
+// The ladder of gemm_f32: the first family whose conditions hold takes the product.
+int gemm_f32_plan(bool transA, bool transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, const float* C,
+                  int ldc, const float* bias, bool accumulate, bool colsum, bool gate, GemmPlan* out) {
     AS_CHECK_ARG(M > 0 && N > 0 && K > 0, "gemm: non-positive shape %d %d %d", M, N, K);
     AS_CHECK_ARG(A && B && C, "gemm: null operand");
     // one short axis against the 32k-frame M axis (the dense layers either side of the stack): gemm_skinny.hip
-    if (!transA && colsum == nullptr && gate == nullptr) {
-        const int took = gemm_skinny(s, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate);
-        if (took != 0) return took < 0 ? took : AMDSPEECH_OK;
-    }
-    if (transA && !transB && bias == nullptr && gate == nullptr) {
-        const int took = gemm_skinny_tn(s, M, N, K, A, lda, B, ldb, C, ldc, accumulate, colsum);
-        if (took != 0) return took < 0 ? took : AMDSPEECH_OK;
-    }
+    if (!transA && !colsum && !gate && gemm_skinny_plan(transB, M, N, K, A, lda, B, ldb, C, ldc, bias, out)) return AMDSPEECH_OK;
+    if (transA && !transB && bias == nullptr && !gate && gemm_skinny_tn_plan(M, N, K, A, lda, B, ldb, accumulate, colsum, out))
+        return AMDSPEECH_OK;
     // both operands row contiguous and tiles that are mostly full: the LDS-free kernel (narrow outputs -- the dense layers'
     // 40- and 80-wide weight gradients -- measured faster through LDS)
     if (transA && !transB && bias == nullptr && M >= 96 && N >= 96 && tn_direct_ok(M, N, K, A, lda, B, ldb))
-        return gemm_f32_tn_group(s, 1, M, N, K, &A, lda, &B, ldb, &C, ldc, colsum ? &colsum : nullptr, accumulate, gate, gate_need, gate_err);
+        return gemm_f32_tn_group_plan(1, M, N, K, A, lda, B, ldb, C, accumulate, out);
+    GemmPlan p = plan_blank();
+    p.tiles_m = ceil_div(M, BM); p.tiles_n = ceil_div(N, BN);
+    const int tiles = p.tiles_m * p.tiles_n;
+    int splits = 1;
     // A k-contiguous (no transA), K a multiple of 64, 16-byte aligned rows, output at least a tile wide, no fused column sums:
     // the LDS-free kernel for the dZ_0 / dX products (transB) and the x.W products
     static const bool kc_direct = runtime_switch("AMDSPEECH_GEMM_KC_DIRECT", 1) != 0;
     // (short K: the pipeline fill per tile is not amortised -- K = 1024 x.W products measured 3 % faster through LDS)
     static const int kc_min_k = dev_knob("AMDSPEECH_KC_MIN_K", 2048);
-    if (kc_direct && !transA && colsum == nullptr && gate == nullptr && K % 64 == 0 && K >= kc_min_k && M >= 128 && N >= 96 &&
+    if (kc_direct && !transA && !colsum && !gate && K % 64 == 0 && K >= kc_min_k && M >= 128 && N >= 96 &&
         (uintptr_t)A % 16 == 0 && lda % 4 == 0 && (uintptr_t)B % 16 == 0 && ldb % 4 == 0 &&
         (size_t)M * lda * 4 < (1ull << 32) && (size_t)(transB ? N : K + 64) * ldb * 4 < (1ull << 32)) {
-        GemmArgs g;
-        g.A = A; g.B = B; g.C = C; g.bias = bias; g.colsum = nullptr; g.gate = nullptr; g.gate_err = nullptr; g.gate_need = 0; g.gate_limit = 0;
-        g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-        g.tiles_m = ceil_div(M, BM); g.tiles_n = ceil_div(N, BN);
-        const int tiles = g.tiles_m * g.tiles_n;
-        int splits = 1;
+        p.family = AMDSPEECH_GEMM_KC_DIRECT; p.variant = transB ? 1 : 0;
         if (tiles < 192) {
             splits = ceil_div(256, tiles);
             if (splits > K / 256) splits = K / 256 > 0 ? K / 256 : 1;
         }
-        g.k_chunk = ceil_div(ceil_div(K, splits), 64) * 64;
-        splits = ceil_div(K, g.k_chunk);
-        g.atomic = (accumulate || splits > 1) ? 1 : 0;
-        g.a_vec = g.b_vec = 1; g.xcd_remap = 1;
-        if (!accumulate && splits > 1) {
-            const long n = (long)M * N;
-            hipLaunchKernelGGL(fill_strided_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, C, M, N, ldc, 0.0f);
+        p.k_chunk = ceil_div(ceil_div(K, splits), 64) * 64;
+        p.a_vec = p.b_vec = 1;
+        // (the kernel always renumbers the workgroups per XCD; the band walk needs whole blocks of 4 column tiles)
+        p.map = (p.tiles_n & 3) == 0 ? AMDSPEECH_GEMM_MAP_KC_BAND : AMDSPEECH_GEMM_MAP_XCD;
+    } else {
+        p.family = AMDSPEECH_GEMM_LDS; p.variant = (transA ? 0 : 2) + (transB ? 1 : 0);      // A_KC * 2 + B_KC
+        // split K until there are >= ~2 workgroups per CU, keeping >= 16 K-tiles per split
+        static const int target_wgs = dev_knob("AMDSPEECH_GEMM_WGS", 512);
+        if (tiles < target_wgs) {
+            splits = ceil_div(target_wgs, tiles);
+            const int max_splits = K / (BK * 16) > 0 ? K / (BK * 16) : 1;
+            if (splits > max_splits) splits = max_splits;
         }
-        if (transB) hipLaunchKernelGGL(gemm_f32_kc_direct_kernel<true>, dim3(tiles * splits), dim3(256), 0, s, g);
-        else hipLaunchKernelGGL(gemm_f32_kc_direct_kernel<false>, dim3(tiles * splits), dim3(256), 0, s, g);
-        AS_CHECK_LAUNCH();
-        return AMDSPEECH_OK;
+        p.k_chunk = ceil_div(ceil_div(K, splits), BK) * BK;
+        p.a_vec = ((uintptr_t)A % 16 == 0) && (lda % 4 == 0);
+        p.b_vec = ((uintptr_t)B % 16 == 0) && (ldb % 4 == 0);
     }
+    splits = ceil_div(K, p.k_chunk);
+    p.splits = splits;
+    p.atomic = (accumulate || splits > 1) ? 1 : 0;
+    p.zero_fill = (!accumulate && splits > 1) ? 1 : 0;
+    p.grid = tiles * splits;
+    if (p.family == AMDSPEECH_GEMM_LDS) p.map = splits > 1 ? AMDSPEECH_GEMM_MAP_XCD : AMDSPEECH_GEMM_MAP_LINEAR;
+    *out = p;
+    return AMDSPEECH_OK;
+}
+
+int gemm_f32_launch(hipStream_t s, const GemmPlan& p, bool transA, bool transB, int M, int N, int K, const float* A, int lda,
+                    const float* B, int ldb, float* C, int ldc, const float* bias, bool accumulate, float* colsum,
+                    const int* gate, int gate_need, unsigned* gate_err) {
+    if (p.family == AMDSPEECH_GEMM_SKINNY_N || p.family == AMDSPEECH_GEMM_SKINNY_K)
+        return gemm_skinny_launch(s, p, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate);
+    if (p.family == AMDSPEECH_GEMM_SKINNY_TN) return gemm_skinny_tn_launch(s, p, M, N, K, A, lda, B, ldb, C, ldc, accumulate, colsum);
+    if (p.family == AMDSPEECH_GEMM_TN_DIRECT)
+        return tn_group_launch(s, p, 1, M, N, K, &A, lda, &B, ldb, &C, ldc, colsum ? &colsum : nullptr, gate, gate_need, gate_err);
     GemmArgs g;
     g.A = A; g.B = B; g.C = C; g.bias = bias; g.colsum = colsum;
     g.gate = gate; g.gate_need = gate_need; g.gate_limit = 300000000ull;    // 3 s
     g.gate_err = gate_err;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    const int tiles_m = ceil_div(M, BM), tiles_n = ceil_div(N, BN);
-    g.tiles_n = tiles_n;
-    const int tiles = tiles_m * tiles_n;
-    // split K until there are >= ~2 workgroups per CU, keeping >= 16 K-tiles per split
-    int splits = 1;
-    static const int target_wgs = dev_knob("AMDSPEECH_GEMM_WGS", 512);
-    if (tiles < target_wgs) {
-        splits = ceil_div(target_wgs, tiles);
-        const int max_splits = K / (BK * 16) > 0 ? K / (BK * 16) : 1;
-        if (splits > max_splits) splits = max_splits;
-    }
-    g.k_chunk = ceil_div(ceil_div(K, splits), BK) * BK;
-    splits = ceil_div(K, g.k_chunk);
-    g.atomic = (accumulate || splits > 1) ? 1 : 0;
-    g.a_vec = ((uintptr_t)A % 16 == 0) && (lda % 4 == 0);
-    g.b_vec = ((uintptr_t)B % 16 == 0) && (ldb % 4 == 0);
-    if (!accumulate && splits > 1) {
+    g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n;
+    g.k_chunk = p.k_chunk; g.atomic = p.atomic; g.a_vec = p.a_vec; g.b_vec = p.b_vec;
+    if (p.zero_fill) {
         const long n = (long)M * N;
         hipLaunchKernelGGL(fill_strided_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, C, M, N, ldc, 0.0f);
     }
-    g.tiles_m = tiles_m;
-    g.xcd_remap = splits > 1 ? 1 : 0;
-    dim3 grid(tiles * splits), block(256);
+    const dim3 grid(p.grid), block(256);
+    if (p.family == AMDSPEECH_GEMM_KC_DIRECT) {
+        g.colsum = nullptr; g.gate = nullptr; g.gate_err = nullptr; g.gate_need = 0; g.gate_limit = 0;
+        g.xcd_remap = 1;
+        if (transB) hipLaunchKernelGGL(gemm_f32_kc_direct_kernel<true>, grid, block, 0, s, g);
+        else hipLaunchKernelGGL(gemm_f32_kc_direct_kernel<false>, grid, block, 0, s, g);
+        AS_CHECK_LAUNCH();
+        return AMDSPEECH_OK;
+    }
+    g.xcd_remap = p.splits > 1 ? 1 : 0;
     constexpr size_t lds = (size_t)2 * 2 * BK * LDS_LD * sizeof(float);
     static unsigned long long lds_seen = 0;
     if (DeviceOnce once{&lds_seen}) {
@@ -292,6 +339,15 @@ int gemm_f32(hipStream_t s, bool transA, bool transB, int M, int N, int K, const
     else hipLaunchKernelGGL((gemm_f32_kernel<false, true>), grid, block, lds, s, g);
     AS_CHECK_LAUNCH();
     return AMDSPEECH_OK;
+}
+
+int gemm_f32(hipStream_t s, bool transA, bool transB, int M, int N, int K, const float* A, int lda,
+             const float* B, int ldb, float* C, int ldc, const float* bias, bool accumulate, float* colsum,
+             const int* gate, int gate_need, unsigned* gate_err) {
+    GemmPlan p;
+    if (int rc = gemm_f32_plan(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, colsum != nullptr, gate != nullptr, &p))
+        return rc;
+    return gemm_f32_launch(s, p, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, colsum, gate, gate_need, gate_err);
 }
 
 // out[c] += sum_r x[r*ld + c]   (bias gradients).  One block per 64 columns,
@@ -371,3 +427,42 @@ int colsum_accumulate(hipStream_t s, const float* x, int rows, int cols, int ld,
 }
 
 }  // namespace amdspeech
+
+using namespace amdspeech;
+
+// The plan of one product as the entry points above make it (amdspeech.h); nothing is launched, no pointer is dereferenced.
+extern "C" int amdspeech_gemm_plan(int precision, int transA, int transB, int M, int N, int K, const void* A, int lda, const void* B,
+                                   int ldb, const void* C, int ldc, const void* bias, int accumulate, int colsum, int count,
+                                   amdspeech_gemm_plan_info* out) {
+    AS_CHECK_ARG(out != nullptr, "gemm_plan: null output");
+    AS_CHECK_ARG(precision >= 0 && precision <= 2 && count >= 1, "gemm_plan: precision %d / count %d out of range", precision, count);
+    const float* a = static_cast<const float*>(A);
+    const float* b = static_cast<const float*>(B);
+    const float* c = static_cast<const float*>(C);
+    if (count >= 2) {
+        AS_CHECK_ARG(precision == 0 && transA != 0 && transB == 0 && bias == nullptr, "gemm_plan: the grouped entry is C += A^T . B in f32, no bias");
+        return gemm_f32_tn_group_plan(count, M, N, K, a, lda, b, ldb, c, accumulate != 0, out);
+    }
+    if (precision == 0)
+        return gemm_f32_plan(transA != 0, transB != 0, M, N, K, a, lda, b, ldb, c, ldc, static_cast<const float*>(bias), accumulate != 0,
+                             colsum != 0, false, out);
+    AS_CHECK_ARG(colsum == 0, "gemm_plan: no fused column sums in reduced precision");
+    return gemm_bf_plan(precision == 2, transA != 0, transB != 0, M, N, K, a, lda, b, ldb, c, ldc, static_cast<const float*>(bias),
+                        accumulate != 0, out);
+}
+
+// Exposed for tests / bench: the grouped weight-gradient launch of the LSTM backward pass, C_i (+)= A_i^T . B_i, and the bias-gradient
+// column sums of the reduced-precision path.
+extern "C" int amdspeech_gemm_f32_tn_group(void* stream, int count, int M, int N, int K, const float* const* A, int lda,
+                                           const float* const* B, int ldb, float* const* C, int ldc, float* const* colsum,
+                                           int accumulate) {
+    AS_CHECK_ARG(count >= 1 && count <= GEMM_GROUP_MAX && M > 0 && N > 0 && K > 0, "gemm group: bad shape");
+    AS_CHECK_ARG(A && B && C, "gemm group: null operand array");
+    for (int i = 0; i < count; ++i)
+        AS_CHECK_ARG(A[i] && B[i] && C[i] && gemm_f32_tn_group_ok(M, N, K, A[i], lda, B[i], ldb), "gemm group: operand %d does not qualify", i);
+    return gemm_f32_tn_group(static_cast<hipStream_t>(stream), count, M, N, K, A, lda, B, ldb, C, ldc, colsum, accumulate != 0);
+}
+
+extern "C" int amdspeech_colsum_accumulate(void* stream, const float* x, int rows, int cols, int ld, float* out) {
+    return colsum_accumulate(static_cast<hipStream_t>(stream), x, rows, cols, ld, out);
+}

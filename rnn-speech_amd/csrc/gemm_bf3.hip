@@ -19,6 +19,7 @@
 // 16-byte LDS word per plane.  Register-staged one K step ahead of the MFMAs; one 32 KiB LDS stage, three workgroups per CU.
 #include "common.h"
 #include <stdlib.h>
+#include <string.h>
 
 namespace amdspeech {
 
@@ -235,10 +236,9 @@ __global__ void bf3_fill_kernel(float* C, int M, int N, int ldc, float v) {
 
 }  // namespace
 
-// Same contract as gemm_f32 (common.h) without the fused column sum / gate: transX != 0 means the operand is stored
-// transposed (A as [K,M], B as [N,K]).
-static int gemm_bf_any(hipStream_t s, bool single, bool transA, bool transB, int M, int N, int K, const float* A, int lda, const float* B,
-                       int ldb, float* C, int ldc, const float* bias, bool accumulate) {
+// The plan of the two reduced-precision products (common.h: GemmPlan): this file's kernel, or the exact-f32 ladder's choice.
+int gemm_bf_plan(bool single, bool transA, bool transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
+                 const float* C, int ldc, const float* bias, bool accumulate, GemmPlan* out) {
     AS_CHECK_ARG(A && B && C && M > 0 && N > 0 && K > 0, "gemm_bf3: bad arguments");
     AS_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, "gemm_bf3: operands must be 16-byte aligned");
     {
@@ -247,14 +247,14 @@ static int gemm_bf_any(hipStream_t s, bool single, bool transA, bool transB, int
         const size_t a_bytes = (a_kc ? (size_t)M * lda : (size_t)K * lda) * 4, b_bytes = (b_kc ? (size_t)N * ldb : (size_t)K * ldb) * 4;
         const bool ok = a_bytes < (1ull << 32) && b_bytes < (1ull << 32) && (!a_kc || (K % TK == 0 && lda % 4 == 0)) &&
                         (!b_kc || (K % TK == 0 && ldb % 4 == 0));
-        if (!ok) return gemm_f32(s, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate);
+        if (!ok) return gemm_f32_plan(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, false, false, out);
     }
-    Bf3Args g;
-    g.A = A; g.B = B; g.C = C; g.bias = bias;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    const int tiles_m = ceil_div(M, TM);
-    g.tiles_n = ceil_div(N, TN);
-    const int tiles = tiles_m * g.tiles_n;
+    GemmPlan p;
+    memset(&p, 0, sizeof(p));
+    p.family = AMDSPEECH_GEMM_BF3; p.variant = (single ? 4 : 0) + (transA ? 0 : 2) + (transB ? 1 : 0);
+    p.tiles_m = ceil_div(M, TM); p.tiles_n = ceil_div(N, TN);
+    p.col_slices = 1; p.a_vec = p.b_vec = 1;
+    const int tiles = p.tiles_m * p.tiles_n;
     // split K until every CU has its three workgroups (they overlap each other's phases), as long as a split keeps >= 16 K steps
     int splits = 1;
     if (tiles < 768) {
@@ -263,10 +263,30 @@ static int gemm_bf_any(hipStream_t s, bool single, bool transA, bool transB, int
         if (splits > max_splits) splits = max_splits;
         if (splits < 1) splits = 1;
     }
-    g.k_chunk = ceil_div(ceil_div(K, splits), TK) * TK;
-    splits = ceil_div(K, g.k_chunk);
-    g.atomic = (accumulate || splits > 1) ? 1 : 0;
-    if (!accumulate && splits > 1) {
+    p.k_chunk = ceil_div(ceil_div(K, splits), TK) * TK;
+    splits = ceil_div(K, p.k_chunk);
+    p.splits = splits;
+    p.atomic = (accumulate || splits > 1) ? 1 : 0;
+    p.zero_fill = (!accumulate && splits > 1) ? 1 : 0;
+    p.grid = tiles * splits;
+    *out = p;
+    return AMDSPEECH_OK;
+}
+
+// Same contract as gemm_f32 (common.h) without the fused column sum / gate: transX != 0 means the operand is stored
+// transposed (A as [K,M], B as [N,K]).
+static int gemm_bf_any(hipStream_t s, bool single, bool transA, bool transB, int M, int N, int K, const float* A, int lda, const float* B,
+                       int ldb, float* C, int ldc, const float* bias, bool accumulate) {
+    GemmPlan p;
+    if (int rc = gemm_bf_plan(single, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, &p)) return rc;
+    if (p.family != AMDSPEECH_GEMM_BF3) return gemm_f32_launch(s, p, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate);
+    Bf3Args g;
+    g.A = A; g.B = B; g.C = C; g.bias = bias;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    g.tiles_n = p.tiles_n;
+    g.k_chunk = p.k_chunk;
+    g.atomic = p.atomic;
+    if (p.zero_fill) {
         const long n = (long)M * N;
         hipLaunchKernelGGL(bf3_fill_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, C, M, N, ldc, 0.0f);
     }
@@ -283,7 +303,7 @@ static int gemm_bf_any(hipStream_t s, bool single, bool transA, bool transB, int
         AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf3_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
         once.done();
     }
-    dim3 grid(tiles * splits), block(256);
+    dim3 grid(p.grid), block(256);
     static const size_t lds_req = (size_t)dev_knob("AMDSPEECH_BF3_LDS", (int)(lds / 1024)) * 1024;      // dev: occupancy probe
     // A "KC" = k contiguous = NOT transposed storage [M,K]; B "KC" = stored [N,K] = transposed.
     if (single) {      // (same 32 KiB request: the lo planes stay unused, the occupancy is what the kernel was tuned at)

@@ -19,6 +19,7 @@
 // The k index of MFMA j inside a 16-k group is 4 (lane >> 4) + j for both operands (any permutation of k is a valid product), which
 // is what makes a lane's b128 the operand of four consecutive MFMAs.
 #include "common.h"
+#include <string.h>
 
 namespace amdspeech {
 
@@ -474,37 +475,56 @@ __global__ void skinny_zero_kernel(float* C, int rows, int cols, int ldc) {
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// C[M,N] (+)= A^T . B with A [K,M], B [K,N] (+ colsum[N] += column sums of B).  1 = taken, 0 = not this shape, < 0 = error.
-int gemm_skinny_tn(hipStream_t st, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                   bool accumulate, float* colsum) {
+// C[M,N] (+)= A^T . B with A [K,M], B [K,N] (+ colsum[N] += column sums of B).  The plan: true = this kernel takes the product
+// (family, variant = FULL * 8 + RT, splits = row chunks of k_chunk rows, tiles_n = 64-column slices), false = not this shape.
+bool gemm_skinny_tn_plan(int M, int N, int K, const float* A, int lda, const float* B, int ldb, bool accumulate, bool colsum, GemmPlan* out) {
     static const bool enabled = dev_knob("AMDSPEECH_GEMM_SKINNY", 1) != 0;      // (dev A/B: the general 128x128 kernels instead)
-    if (!enabled || K < 4096) return 0;
+    if (!enabled || K < 4096) return false;
     const bool small_is_a = M <= N;
     const int s = small_is_a ? M : N, wide = small_is_a ? N : M;
-    if (s > 124 || wide < 128) return 0;
-    if ((s | wide | lda | ldb) & 3) return 0;
-    if (!aligned16(A) || !aligned16(B)) return 0;
+    if (s > 124 || wide < 128) return false;
+    if ((s | wide | lda | ldb) & 3) return false;
+    if (!aligned16(A) || !aligned16(B)) return false;
     const size_t lim = (size_t)SK_OOB;
-    if (((size_t)(K - 1) * lda + M) * 4 >= lim || ((size_t)(K - 1) * ldb + N) * 4 >= lim) return 0;
+    if (((size_t)(K - 1) * lda + M) * 4 >= lim || ((size_t)(K - 1) * ldb + N) * 4 >= lim) return false;
+    // tiles of the small operand (+ the ones column when the wide operand's column sums are wanted: the GEMM's B is the operand
+    // whose columns are summed): FULL fragments of 64, then a remainder of RT x 16
+    const int s_eff = s + ((colsum && small_is_a) ? 1 : 0);
+    const int full = s_eff / 64, rt = ceil_div(s_eff - 64 * full, 16);
+    if (full > 1 || rt > 4 || full * 8 + rt == 0) return false;
+    GemmPlan p;
+    memset(&p, 0, sizeof(p));
+    p.family = AMDSPEECH_GEMM_SKINNY_TN; p.variant = full * 8 + rt;
+    p.tiles_m = 1; p.tiles_n = ceil_div(wide, 64); p.col_slices = p.tiles_n;
+    int nchunks = ceil_div(256, p.tiles_n);
+    nchunks = ceil_div(nchunks, 8) * 8;
+    p.k_chunk = ceil_div(ceil_div(K, nchunks), 32) * 32;
+    p.splits = nchunks;                              // (workgroups whose chunk starts past K return at once)
+    p.atomic = 1; p.zero_fill = accumulate ? 0 : 1;
+    p.grid = p.tiles_n * nchunks;
+    p.map = AMDSPEECH_GEMM_MAP_XCD;                  // the slices of one row chunk share an XCD
+    p.a_vec = p.b_vec = 1;
+    *out = p;
+    return true;
+}
+
+int gemm_skinny_tn_launch(hipStream_t st, const GemmPlan& p, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
+                          float* C, int ldc, bool accumulate, float* colsum) {
+    const bool small_is_a = M <= N;
     SkinnyTnArgs g;
     g.S = small_is_a ? A : B; g.lds = small_is_a ? lda : ldb;
     g.W = small_is_a ? B : A; g.ldw = small_is_a ? ldb : lda;
-    g.C = C; g.ldc = ldc; g.colsum = colsum; g.K = K; g.s = s; g.wide = wide;
+    g.C = C; g.ldc = ldc; g.colsum = colsum; g.K = K; g.s = small_is_a ? M : N; g.wide = small_is_a ? N : M;
     g.small_is_a = small_is_a ? 1 : 0;
     g.colsum_small = small_is_a ? 0 : 1;             // (the GEMM's B is the operand whose columns are summed)
-    g.nslices = ceil_div(wide, 64);
-    int nchunks = ceil_div(256, g.nslices);
-    nchunks = ceil_div(nchunks, 8) * 8;
-    g.chunk = ceil_div(ceil_div(K, nchunks), 32) * 32;
-    if (!accumulate) {
+    g.nslices = p.tiles_n;
+    g.chunk = p.k_chunk;
+    if (p.zero_fill) {
         const long n = (long)M * N;
         hipLaunchKernelGGL(skinny_zero_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, C, M, N, ldc);
     }
-    const dim3 grid(g.nslices * nchunks), block(512);
-    // tiles of the small operand (+ the ones column when the wide operand's column sums are wanted): FULL fragments of 64, then
-    // a remainder of RT x 16
-    const int s_eff = s + ((colsum != nullptr && !g.colsum_small) ? 1 : 0);
-    const int full = s_eff / 64, rt = ceil_div(s_eff - 64 * full, 16);
+    const dim3 grid(p.grid), block(512);
+    const int full = p.variant / 8, rt = p.variant % 8;
     const size_t lds = (size_t)2 * (4 * full + rt) * 4 * 64 * 16;          // two waves' accumulators (>= red + red_cs)
 #define SK_TN(F, R)                                                                                                          \
     do {                                                                                                                      \
@@ -516,7 +536,7 @@ int gemm_skinny_tn(hipStream_t st, int M, int N, int K, const float* A, int lda,
         }                                                                                                                     \
         hipLaunchKernelGGL((gemm_skinny_tn_kernel<F, R>), grid, block, lds, st, g);                                           \
     } while (0)
-    switch (full * 8 + rt) {
+    switch (p.variant) {
         case 1: SK_TN(0, 1); break;
         case 2: SK_TN(0, 2); break;
         case 3: SK_TN(0, 3); break;
@@ -526,53 +546,75 @@ int gemm_skinny_tn(hipStream_t st, int M, int N, int K, const float* A, int lda,
         case 10: SK_TN(1, 2); break;
         case 11: SK_TN(1, 3); break;
         case 12: SK_TN(1, 4); break;
-        default: return 0;
+        default: AS_CHECK_ARG(false, "gemm_skinny_tn: no kernel for variant %d", p.variant);
     }
 #undef SK_TN
     AS_CHECK_LAUNCH();
-    return 1;
+    return AMDSPEECH_OK;
 }
 
-// Returns 1 when one of the two kernels took the product, 0 when the shape is not theirs (the caller goes on to the general
-// kernels), a negative AMDSPEECH_E* on a launch error.
-int gemm_skinny(hipStream_t s, bool transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
-                const float* bias, bool accumulate) {
+// The two kernels for a short N or K against a long M.  The plan: true = one of them takes the product (skinny-n: variant = NT;
+// skinny-k: variant = KT * 2 + transB, col_slices = 1 or 2; tiles_m = row blocks), false = the shape is not theirs (the caller
+// goes on to the general kernels).
+bool gemm_skinny_plan(bool transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, const float* C, int ldc,
+                      const float* bias, GemmPlan* out) {
     static const bool enabled = dev_knob("AMDSPEECH_GEMM_SKINNY", 1) != 0;      // (dev A/B: the general 128x128 kernels instead)
-    if (!enabled || M < 256) return 0;
-    if ((N | K | lda | ldb | ldc) & 3) return 0;
-    if (!aligned16(A) || !aligned16(B) || !aligned16(C) || (bias != nullptr && !aligned16(bias))) return 0;
+    if (!enabled || M < 256) return false;
+    if ((N | K | lda | ldb | ldc) & 3) return false;
+    if (!aligned16(A) || !aligned16(B) || !aligned16(C) || (bias != nullptr && !aligned16(bias))) return false;
     const size_t lim = (size_t)SK_OOB;
-    if (((size_t)(M - 1) * lda + K) * 4 >= lim) return 0;
+    if (((size_t)(M - 1) * lda + K) * 4 >= lim) return false;
     // (the OUTPUT too: its store offsets are 32-bit with SK_OOB as the "outside" mark -- a wide or strided C of 2 GiB and more
     //  would have its stores dropped or wrapped instead of going to the general kernel)
-    if (((size_t)(M - 1) * ldc + N) * 4 >= lim) return 0;
-    SkinnyArgs g;
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.accumulate = accumulate ? 1 : 0;
+    if (((size_t)(M - 1) * ldc + N) * 4 >= lim) return false;
+    GemmPlan p;
+    memset(&p, 0, sizeof(p));
+    p.splits = 1; p.col_slices = 1; p.k_chunk = K; p.a_vec = p.b_vec = 1; p.tiles_n = 1;
     if (K <= 80 && N >= 64) {
         const size_t be = transB ? (size_t)(N - 1) * ldb + K : (size_t)(K - 1) * ldb + N;
-        if (be * 4 >= lim) return 0;
+        if (be * 4 >= lim) return false;
         const int row_blocks = ceil_div(M, 128);
         const int kt = ceil_div(K, 16);
         // (two column slices measured faster for the 40-long reduction of the input layer, slower for the 80-long one: 27.5 vs 29.5
         // and 39.5 vs 33.6 us at 32032 x 512)
-        const dim3 grid(row_blocks, (row_blocks < 512 && N >= 256 && kt <= 3) ? 2 : 1), block(256);
+        p.family = AMDSPEECH_GEMM_SKINNY_K; p.variant = (kt <= 3 ? 3 : 5) * 2 + (transB ? 1 : 0);
+        p.tiles_m = row_blocks;
+        p.col_slices = (row_blocks < 512 && N >= 256 && kt <= 3) ? 2 : 1;
+        p.grid = row_blocks * p.col_slices;
+        *out = p;
+        return true;
+    }
+    if (!transB && N <= 96 && K >= 64) {
+        if (((size_t)(K - 1) * ldb + N) * 4 >= lim) return false;
+        const int nt = ceil_div(N, 16);
+        p.family = AMDSPEECH_GEMM_SKINNY_N; p.variant = nt < 6 ? nt : 6;
+        p.tiles_m = ceil_div(M, 64);
+        p.grid = p.tiles_m;
+        *out = p;
+        return true;
+    }
+    return false;
+}
+
+int gemm_skinny_launch(hipStream_t s, const GemmPlan& p, bool transB, int M, int N, int K, const float* A, int lda, const float* B,
+                       int ldb, float* C, int ldc, const float* bias, bool accumulate) {
+    SkinnyArgs g;
+    g.A = A; g.B = B; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    g.accumulate = accumulate ? 1 : 0;
+    const dim3 block(256);
+    if (p.family == AMDSPEECH_GEMM_SKINNY_K) {
+        const dim3 grid(p.tiles_m, p.col_slices);
 #define SK_K(KT)                                                                                           \
         do {                                                                                               \
             if (transB) hipLaunchKernelGGL((gemm_skinny_k_kernel<KT, true>), grid, block, 0, s, g);        \
             else hipLaunchKernelGGL((gemm_skinny_k_kernel<KT, false>), grid, block, 0, s, g);              \
         } while (0)
-        if (kt <= 3) SK_K(3);
+        if (p.variant / 2 == 3) SK_K(3);
         else SK_K(5);
 #undef SK_K
-        AS_CHECK_LAUNCH();
-        return 1;
-    }
-    if (!transB && N <= 96 && K >= 64) {
-        if (((size_t)(K - 1) * ldb + N) * 4 >= lim) return 0;
-        const dim3 grid(ceil_div(M, 64)), block(256);
-        const int nt = ceil_div(N, 16);
-        switch (nt) {
+    } else {
+        const dim3 grid(p.grid);
+        switch (p.variant) {
             case 1: hipLaunchKernelGGL(gemm_skinny_n_kernel<1>, grid, block, 0, s, g); break;
             case 2: hipLaunchKernelGGL(gemm_skinny_n_kernel<2>, grid, block, 0, s, g); break;
             case 3: hipLaunchKernelGGL(gemm_skinny_n_kernel<3>, grid, block, 0, s, g); break;
@@ -580,10 +622,9 @@ int gemm_skinny(hipStream_t s, bool transB, int M, int N, int K, const float* A,
             case 5: hipLaunchKernelGGL(gemm_skinny_n_kernel<5>, grid, block, 0, s, g); break;
             default: hipLaunchKernelGGL(gemm_skinny_n_kernel<6>, grid, block, 0, s, g); break;
         }
-        AS_CHECK_LAUNCH();
-        return 1;
     }
-    return 0;
+    AS_CHECK_LAUNCH();
+    return AMDSPEECH_OK;
 }
 
 }  // namespace amdspeech

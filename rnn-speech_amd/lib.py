@@ -42,6 +42,14 @@ class CtcPlanInfo(C.Structure):      # amdspeech_ctc_plan_info (include/amdspeec
     _fields_ = [(n, C.c_int) for n in ("kernel", "threads", "rmax", "smax")]
 
 
+class GemmPlanInfo(C.Structure):     # amdspeech_gemm_plan_info (include/amdspeech.h): the kernel and launch geometry of one product, read-only
+    _fields_ = [(n, C.c_int) for n in ("family", "variant", "splits", "k_chunk", "atomic", "zero_fill", "grid", "tiles_m", "tiles_n", "map",
+                                       "bm", "bn", "col_slices", "a_vec", "b_vec")]
+
+
+GEMM_FAMILIES = ("skinny_n", "skinny_k", "skinny_tn", "tn_direct", "kc_direct", "lds", "bf3")      # AMDSPEECH_GEMM_* (include/amdspeech.h)
+GEMM_MAP_LINEAR, GEMM_MAP_XCD, GEMM_MAP_XCD_BLOCKS, GEMM_MAP_KC_BAND = range(4)      # AMDSPEECH_GEMM_MAP_*
+GEMM_GROUP_MAX = 10                                                                 # AMDSPEECH_GEMM_GROUP_MAX
 CTC_KERNELS = ("wave", "shift", "pair", "edge")      # AMDSPEECH_CTC_KERNEL_* (include/amdspeech.h)
 LSTM_PATHS = ("flow", "big1", "big", "hoist", "diag", "diag_bf3")      # AMDSPEECH_LSTM_PATH_* (include/amdspeech.h)
 LSTM_ARMED, LSTM_ARM_NEXT, LSTM_SAME_WS, LSTM_PER_DIAGONAL, LSTM_INJECT_TIMEOUT = 1, 2, 4, 8, 16      # amdspeech_lstm_desc.flags (include/amdspeech.h)
@@ -67,6 +75,9 @@ PROTOTYPES = {
     "amdspeech_gemm_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
     "amdspeech_gemm_bf16x3": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
     "amdspeech_gemm_bf16": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
+    "amdspeech_gemm_plan": (_I, [_I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, C.POINTER(GemmPlanInfo)]),
+    "amdspeech_gemm_f32_tn_group": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I]),
+    "amdspeech_colsum_accumulate": (_I, [_P, _P, _I, _I, _I, _P]),
     "amdspeech_gemm_bf16_packed_scratch_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
     "amdspeech_gemm_bf16_packed": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _SZ]),
     "amdspeech_batchnorm_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F]),

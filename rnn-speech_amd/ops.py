@@ -79,6 +79,67 @@ def gemm_bf16(a, b, **kw):
     return gemm_bf16x3(a, b, single=True, **kw)
 
 
+def _plan_operand(x):
+    """(address, rows, cols, ld) of an operand of gemm_plan: a tensor, or (rows, cols), (rows, cols, ld), (rows, cols, ld, address) --
+    the address is only looked at for null and alignment (default: a nominal 16-byte aligned one)."""
+    if torch.is_tensor(x):
+        return x.data_ptr(), x.shape[0], x.shape[1], x.stride(0)
+    x = tuple(int(v) for v in x)
+    rows, cols = x[:2]
+    return (x[3] if len(x) > 3 else 4096), rows, cols, (x[2] if len(x) > 2 else cols)
+
+
+def gemm_plan(a, b, trans_a=False, trans_b=False, bias=None, out=None, accumulate=False, colsum=False, count=1, precision=0):
+    """The kernel gemm() (precision 0), gemm_bf16x3() (1) or gemm_bf16() (2) takes for a product and its launch geometry
+    (amdspeech.h: amdspeech_gemm_plan), as a dict of ints with "family" as a name (lib.GEMM_FAMILIES).  Nothing is launched.
+    a, b, out: tensors, or shapes as _plan_operand takes them (out=None: a contiguous, aligned result); bias: a tensor, an
+    address, True (an aligned one) or None; colsum: with linear_bwd's fused column sums; count >= 2: gemm_tn_group()."""
+    pa, ar, ac, lda = _plan_operand(a)
+    pb, br, bc, ldb = _plan_operand(b)
+    M, K = (ac, ar) if trans_a else (ar, ac)
+    K2, N = (bc, br) if trans_b else (br, bc)
+    assert K == K2, ((ar, ac), (br, bc))
+    pc, _, _, ldc = _plan_operand(out if out is not None else (M, N))
+    pbias = 0 if bias is None or bias is False else (4096 if bias is True else (bias.data_ptr() if torch.is_tensor(bias) else int(bias)))
+    info = _l.GemmPlanInfo()
+    _l.check(_l.load().amdspeech_gemm_plan(int(precision), int(trans_a), int(trans_b), M, N, K, C.c_void_p(pa), lda, C.c_void_p(pb), ldb,
+                                           C.c_void_p(pc), ldc, C.c_void_p(pbias), int(accumulate), int(colsum), int(count), C.byref(info)),
+             "gemm_plan")
+    plan = {name: int(getattr(info, name)) for name, _ in _l.GemmPlanInfo._fields_}
+    plan["family"] = _l.GEMM_FAMILIES[plan["family"]]
+    return plan
+
+
+def gemm_tn_group(a, b, out, colsum=None, accumulate=False):
+    """out[i] (+)= a[i]^T @ b[i] for up to lib.GEMM_GROUP_MAX problems of one shape in ONE launch (amdspeech_gemm_f32_tn_group: the
+    weight gradients of an LSTM backward pass); a[i] [K,M], b[i] [K,N], out[i] [M,N] with contiguous rows.  colsum: None, or a list with
+    a [N] tensor (+= column sums of b[i]) or None per problem.  A shape the kernel does not take raises."""
+    count = len(a)
+    assert count == len(b) == len(out) and (colsum is None or len(colsum) == count)
+    _chk_f32_rows(*a, *b, *out)
+    K, M = a[0].shape
+    N = b[0].shape[1]
+    for x, y, z in zip(a, b, out):
+        assert tuple(x.shape) == (K, M) and tuple(y.shape) == (K, N) and tuple(z.shape) == (M, N)
+        assert x.stride(0) == a[0].stride(0) and y.stride(0) == b[0].stride(0) and z.stride(0) == out[0].stride(0)
+    if colsum is not None:
+        _chk_f32(*colsum)
+    arr = lambda ts: (C.c_void_p * count)(*[t.data_ptr() if t is not None else None for t in ts])
+    _l.check(_l.load().amdspeech_gemm_f32_tn_group(_stream(), count, M, N, K, arr(a), a[0].stride(0), arr(b), b[0].stride(0), arr(out),
+                                                   out[0].stride(0), arr(colsum) if colsum is not None else None, int(accumulate)),
+             "gemm_f32_tn_group")
+    return out
+
+
+def colsum_accumulate(x, out):
+    """out[c] += sum_r x[r, c] (amdspeech_colsum_accumulate); x [rows, cols] with contiguous rows."""
+    _chk_f32_rows(x)
+    _chk_f32(out)
+    assert out.numel() == x.shape[1]
+    _l.check(_l.load().amdspeech_colsum_accumulate(_stream(), _p(x), x.shape[0], x.shape[1], x.stride(0), _p(out)), "colsum_accumulate")
+    return out
+
+
 def gemm_bf16_packed(a, b, trans_a=False, trans_b=False, bias=None, out=None, accumulate=False):
     """The plain-bf16 product through bf16 COPIES of the operands (amdspeech_gemm_bf16_packed: what the H = 1024 LSTM path runs at
     precision = "bf16").  Returns None when the shape is not taken (the caller then uses gemm_bf16)."""

@@ -47,6 +47,22 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     assert (lib.CTC_KERNELS[info.kernel], info.threads, info.rmax, info.smax) == ("shift", 256, 2, 323)
     assert handle.amdspeech_ctc_plan(1001, 32, 80, 2560, ctypes.byref(info)) != 0 and b"2559" in handle.amdspeech_last_error()
     assert handle.amdspeech_ctc_plan(1001, 32, 80, 161, None) != 0
+    # the GEMM plan query: a struct of ints as the header declares it, the family names in the header's order, no device needed
+    assert {"amdspeech_gemm_plan", "amdspeech_gemm_f32_tn_group", "amdspeech_colsum_accumulate"} <= declared
+    decl = header.split("typedef struct amdspeech_gemm_plan_info {")[1].split("}")[0]
+    assert [n.strip() for n in decl.replace("int", "").replace(";", "").split(",")] == [n for n, _ in lib.GemmPlanInfo._fields_]
+    assert ctypes.sizeof(lib.GemmPlanInfo) == 4 * len(lib.GemmPlanInfo._fields_)
+    consts = re.findall(r"AMDSPEECH_GEMM_([A-Z0-9_]+) = (\d+)", header)
+    families = sorted((int(v), n.lower()) for n, v in consts if not n.startswith("MAP_") and n != "GROUP_MAX")
+    assert families == list(enumerate(lib.GEMM_FAMILIES))
+    assert [int(v) for n, v in consts if n.startswith("MAP_")] == [lib.GEMM_MAP_LINEAR, lib.GEMM_MAP_XCD, lib.GEMM_MAP_XCD_BLOCKS, lib.GEMM_MAP_KC_BAND]
+    assert "AMDSPEECH_GEMM_GROUP_MAX = %d" % lib.GEMM_GROUP_MAX in header
+    ginfo = lib.GemmPlanInfo()
+    nominal = ctypes.c_void_p(4096)      # (looked at for null and alignment only)
+    assert handle.amdspeech_gemm_plan(0, 0, 0, 32032, 80, 512, nominal, 512, nominal, 80, nominal, 80, nominal, 0, 0, 1, ctypes.byref(ginfo)) == 0
+    assert (lib.GEMM_FAMILIES[ginfo.family], ginfo.variant, ginfo.splits, ginfo.atomic) == ("skinny_n", 5, 1, 0)
+    assert handle.amdspeech_gemm_plan(0, 0, 0, 32032, 80, 512, nominal, 512, nominal, 80, None, 80, None, 0, 0, 1, ctypes.byref(ginfo)) != 0
+    assert b"null operand" in handle.amdspeech_last_error()
 
 
 def test_product_path_fails_loudly_without_the_library(tmp_path, monkeypatch):

@@ -29,7 +29,10 @@ def ops():
 # ------------------------------------------------------------------------ GEMM
 @pytest.mark.parametrize("M,N,K", [(100, 80, 40), (257, 130, 33), (1000, 512, 512), (64, 128, 5000),
                                    (16, 16, 4), (3203, 2048, 64), (512, 2048, 4096),
-                                   # the LDS-free kernels' edges: ragged last tiles, K = 33 x 64, a short last band of row tiles
+                                   # the LDS-free kernels' edges: ragged last tiles, K = 33 x 64, a short last band of row tiles.  By
+                                   # ops.gemm_plan: kc-direct without trans_a; with trans_a the call with a bias takes the LDS kernel and
+                                   # only the accumulate call below is tn-direct -- not at (130, 640, 2112), whose lda = 130 leaves the rows
+                                   # unaligned.  tests/test_gpu_gemm_paths.py holds tn-direct's odd K, ragged M and block maps by plan.
                                    (1000, 200, 2048), (130, 640, 2112), (4100, 512, 2048)])
 @pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, False), (True, True)])
 def test_gemm_matches_fp64(ops, M, N, K, ta, tb):
