@@ -578,6 +578,28 @@ int amdspeech_frontend_fbank(void* stream, const float* pcm, const int* n_sample
                              int n_max, int sample_rate, int t_max,
                              float* feat, int* n_frames, void* ws);
 
+/* The kernels the two calls above take for a shape, as plain numbers: a READ-ONLY view of the plan the launch itself reads (one
+ * function decides for both).  Nothing is launched and no device is needed; the arguments are checked as the calls check them
+ * (mode 0 mfcc / 1 fbank, B, n_max, t_max > 0, sample_rate >= 1000 and a DFT of at most 2048 points, n_mfcc in 1 .. 128 for mfcc:
+ * anything else is AMDSPEECH_EINVAL with a message, here and there).  Honours AMDSPEECH_FRONTEND_MFMA (read once per process).
+ *   frames_kernel  0 the vector-ALU frame kernel (8 frames per workgroup), 1 the matrix-core one (a queue of 32-frame tiles).  The
+ *                  choice is by LDS bytes: the matrix-core kernel needs (64 (kp + 4) + 31 hop + frame_len) * 4 <= 163,584, which
+ *                  holds for mfcc below 35.75 kHz and for fbank below 69.95 kHz; AMDSPEECH_FRONTEND_MFMA=0 takes kernel 0 everywhere
+ *   maxq           bin tiles a wave of the matrix-core kernel can own: 4 (up to 16 tiles), 5 (up to 20), 9 (above); 0 for kernel 0
+ *   n_dft, frame_len, hop, n_bins   DFT points (mfcc: round(0.025 rate); fbank: 512), window samples kept, samples between frames
+ *   bin_tiles, kp  16-bin tiles of the spectrum, padded length of the folded frame (multiples of 16 / 32)
+ *   lds_bytes      dynamic LDS of the frame kernel that is launched
+ *   t_full         frames of an n_max-sample row (the pitch of the workspace)
+ *   tiles_per_utt, n_items, workgroups   kernel 1: 32-frame tiles per row, queue items (tiles_per_utt * B), workgroups that drain
+ *                  the queue (at most 512);  kernel 0: grid x (8-frame tiles per row), grid x * grid y (y = B), and the same again
+ *   dct_kernel     -1 fbank (no DCT), 0 the vector-ALU DCT, 1 the matrix-core DCT;  dct_col_tiles: its 16-coefficient column tiles
+ *   meta_by_copy   1 when B > 256: the lengths reach the device by a copy and a stream synchronisation, not as kernel arguments */
+typedef struct amdspeech_frontend_plan_info {
+    int frames_kernel, maxq, n_dft, frame_len, hop, n_bins, bin_tiles, kp, lds_bytes, t_full, tiles_per_utt, n_items, workgroups, dct_kernel, dct_col_tiles, meta_by_copy;
+} amdspeech_frontend_plan_info;
+int amdspeech_frontend_plan(int mode, int sample_rate, int n_mfcc, int B, int n_max, int t_max,
+                            amdspeech_frontend_plan_info* out);
+
 /* ------------------------------------------------------------- profiling ----
  * Optional HIP-event timing of the recurrence kernels (no reference counterpart;
  * feeds bench.py's roofline line).  When enabled, lstm_fwd / lstm_bwd bracket

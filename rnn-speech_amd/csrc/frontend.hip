@@ -692,15 +692,68 @@ __global__ void write_meta_kernel(MetaArg m, int* dst, int n) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = m.v[i];
 }
 
-static int run_frontend(hipStream_t s, int mode, const float* pcm, const int* n_samples, int B, int n_max,
-                        int sr, int n_mfcc, int t_max, float* feat, int* n_frames, void* ws) {
-    AS_CHECK_ARG(pcm && n_samples && feat && n_frames && ws, "frontend: null pointer");
+// ---- the plan: which kernels a call takes and their launch geometry, as plain numbers (amdspeech.h: amdspeech_frontend_plan_info).
+// run_frontend plans first (nothing is dereferenced, nothing is launched, no device is needed) and LAUNCHES from the struct;
+// amdspeech_frontend_plan returns the same struct to the caller.  The conditions exist once.  The frame kernel is chosen by LDS
+// bytes, not by a sample rate: the matrix-core kernel holds the folded frames e / o of 32 frames plus their PCM span, which stops
+// fitting a CU at 35.75 kHz for mfcc (n_dft = round(0.025 sr)) and at 69.95 kHz for fbank (512 points at every rate; the
+// span grows with the hop); past that, and with AMDSPEECH_FRONTEND_MFMA=0, the vector-ALU kernel of 8 frames per workgroup runs.
+typedef amdspeech_frontend_plan_info FrontPlan;
+constexpr int FRAMES_LDS_MAX = 160 * 1024 - 256;    // (the CU's 160 KiB less the kernel's static word)
+
+static int plan_frontend(int mode, int sr, int n_mfcc, int B, int n_max, int t_max, bool on_mfma, int max_wgs, FrontPlan* p) {
+    AS_CHECK_ARG(mode == MODE_MFCC || mode == MODE_FBANK, "frontend: mode %d is neither mfcc (0) nor fbank (1)", mode);
     AS_CHECK_ARG(B > 0 && n_max > 0 && sr >= 1000 && t_max > 0, "frontend: bad shape");
     AS_CHECK_ARG(mode == MODE_FBANK || (n_mfcc >= 1 && n_mfcc <= N_MELS), "frontend: n_mfcc out of range");
     const FrontCfg c = make_cfg(mode, sr);
-    // (44.1 / 48 kHz signals -- n_fft = round(0.025 sr) = 1102 / 1200 -- go through the vector-ALU frame kernel, whose LDS need
-    //  grows with the frame; 2048 points = 81.9 kHz is where its 8 frames stop fitting a CU)
+    // (2048 points = 81.9 kHz is where the vector-ALU kernel's 8 frames stop fitting a CU)
     AS_CHECK_ARG(c.n_dft <= 2048, "frontend: sample rate %d gives a %d-point DFT (max 2048)", sr, c.n_dft);
+    int t_full = num_frames(c, n_max);
+    if (t_full < 1) t_full = 1;
+    const int half = c.n_dft / 2;
+    const int kp = (half + 1 + 31) / 32 * 32, nbp = (c.n_bins + 15) / 16 * 16;      // (build_tables)
+    p->n_dft = c.n_dft; p->frame_len = c.frame_len; p->hop = c.hop; p->n_bins = c.n_bins;
+    p->bin_tiles = nbp / 16; p->kp = kp; p->t_full = t_full;
+    // e / o (later the power spectrum over them: nbp <= 2 kp) and the PCM span of the 32 frames
+    const size_t mfma_lds = ((size_t)2 * FR * (kp + 4) + (size_t)(FR - 1) * c.hop + c.frame_len) * 4;
+    if (on_mfma && mfma_lds <= (size_t)FRAMES_LDS_MAX) {
+        p->frames_kernel = 1;
+        p->maxq = p->bin_tiles <= 16 ? 4 : p->bin_tiles <= 20 ? 5 : 9;
+        p->lds_bytes = (int)mfma_lds;
+        p->tiles_per_utt = ceil_div(t_full, FR);
+        p->n_items = p->tiles_per_utt * B;
+        // two workgroups per CU's worth (what the LDS allows at 16 kHz), never more than there are items
+        p->workgroups = p->n_items < max_wgs ? p->n_items : (max_wgs > 0 ? max_wgs : 512);
+    } else {
+        p->frames_kernel = 0;
+        p->maxq = 0;
+        p->lds_bytes = (int)(((size_t)c.frame_len * FPB + (size_t)c.n_dft * 2 + (size_t)c.n_bins * FPB) * 4);
+        p->tiles_per_utt = ceil_div(t_full, FPB);      // grid x; grid y = B: one workgroup per item
+        p->n_items = p->tiles_per_utt * B;
+        p->workgroups = p->n_items;
+    }
+    p->dct_kernel = mode == MODE_FBANK ? -1 : on_mfma ? 1 : 0;
+    p->dct_col_tiles = p->dct_kernel == 1 ? (n_mfcc + 15) / 16 : 0;
+    p->meta_by_copy = B > META_MAX ? 1 : 0;
+    return AMDSPEECH_OK;
+}
+
+// The two run-time switches, read once per process.
+static bool frontend_on_mfma() {
+    static const bool on = runtime_switch("AMDSPEECH_FRONTEND_MFMA", 1) != 0;
+    return on;
+}
+static int frontend_max_wgs() {
+    static const int n = dev_knob("AMDSPEECH_FRONTEND_WGS", 512);     // (dev: queue width)
+    return n;
+}
+
+static int run_frontend(hipStream_t s, int mode, const float* pcm, const int* n_samples, int B, int n_max,
+                        int sr, int n_mfcc, int t_max, float* feat, int* n_frames, void* ws) {
+    AS_CHECK_ARG(pcm && n_samples && feat && n_frames && ws, "frontend: null pointer");
+    FrontPlan pl;
+    if (int rc = plan_frontend(mode, sr, n_mfcc, B, n_max, t_max, frontend_on_mfma(), frontend_max_wgs(), &pl)) return rc;
+    const FrontCfg c = make_cfg(mode, sr);
     const FrontLayout lo = front_layout(c, B, n_max, mode == MODE_MFCC ? N_MELS : 1);
     const Tables* tb = get_tables(c, mode == MODE_MFCC ? n_mfcc : 0);
     AS_CHECK_ARG(tb != nullptr, "frontend: could not place the constant tables in device memory");
@@ -716,7 +769,7 @@ static int run_frontend(hipStream_t s, int mode, const float* pcm, const int* n_
         AS_CHECK_ARG(mode == MODE_MFCC || n_frames[b] == 0 || n_frames[b] >= 9, "frontend: fbank delta needs >= 9 frames (utterance %d)", b);
     }
     int* d_n = reinterpret_cast<int*>(w + lo.total);          // workspace_bytes() reserves 2*B ints past `total`
-    if (B <= META_MAX) {
+    if (!pl.meta_by_copy) {
         MetaArg ma;
         for (int i = 0; i < 2 * B; ++i) ma.v[i] = meta[i];
         hipLaunchKernelGGL(write_meta_kernel, dim3(1), dim3(256), 0, s, ma, d_n, 2 * B);
@@ -737,12 +790,8 @@ static int run_frontend(hipStream_t s, int mode, const float* pcm, const int* n_
     a.power_scale = c.power_scale;
     a.cos_t = tb->dev + tb->o_cos; a.sin_t = tb->dev + tb->o_sin; a.filt_t = tb->dev + tb->o_filt_t;
     a.half = tb->half; a.kp = tb->kp; a.nbp = tb->nbp; a.mp = tb->mp;
-    static const bool on_mfma = runtime_switch("AMDSPEECH_FRONTEND_MFMA", 1) != 0;
-    // e / o (later the power spectrum over them: nbp <= 2 kp) and the PCM span of the 32 frames
-    const size_t mfma_lds = ((size_t)2 * FR * (tb->kp + 4) + (size_t)(FR - 1) * c.hop + c.frame_len) * 4;
-    constexpr int FRAMES_LDS_MAX = 160 * 1024 - 256;    // (the CU's 160 KiB less the kernel's static word)
-    if (on_mfma && mfma_lds <= (size_t)FRAMES_LDS_MAX) {      // (sample rates above 32 kHz: the vector-ALU kernel)
-        const size_t lds = mfma_lds;
+    const size_t lds = (size_t)pl.lds_bytes;
+    if (pl.frames_kernel == 1) {
         static unsigned long long frames_lds_seen = 0;
         if (DeviceOnce once{&frames_lds_seen}) {     // (an 800-point DFT needs 150 KiB)
             AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(frontend_frames_mfma_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, FRAMES_LDS_MAX));
@@ -751,23 +800,18 @@ static int run_frontend(hipStream_t s, int mode, const float* pcm, const int* n_
             once.done();
         }
         a.queue = ctl;
-        a.tiles_per_utt = ceil_div(lo.t_full, FR);
-        a.n_items = a.tiles_per_utt * B;
-        // two workgroups per CU's worth (what the LDS allows at 16 kHz), never more than there are items
-        static const int max_wgs = dev_knob("AMDSPEECH_FRONTEND_WGS", 512);     // (dev: queue width)
-        const int wgs = a.n_items < max_wgs ? a.n_items : (max_wgs > 0 ? max_wgs : 512);
-        const int nbt = tb->nbp / 16;
-        if (nbt <= 16) hipLaunchKernelGGL(frontend_frames_mfma_kernel<4>, dim3(wgs), dim3(256), lds, s, a);
-        else if (nbt <= 20) hipLaunchKernelGGL(frontend_frames_mfma_kernel<5>, dim3(wgs), dim3(256), lds, s, a);
-        else hipLaunchKernelGGL(frontend_frames_mfma_kernel<9>, dim3(wgs), dim3(256), lds, s, a);
+        a.tiles_per_utt = pl.tiles_per_utt;
+        a.n_items = pl.n_items;
+        if (pl.maxq == 4) hipLaunchKernelGGL(frontend_frames_mfma_kernel<4>, dim3(pl.workgroups), dim3(256), lds, s, a);
+        else if (pl.maxq == 5) hipLaunchKernelGGL(frontend_frames_mfma_kernel<5>, dim3(pl.workgroups), dim3(256), lds, s, a);
+        else hipLaunchKernelGGL(frontend_frames_mfma_kernel<9>, dim3(pl.workgroups), dim3(256), lds, s, a);
     } else {
-        const size_t lds = ((size_t)c.frame_len * FPB + (size_t)c.n_dft * 2 + (size_t)c.n_bins * FPB) * 4;
         static unsigned long long valu_lds_seen = 0;
         if (DeviceOnce once{&valu_lds_seen}) {      // (a 1200-point frame needs 67 KiB, a 2048-point one 115 KiB)
             AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(frontend_frames_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FRAMES_LDS_MAX));
             once.done();
         }
-        hipLaunchKernelGGL(frontend_frames_kernel, dim3(ceil_div(lo.t_full, FPB), B), dim3(256), lds, s, a);
+        hipLaunchKernelGGL(frontend_frames_kernel, dim3(pl.tiles_per_utt, B), dim3(256), lds, s, a);
     }
     double* stat = reinterpret_cast<double*>(w + lo.stat);
     if (mode == MODE_MFCC) {      // (the per-utterance maximum came out of the frames kernel)
@@ -778,7 +822,7 @@ static int run_frontend(hipStream_t s, int mode, const float* pcm, const int* n_
                                              (int)(((size_t)N_MELS * N_MELS + 4 * N_MELS) * sizeof(float))));
             once.done();
         }
-        if (on_mfma)
+        if (pl.dct_kernel == 1)
             hipLaunchKernelGGL(mfcc_dct_mfma_kernel, dim3(ceil_div((long)t_max * B, 64)), dim3(256), 0, s, a.logmel, a.nframes,
                                umax, tb->dev + tb->o_dct, lo.t_full, t_max, B, n_mfcc, feat);
         else
@@ -926,6 +970,11 @@ extern "C" size_t amdspeech_frontend_workspace_bytes(int mode, int B, int n_max,
 extern "C" int amdspeech_frontend_num_frames(int mode, int n_samples, int sample_rate) {
     if ((mode != MODE_MFCC && mode != MODE_FBANK) || sample_rate < 1000) return AMDSPEECH_EINVAL;
     return num_frames(make_cfg(mode, sample_rate), n_samples);
+}
+
+extern "C" int amdspeech_frontend_plan(int mode, int sample_rate, int n_mfcc, int B, int n_max, int t_max, amdspeech_frontend_plan_info* out) {
+    AS_CHECK_ARG(out != nullptr, "frontend_plan: null output");
+    return plan_frontend(mode, sample_rate, n_mfcc, B, n_max, t_max, frontend_on_mfma(), frontend_max_wgs(), out);
 }
 
 extern "C" int amdspeech_frontend_mfcc(void* stream, const float* pcm, const int* n_samples, int B, int n_max,

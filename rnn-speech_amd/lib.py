@@ -47,6 +47,11 @@ class GemmPlanInfo(C.Structure):     # amdspeech_gemm_plan_info (include/amdspee
                                        "bm", "bn", "col_slices", "a_vec", "b_vec")]
 
 
+class FrontendPlanInfo(C.Structure):     # amdspeech_frontend_plan_info (include/amdspeech.h): the kernels and launch geometry of a front-end call, read-only
+    _fields_ = [(n, C.c_int) for n in ("frames_kernel", "maxq", "n_dft", "frame_len", "hop", "n_bins", "bin_tiles", "kp", "lds_bytes", "t_full",
+                                       "tiles_per_utt", "n_items", "workgroups", "dct_kernel", "dct_col_tiles", "meta_by_copy")]
+
+
 GEMM_FAMILIES = ("skinny_n", "skinny_k", "skinny_tn", "tn_direct", "kc_direct", "lds", "bf3")      # AMDSPEECH_GEMM_* (include/amdspeech.h)
 GEMM_MAP_LINEAR, GEMM_MAP_XCD, GEMM_MAP_XCD_BLOCKS, GEMM_MAP_KC_BAND = range(4)      # AMDSPEECH_GEMM_MAP_*
 GEMM_GROUP_MAX = 10                                                                 # AMDSPEECH_GEMM_GROUP_MAX
@@ -134,6 +139,7 @@ PROTOTYPES = {
     "amdspeech_clip_adam": (_I, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P]),
     "amdspeech_frontend_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "amdspeech_frontend_num_frames": (_I, [_I, _I, _I]),
+    "amdspeech_frontend_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(FrontendPlanInfo)]),
     "amdspeech_frontend_mfcc": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "amdspeech_frontend_fbank": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "amdspeech_profile_enable": (_I, [_I]),

@@ -844,6 +844,16 @@ def resample(pcm, n_samples, rate_in, rate_out):
     return out, n_out
 
 
+def frontend_plan(mode, sample_rate, n_mfcc, B, n_max, t_max):
+    """The kernels `frontend` takes for a call (amdspeech.h: amdspeech_frontend_plan), as a dict of ints.  mode "mfcc" / "fbank".
+    Read-only: nothing is launched, no device is needed.  A call the front end refuses raises here too."""
+    info = _l.FrontendPlanInfo()
+    imode = {"mfcc": MODE_MFCC, "fbank": MODE_FBANK}.get(mode, mode)
+    _l.check(_l.load().amdspeech_frontend_plan(int(imode), int(sample_rate), int(n_mfcc), int(B), int(n_max), int(t_max), C.byref(info)),
+             "frontend_plan")
+    return {name: int(getattr(info, name)) for name, _ in _l.FrontendPlanInfo._fields_}
+
+
 def frontend(pcm, n_samples, sample_rate, mode, t_max, n_mfcc=20):
     """pcm float32 [B, n_max] (device), n_samples: python ints.  Returns
     (feat [t_max, B, D] device, n_frames list of UNtruncated frame counts)."""

@@ -63,6 +63,20 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     assert (lib.GEMM_FAMILIES[ginfo.family], ginfo.variant, ginfo.splits, ginfo.atomic) == ("skinny_n", 5, 1, 0)
     assert handle.amdspeech_gemm_plan(0, 0, 0, 32032, 80, 512, nominal, 512, nominal, 80, None, 80, None, 0, 0, 1, ctypes.byref(ginfo)) != 0
     assert b"null operand" in handle.amdspeech_last_error()
+    # the front-end plan query: a struct of ints as the header declares it, the headline call on the matrix-core <4> kernel with twice
+    # as many queue items as workgroups, no device needed; what the call refuses is refused here
+    assert "amdspeech_frontend_plan" in declared
+    decl = header.split("typedef struct amdspeech_frontend_plan_info {")[1].split("}")[0]
+    assert [n.strip() for n in decl.replace("int", "").replace(";", "").split(",")] == [n for n, _ in lib.FrontendPlanInfo._fields_]
+    assert ctypes.sizeof(lib.FrontendPlanInfo) == 4 * len(lib.FrontendPlanInfo._fields_)
+    finfo = lib.FrontendPlanInfo()
+    assert handle.amdspeech_frontend_plan(0, 16000, 40, 32, 160000, 1001, ctypes.byref(finfo)) == 0
+    if os.environ.get("AMDSPEECH_FRONTEND_MFMA", "1") != "0":
+        assert (finfo.frames_kernel, finfo.maxq, finfo.bin_tiles, finfo.n_items, finfo.workgroups, finfo.dct_kernel, finfo.dct_col_tiles) == (1, 4, 13, 1024, 512, 1, 3)
+    assert (finfo.n_dft, finfo.frame_len, finfo.hop, finfo.n_bins, finfo.kp, finfo.t_full, finfo.meta_by_copy) == (400, 400, 160, 201, 224, 1001, 0)
+    assert handle.amdspeech_frontend_plan(0, 16000, 129, 32, 160000, 1001, ctypes.byref(finfo)) != 0 and b"n_mfcc out of range" in handle.amdspeech_last_error()
+    assert handle.amdspeech_frontend_plan(0, 96000, 20, 32, 160000, 1001, ctypes.byref(finfo)) != 0 and b"max 2048" in handle.amdspeech_last_error()
+    assert handle.amdspeech_frontend_plan(0, 16000, 40, 32, 160000, 1001, None) != 0
 
 
 def test_product_path_fails_loudly_without_the_library(tmp_path, monkeypatch):

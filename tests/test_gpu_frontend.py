@@ -10,6 +10,20 @@ pytestmark = pytest.mark.gpu
 
 from oracle import frontend as ofe  # noqa: E402  (checker only)
 
+MFMA = os.environ.get("AMDSPEECH_FRONTEND_MFMA", "1") != "0"      # (the switch test below runs part of this file under =0)
+
+
+def assert_plan(mode, sr, n_mfcc, B, n_max, t_max, frames_kernel, maxq, **more):
+    """The plan query (the function the launch itself reads) names the kernels this test was written for: `frames_kernel` / `maxq`
+    by default, the vector-ALU kernels everywhere under AMDSPEECH_FRONTEND_MFMA=0."""
+    from rnn_speech_amd import ops
+    plan = ops.frontend_plan(mode, sr, n_mfcc, B, n_max, t_max)
+    want = dict(frames_kernel=frames_kernel if MFMA else 0, maxq=maxq if MFMA else 0, dct_kernel=-1 if mode == "fbank" else int(MFMA))
+    if MFMA:
+        want.update(more)
+    assert {k: plan[k] for k in want} == want, (mode, sr, plan)
+    return plan
+
 
 def synth(seed, n, sr):
     rng = np.random.RandomState(seed)
@@ -25,6 +39,7 @@ def test_mfcc_matches_oracle(sr, n_mfcc):
     from rnn_speech_amd.audioprocessor import AudioProcessor
     ap = AudioProcessor(10 ** 6, "mfcc", n_mfcc=n_mfcc)
     sigs = [synth(1, sr + 321, sr), synth(2, sr // 2 + 17, sr), synth(3, 2 * sr, sr)]   # ragged batch
+    assert_plan("mfcc", sr, n_mfcc, 3, 2 * sr, 250, 1, {16000: 4, 22050: 5, 8000: 4}[sr], bin_tiles={16000: 13, 22050: 18, 8000: 7}[sr])
     feat, lengths = ap.process_batch(sigs, sr, t_max=250)
     feat = feat.cpu().numpy()
     for b, sig in enumerate(sigs):
@@ -41,6 +56,7 @@ def test_fbank_matches_reference_golden(golden_dir, tag):
     from rnn_speech_amd.audioprocessor import AudioProcessor
     z = np.load(os.path.join(golden_dir, "fbank_%s.npz" % tag))
     ap = AudioProcessor(10 ** 6, "fbank")
+    assert_plan("fbank", int(z["sr"]), 0, 1, len(z["sig"]), int(z["length"]), 1, 5, bin_tiles=17, n_dft=512)      # (fbank: <5> at every golden rate)
     feat, length = ap.process_signal(z["sig"], int(z["sr"]))
     assert length == int(z["length"]) and feat.shape == z["feat"].shape
     # static log-mel dims are pinned by the reference's numpy body; deltas by scipy savgol semantics
@@ -88,6 +104,8 @@ def test_mfcc_front_end_at_headline_batch_matches_oracle():
     sigs[31] = sigs[31][:33333]
     sigs[9] = sigs[9].copy()
     sigs[9][60000:] *= 1e-4                                 # a loud start and a near-silent tail: the 80 dB floor binds
+    # 32 tiles a row: twice as many queue items as workgroups, on <4> and the matrix-core DCT of three column tiles
+    assert_plan("mfcc", sr, 40, B, n, T, 1, 4, tiles_per_utt=32, n_items=1024, workgroups=512, dct_col_tiles=3, meta_by_copy=0)
     feat, lengths = ap.process_batch(sigs, sr)
     assert feat.shape == (T, B, 40)
     feat = feat.cpu().numpy()
@@ -168,22 +186,32 @@ def test_files_to_features_matches_signal_path(tmp_path):
     assert n1 == lengths[1] and np.abs(one - feat[:n1, 1].cpu().numpy()).max() < 1e-4
 
 
-def test_sample_rates_above_32_khz_run_the_vector_alu_frame_kernel_and_match_the_oracle():
-    """44.1 / 48 kHz `process_signal`: n_fft = round(0.025 sr) = 1102 / 1200 needs more LDS than a CU has for the matrix-core frame
-    kernel, so these rates are what still reaches `frontend_frames_kernel` (the round-1 vector-ALU kernel) by default -- no GPU test
-    did any more.  Both feature types, against the oracle."""
+def test_sample_rates_past_the_lds_cut_run_the_vector_alu_frame_kernel_and_match_the_oracle():
+    """The frame kernel is chosen by LDS bytes, not by a rate (ops.frontend_plan; tests/test_cpu_frontend_ref.py holds the cuts): the
+    matrix-core kernel keeps 32 folded frames and their PCM span in LDS, which stops fitting a CU between 35 and 36 kHz for mfcc
+    (n_fft = round(0.025 sr)) and only at 69.95 kHz for fbank (512 points at every rate).  So 44.1 / 48 kHz `process_signal` reaches
+    `frontend_frames_kernel` (the round-1 vector-ALU kernel) by default for MFCC -- with the matrix-core DCT behind it -- while
+    fbank at 44.1 kHz is still the matrix-core `<5>` kernel and needs 96 kHz to reach the vector-ALU one.  Every one of them against
+    the oracle, the plan asserted first."""
     from rnn_speech_amd.audioprocessor import AudioProcessor
     for sr in (44100, 48000):
         sig = synth(5, sr + 777, sr)
+        assert_plan("mfcc", sr, 20, 1, len(sig), 1 + len(sig) // (sr // 100), 0, 0, n_dft={44100: 1102, 48000: 1200}[sr], dct_col_tiles=2)
         ap = AudioProcessor(10 ** 6, "mfcc", n_mfcc=20)
         feat, length = ap.process_signal(sig, sr)
         ref = ofe.mfcc(sig, sr, n_mfcc=20)
         assert length == len(ref) and feat.shape == ref.shape
         assert np.abs(feat - ref).max() < 2e-3, (sr, np.abs(feat - ref).max())
     sig = synth(6, 44100 + 123, 44100)
+    assert_plan("fbank", 44100, 0, 1, len(sig), 100, 1, 5, frame_len=512, hop=441)
     feat, length = AudioProcessor(10 ** 6, "fbank").process_signal(sig, 44100)
     ref = ofe.fbank(sig, 44100)
     assert length == len(ref) and np.abs(feat - ref).max() < 2e-3
+    sig = synth(7, 96000 // 2 + 123, 96000)                 # the vector-ALU frame kernel for fbank: 512 of a 2400-sample window
+    assert_plan("fbank", 96000, 0, 1, len(sig), 100, 0, 0, frame_len=512, hop=960)
+    feat, length = AudioProcessor(10 ** 6, "fbank").process_signal(sig, 96000)
+    ref = ofe.fbank(sig, 96000)
+    assert length == len(ref) and feat.shape == ref.shape and np.abs(feat - ref).max() < 2e-3, np.abs(feat - ref).max()
 
 
 def test_vector_alu_front_end_switch_keeps_parity():
