@@ -93,14 +93,15 @@ int amdspeech_gemm_bf16(void* stream, int transA, int transB, int M, int N, int 
  *   family     AMDSPEECH_GEMM_* below
  *   variant    the kernel's template arguments as the launch switches on them: SKINNY_N NT (1 .. 6); SKINNY_K KT * 2 + transB
  *              (KT 3 or 5); SKINNY_TN FULL * 8 + RT; TN_DIRECT the number of problems; KC_DIRECT transB; LDS A_KC * 2 + B_KC
- *              (A_KC = !transA, B_KC = transB); BF3 single * 4 + A_KC * 2 + B_KC
+ *              (A_KC = !transA, B_KC = transB); BF3 single * 4 + A_KC * 2 + B_KC; BF16P (amdspeech_gemm_bf16_packed_plan only)
+ *              A_KC * 2 + B_KC: which operand copy converts in place (KC) and which transposes
  *   splits, k_chunk   K ranges and their length (SKINNY_TN: row chunks, those that start past K add nothing);  atomic: the result
  *              leaves through f32 atomics;  zero_fill: a fill launch precedes;  grid: workgroups of the main launch
  *   tiles_m, tiles_n  output tiles (SKINNY_*: row blocks / 64-column slices)
  *   map        workgroup -> tile: AMDSPEECH_GEMM_MAP_* below;  bm, bn: the block of MAP_XCD_BLOCKS;  col_slices: SKINNY_K's slices of N
  *   a_vec, b_vec      16-byte loads on that operand (0: the scalar loads of the LDS kernel)                                     */
 enum { AMDSPEECH_GEMM_SKINNY_N = 0, AMDSPEECH_GEMM_SKINNY_K = 1, AMDSPEECH_GEMM_SKINNY_TN = 2, AMDSPEECH_GEMM_TN_DIRECT = 3,
-       AMDSPEECH_GEMM_KC_DIRECT = 4, AMDSPEECH_GEMM_LDS = 5, AMDSPEECH_GEMM_BF3 = 6 };
+       AMDSPEECH_GEMM_KC_DIRECT = 4, AMDSPEECH_GEMM_LDS = 5, AMDSPEECH_GEMM_BF3 = 6, AMDSPEECH_GEMM_BF16P = 7 };
 enum { AMDSPEECH_GEMM_MAP_LINEAR = 0, AMDSPEECH_GEMM_MAP_XCD = 1, AMDSPEECH_GEMM_MAP_XCD_BLOCKS = 2, AMDSPEECH_GEMM_MAP_KC_BAND = 3 };
 enum { AMDSPEECH_GEMM_GROUP_MAX = 10 };
 typedef struct amdspeech_gemm_plan_info {
@@ -130,6 +131,21 @@ size_t amdspeech_gemm_bf16_packed_scratch_bytes(int transA, int transB, int M, i
 int amdspeech_gemm_bf16_packed(void* stream, int transA, int transB, int M, int N, int K,
                                const float* A, int lda, const float* B, int ldb,
                                float* C, int ldc, const float* bias, int accumulate, void* scratch, size_t scratch_bytes);
+/* The plan of that call's product kernel, READ-ONLY as amdspeech_gemm_plan (one function plans for launch and query): family
+ * AMDSPEECH_GEMM_BF16P, variant A_KC * 2 + B_KC, tiles_m x tiles_n tiles of 256 x 256, `splits` K ranges of k_chunk = 32 * (k tiles
+ * per split) whose partial tiles one reduce launch adds up (atomic = zero_fill = 0), grid = tiles * splits.  A shape the call does
+ * not take (scratch bytes 0) is AMDSPEECH_EINVAL with the call's message.  amdspeech_gemm_plan itself knows no precision 3.    */
+int amdspeech_gemm_bf16_packed_plan(int transA, int transB, int M, int N, int K, int lda, int ldb, amdspeech_gemm_plan_info* out);
+/* Exposed for tests: the operand copies of that path, as lstm_fwd / lstm_bwd share them between products.  bf16 values are
+ * unsigned shorts, rounded to nearest even; src and dst 16-byte aligned, ld a multiple of 4.
+ *   amdspeech_bf16_copy, transpose == 0: dst[rows][cols] = bf16(src[rows][ld]) -- dense (ldd == cols), cols a multiple of 8, no
+ *     colsum, no plain;  transpose != 0: dst[cols][ldd] = bf16(src)^T in 64 x 64 tiles (rows, cols multiples of 64, ldd a multiple
+ *     of 8, >= rows; columns rows .. ldd of dst are not written), colsum[c] += sum over r of src[r][c] (f32 atomics) when given,
+ *     plain[rows][cols] = bf16(src) (dense, 16-byte aligned) when given: the row-major copy from the same read.
+ *   amdspeech_bf16_transpose: dst[cols][ldd] = src[rows][cols]^T, src dense bf16; the same tiles and conditions.                 */
+int amdspeech_bf16_copy(void* stream, const float* src, long ld, long rows, int cols, int transpose, unsigned short* dst, long ldd,
+                        float* colsum, unsigned short* plain);
+int amdspeech_bf16_transpose(void* stream, const unsigned short* src, long rows, int cols, unsigned short* dst, long ldd);
 
 /* ----------------------------------------------------------- batch norm ----
  * Optional normalisation of the input-layer output, models/AcousticModel.py:253-259

@@ -119,6 +119,7 @@ int gemm_bf_plan(bool single, bool transA, bool transB, int M, int N, int K, con
 
 // gemm_bf16p.hip (round 5): ... through bf16 COPIES of the operands (k contiguous) and a 256 x 256 x 64 global_load_lds kernel.
 // The two steps separately -- lstm.hip shares copies between products -- and the one-call form with caller scratch.
+// (bf16p_gemm launches from the plan amdspeech_gemm_bf16_packed_plan reports: family BF16P.)
 int bf16p_copy(hipStream_t s, const float* src, long ld, long rows, int cols, bool transpose, unsigned short* dst, long ldd, float* colsum,
                unsigned short* plain = nullptr);
 size_t bf16p_partial_bytes(int M, int N, int K);

@@ -18,6 +18,7 @@
 //   3. split K (the weight gradients: M x N = 1024 x 4096 is 64 tiles) writes f32 partial tiles to scratch; one reduce pass adds
 //      them to C (no atomics).
 #include "common.h"
+#include <string.h>
 
 namespace amdspeech {
 namespace {
@@ -297,17 +298,30 @@ size_t bf16p_partial_bytes(int M, int N, int K) {
     return splits > 1 ? (size_t)splits * ceil_div(M, BM) * ceil_div(N, BN) * BM * BN * sizeof(float) : 0;
 }
 size_t bf16p_partial_bytes_max() { return (size_t)SPLIT_TILES_MAX * BM * BN * sizeof(float); }
+// The plan of the product kernel (common.h: GemmPlan): tiles, splits and grid as bf16p_gemm launches them and as
+// amdspeech_gemm_bf16_packed_plan reports them (which adds the variant: the copies are not this function's business).
+static GemmPlan bf16p_plan(int M, int N, int K) {
+    GemmPlan p;
+    memset(&p, 0, sizeof(p));
+    p.family = AMDSPEECH_GEMM_BF16P;
+    p.tiles_m = ceil_div(M, BM); p.tiles_n = ceil_div(N, BN);
+    p.col_slices = 1; p.a_vec = p.b_vec = 1;
+    p.splits = bf16p_splits(M, N, K);
+    p.k_chunk = BKT * ceil_div(K / BKT, p.splits);
+    p.grid = p.tiles_m * p.tiles_n * p.splits;
+    return p;
+}
 // C[M][N] (+)= Ak[M][K] . Bk[N][K]^T (+ bias), both operands bf16 with k contiguous (lda, ldb in elements, multiples of 8)
 int bf16p_gemm(hipStream_t s, int M, int N, int K, const unsigned short* Ak, long lda, const unsigned short* Bk, long ldb, float* C, long ldc,
                const float* bias, bool accumulate, void* partial, size_t partial_bytes) {
     AS_CHECK_ARG(M > 0 && N > 0 && K >= BKT && K % BKT == 0 && lda % 8 == 0 && ldb % 8 == 0 && Ak && Bk && C, "bf16p_gemm: bad arguments");
+    const GemmPlan p = bf16p_plan(M, N, K);
     PackedArgs g;
     g.A = Ak; g.B = Bk; g.C = C; g.bias = bias; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-    const int tiles_m = ceil_div(M, BM);
-    g.tiles_n = ceil_div(N, BN);
-    const int tiles = tiles_m * g.tiles_n, nkt = K / BKT;
-    g.splits = bf16p_splits(M, N, K);
-    g.k_tiles_per_split = ceil_div(nkt, g.splits);
+    g.tiles_n = p.tiles_n;
+    const int tiles = p.tiles_m * p.tiles_n;
+    g.splits = p.splits;
+    g.k_tiles_per_split = p.k_chunk / BKT;
     AS_CHECK_ARG(g.splits == 1 || (partial != nullptr && partial_bytes >= bf16p_partial_bytes(M, N, K)), "bf16p_gemm: no room for the split-K partial tiles");
     g.partial = static_cast<float*>(partial); g.accumulate = accumulate ? 1 : 0;
     static unsigned long long attr_done = 0;
@@ -315,9 +329,9 @@ int bf16p_gemm(hipStream_t s, int M, int N, int K, const unsigned short* Ak, lon
         AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, NST * STAGE));
         once.done();
     }
-    hipLaunchKernelGGL(gemm_bf16p_kernel, dim3(tiles * g.splits), dim3(512), NST * STAGE, s, g);
+    hipLaunchKernelGGL(gemm_bf16p_kernel, dim3(p.grid), dim3(512), NST * STAGE, s, g);
     if (g.splits > 1)
-        hipLaunchKernelGGL(gemm_bf16p_reduce_kernel, dim3(ceil_div((long)tiles * BM * BN / 4, 256)), dim3(256), 0, s, g.partial, g.splits, tiles_m,
+        hipLaunchKernelGGL(gemm_bf16p_reduce_kernel, dim3(ceil_div((long)tiles * BM * BN / 4, 256)), dim3(256), 0, s, g.partial, g.splits, p.tiles_m,
                            g.tiles_n, C, ldc, M, N, bias, accumulate ? 1 : 0);
     AS_CHECK_LAUNCH();
     return AMDSPEECH_OK;
@@ -358,10 +372,32 @@ extern "C" size_t amdspeech_gemm_bf16_packed_scratch_bytes(int trans_a, int tran
     if (!gemm_bf16_packed_ok(trans_a != 0, trans_b != 0, M, N, K, lda, ldb)) return 0;
     return gemm_bf16_packed_scratch_bytes(M, N, K);
 }
+// The plan the call above launches its product kernel from (bf16p_gemm plans with the same function); a shape the call refuses is
+// refused here with the call's message.
+extern "C" int amdspeech_gemm_bf16_packed_plan(int trans_a, int trans_b, int M, int N, int K, int lda, int ldb, amdspeech_gemm_plan_info* out) {
+    AS_CHECK_ARG(out != nullptr, "gemm_bf16_packed_plan: null output");
+    AS_CHECK_ARG(gemm_bf16_packed_ok(trans_a != 0, trans_b != 0, M, N, K, lda, ldb), "gemm_bf16_packed: shape not taken");
+    *out = bf16p_plan(M, N, K);
+    out->variant = (trans_a != 0 ? 0 : 2) + (trans_b != 0 ? 1 : 0);
+    return AMDSPEECH_OK;
+}
 extern "C" int amdspeech_gemm_bf16_packed(void* stream, int trans_a, int trans_b, int M, int N, int K, const float* A, int lda,
                                           const float* B, int ldb, float* C, int ldc, const float* bias, int accumulate,
                                           void* scratch, size_t scratch_bytes) {
     AS_CHECK_ARG(A && B && C, "gemm_bf16_packed: null pointer");
     return gemm_bf16_packed(static_cast<hipStream_t>(stream), trans_a != 0, trans_b != 0, M, N, K, A, lda, B, ldb, C, ldc, bias,
                             accumulate != 0, nullptr, scratch, scratch_bytes);
+}
+
+// Exposed for tests: the operand copies of the packed path as lstm.hip calls them (bf16p_copy, bf16p_transpose), with the checks
+// their callers make by construction: rows at least as long as their contents, 16-byte aligned matrices.
+extern "C" int amdspeech_bf16_copy(void* stream, const float* src, long ld, long rows, int cols, int transpose, unsigned short* dst, long ldd,
+                                   float* colsum, unsigned short* plain) {
+    AS_CHECK_ARG(src && dst && rows > 0 && cols > 0 && ld >= cols && ldd >= (transpose != 0 ? rows : (long)cols) && ((uintptr_t)plain % 16) == 0,
+                 "bf16_copy: bad arguments");
+    return bf16p_copy(static_cast<hipStream_t>(stream), src, ld, rows, cols, transpose != 0, dst, ldd, colsum, plain);
+}
+extern "C" int amdspeech_bf16_transpose(void* stream, const unsigned short* src, long rows, int cols, unsigned short* dst, long ldd) {
+    AS_CHECK_ARG(src && dst && cols > 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0, "bf16_transpose: bad arguments");
+    return bf16p_transpose(static_cast<hipStream_t>(stream), src, rows, cols, dst, ldd);
 }

@@ -52,7 +52,7 @@ class FrontendPlanInfo(C.Structure):     # amdspeech_frontend_plan_info (include
                                        "tiles_per_utt", "n_items", "workgroups", "dct_kernel", "dct_col_tiles", "meta_by_copy")]
 
 
-GEMM_FAMILIES = ("skinny_n", "skinny_k", "skinny_tn", "tn_direct", "kc_direct", "lds", "bf3")      # AMDSPEECH_GEMM_* (include/amdspeech.h)
+GEMM_FAMILIES = ("skinny_n", "skinny_k", "skinny_tn", "tn_direct", "kc_direct", "lds", "bf3", "bf16p")      # AMDSPEECH_GEMM_* (include/amdspeech.h)
 GEMM_MAP_LINEAR, GEMM_MAP_XCD, GEMM_MAP_XCD_BLOCKS, GEMM_MAP_KC_BAND = range(4)      # AMDSPEECH_GEMM_MAP_*
 GEMM_GROUP_MAX = 10                                                                 # AMDSPEECH_GEMM_GROUP_MAX
 CTC_KERNELS = ("wave", "shift", "pair", "edge")      # AMDSPEECH_CTC_KERNEL_* (include/amdspeech.h)
@@ -85,6 +85,9 @@ PROTOTYPES = {
     "amdspeech_colsum_accumulate": (_I, [_P, _P, _I, _I, _I, _P]),
     "amdspeech_gemm_bf16_packed_scratch_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
     "amdspeech_gemm_bf16_packed": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _SZ]),
+    "amdspeech_gemm_bf16_packed_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, C.POINTER(GemmPlanInfo)]),
+    "amdspeech_bf16_copy": (_I, [_P, _P, C.c_long, C.c_long, _I, _I, _P, C.c_long, _P, _P]),
+    "amdspeech_bf16_transpose": (_I, [_P, _P, C.c_long, _I, _P, C.c_long]),
     "amdspeech_batchnorm_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F]),
     "amdspeech_batchnorm_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I]),
     "amdspeech_batchnorm_sum": (_I, [_P, _P, _P, _I, _P, _I, _I, _I]),

@@ -63,14 +63,15 @@ def gemm(a, b, trans_a=False, trans_b=False, bias=None, out=None, accumulate=Fal
 def gemm_bf16x3(a, b, trans_a=False, trans_b=False, bias=None, out=None, accumulate=False, single=False):
     """The same product as gemm() in split precision (bf16 hi/lo pairs, three bf16 MFMAs per product term, f32 accumulate);
     single=True: plain bf16 operands (one bf16 per value, one MFMA per term: precision = "bf16")."""
-    _chk_f32(a, b, bias, out)
+    _chk_f32(bias)
+    _chk_f32_rows(a, b, out)
     M, K = (a.shape[1], a.shape[0]) if trans_a else a.shape
     K2, N = (b.shape[1], b.shape[0]) if trans_b else b.shape
     assert K == K2, (a.shape, b.shape)
     if out is None:
         out = torch.empty(M, N, device=a.device, dtype=torch.float32)
     fn = _l.load().amdspeech_gemm_bf16 if single else _l.load().amdspeech_gemm_bf16x3
-    _l.check(fn(_stream(), int(trans_a), int(trans_b), M, N, K, _p(a), a.shape[1], _p(b), b.shape[1], _p(out), out.shape[1], _p(bias),
+    _l.check(fn(_stream(), int(trans_a), int(trans_b), M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0), _p(bias),
                 int(accumulate)), "gemm_bf16" if single else "gemm_bf16x3")
     return out
 
@@ -140,23 +141,77 @@ def colsum_accumulate(x, out):
     return out
 
 
-def gemm_bf16_packed(a, b, trans_a=False, trans_b=False, bias=None, out=None, accumulate=False):
+def gemm_bf16_packed(a, b, trans_a=False, trans_b=False, bias=None, out=None, accumulate=False, scratch=None):
     """The plain-bf16 product through bf16 COPIES of the operands (amdspeech_gemm_bf16_packed: what the H = 1024 LSTM path runs at
-    precision = "bf16").  Returns None when the shape is not taken (the caller then uses gemm_bf16)."""
-    _chk_f32(a, b, bias, out)
+    precision = "bf16").  Returns None when the shape is not taken (the caller then uses gemm_bf16).  scratch: a uint8 device tensor
+    used as given (256-byte aligned, at least the bytes amdspeech_gemm_bf16_packed_scratch_bytes names); None allocates one."""
+    _chk_f32(bias)
+    _chk_f32_rows(a, b, out)
     M, K = (a.shape[1], a.shape[0]) if trans_a else a.shape
     K2, N = (b.shape[1], b.shape[0]) if trans_b else b.shape
     assert K == K2, (a.shape, b.shape)
     lib = _l.load()
-    n = lib.amdspeech_gemm_bf16_packed_scratch_bytes(int(trans_a), int(trans_b), M, N, K, a.shape[1], b.shape[1])
+    n = lib.amdspeech_gemm_bf16_packed_scratch_bytes(int(trans_a), int(trans_b), M, N, K, a.stride(0), b.stride(0))
     if n == 0:
         return None
     if out is None:
         out = torch.empty(M, N, device=a.device, dtype=torch.float32)
-    scratch = torch.empty(n, device=a.device, dtype=torch.uint8)
-    _l.check(lib.amdspeech_gemm_bf16_packed(_stream(), int(trans_a), int(trans_b), M, N, K, _p(a), a.shape[1], _p(b), b.shape[1], _p(out),
-                                            out.shape[1], _p(bias), int(accumulate), _p(scratch), n), "gemm_bf16_packed")
+    if scratch is None:
+        scratch = torch.empty(n, device=a.device, dtype=torch.uint8)
+    if not (scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.numel() >= n and scratch.data_ptr() % 256 == 0):
+        raise ValueError("scratch: expected a contiguous uint8 device tensor of >= %d bytes, 256-byte aligned" % n)
+    _l.check(lib.amdspeech_gemm_bf16_packed(_stream(), int(trans_a), int(trans_b), M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out),
+                                            out.stride(0), _p(bias), int(accumulate), _p(scratch), scratch.numel()), "gemm_bf16_packed")
     return out
+
+
+def gemm_bf16_packed_plan(a, b, trans_a=False, trans_b=False):
+    """The plan of gemm_bf16_packed()'s product kernel (amdspeech.h: amdspeech_gemm_bf16_packed_plan), as gemm_plan() returns one:
+    family "bf16p".  a, b: tensors or shapes as _plan_operand takes them.  A shape that is not taken raises."""
+    _, ar, ac, lda = _plan_operand(a)
+    _, br, bc, ldb = _plan_operand(b)
+    M, K = (ac, ar) if trans_a else (ar, ac)
+    K2, N = (bc, br) if trans_b else (br, bc)
+    assert K == K2, ((ar, ac), (br, bc))
+    info = _l.GemmPlanInfo()
+    _l.check(_l.load().amdspeech_gemm_bf16_packed_plan(int(trans_a), int(trans_b), M, N, K, lda, ldb, C.byref(info)), "gemm_bf16_packed_plan")
+    plan = {name: int(getattr(info, name)) for name, _ in _l.GemmPlanInfo._fields_}
+    plan["family"] = _l.GEMM_FAMILIES[plan["family"]]
+    return plan
+
+
+def _chk_bf16_rows(*ts):
+    """2-D device matrices of bf16 values (torch.bfloat16, or their bits as int16) with contiguous rows."""
+    for t in ts:
+        if t is None:
+            continue
+        if not (t.is_cuda and t.dtype in (torch.bfloat16, torch.int16) and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]):
+            raise ValueError("expected a bfloat16 / int16 device matrix with contiguous rows, got %s %s %s" % (t.dtype, t.device, t.stride()))
+
+
+def bf16_copy(src, dst, transpose=False, colsum=None, plain=None):
+    """dst = bf16(src) (amdspeech_bf16_copy: the operand copies of the packed bf16 path).  src [rows, cols] f32 with contiguous rows;
+    dst [rows, cols] dense, or -- transpose -- [cols, rows] with contiguous rows; then also colsum [cols] f32 (+= column sums of src)
+    and plain [rows, cols] dense (the row-major copy from the same read)."""
+    _chk_f32_rows(src)
+    _chk_f32(colsum)
+    _chk_bf16_rows(dst, plain)
+    rows, cols = src.shape
+    assert tuple(dst.shape) == ((cols, rows) if transpose else (rows, cols)), (src.shape, dst.shape)
+    assert colsum is None or colsum.numel() == cols
+    assert plain is None or (tuple(plain.shape) == (rows, cols) and plain.is_contiguous())
+    _l.check(_l.load().amdspeech_bf16_copy(_stream(), _p(src), src.stride(0), rows, cols, int(transpose), _p(dst), dst.stride(0), _p(colsum),
+                                           _p(plain)), "bf16_copy")
+    return dst
+
+
+def bf16_transpose(src, dst):
+    """dst [cols, rows] = src [rows, cols]^T in bf16 (amdspeech_bf16_transpose); src dense, dst with contiguous rows."""
+    _chk_bf16_rows(src, dst)
+    rows, cols = src.shape
+    assert src.is_contiguous() and tuple(dst.shape) == (cols, rows), (src.shape, dst.shape)
+    _l.check(_l.load().amdspeech_bf16_transpose(_stream(), _p(src), rows, cols, _p(dst), dst.stride(0)), "bf16_transpose")
+    return dst
 
 
 def linear_fwd(x, w, b, out=None):
