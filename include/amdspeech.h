@@ -616,6 +616,39 @@ typedef struct amdspeech_frontend_plan_info {
 int amdspeech_frontend_plan(int mode, int sample_rate, int n_mfcc, int B, int n_max, int t_max,
                             amdspeech_frontend_plan_info* out);
 
+/* ---------------------------------------------------- low frame rate input ---
+ * Frame stacking and subsampling between the front end and the input Linear (no reference counterpart: an opt-in deviation,
+ * off when stack = skip = 1, where no caller makes this call): `stack` consecutive front-end frames are concatenated into one
+ * model frame and every `skip`-th such frame is kept.  With the input Linear behind it this is a strided 1-D convolution over
+ * time; everything past it runs ceil(T / skip) frames.
+ *   x         float [t_in][B][D]   the front end's `feat`, time-major
+ *   n_frames  int32 [B] (HOST)     the front end's UNtruncated frame counts: n_frames[b] may exceed t_in
+ *   out       float [t_out][B][stack * D],  t_out = ceil(t_in / skip)
+ *   n_out     int32 [B] (HOST, out) ceil(n_frames[b] / skip), untruncated in the same way
+ *   out[j][b][i * D + d] = x[j * skip + i][b][d]   if j * skip + i < min(n_frames[b], t_in),   0 otherwise
+ * The kernel writes EVERY element of out (a row past its utterance is all zeros), masks by n_frames[b] itself -- frames of x at or
+ * past it are never read and may hold anything -- and copies bit patterns: -0.0, denormals, infinities and NaN payloads of the
+ * valid region arrive unchanged.  Asynchronous on `stream`; the lengths travel as kernel arguments up to 256 rows, above that
+ * through a device buffer of the call's own (the call then waits for the stream before it returns).
+ * AMDSPEECH_EINVAL with a message: null pointers, non-positive sizes, a negative count, stack or skip outside 1 .. 16,
+ * stack * D > 4096, x and out ranges that overlap, and -- when D is a multiple of 4 (16-byte loads and stores) -- a base pointer
+ * that is not 16-byte aligned.
+ * amdspeech_frame_stack_num_frames: ceil(n_frames / skip), host arithmetic (AMDSPEECH_EINVAL for n_frames < 0 or a bad skip).
+ * amdspeech_frame_stack_plan: the launch geometry as plain numbers, a READ-ONLY view of the plan the launch itself reads (one
+ * function decides for both); no device is needed, the shape is checked as the call checks it.
+ *   t_out, d_out   ceil(t_in / skip), stack * D
+ *   vec            words per lane and access: 4 when D % 4 == 0, else 1
+ *   workgroups     of 256 threads; the smallest power of two of lanes that covers d_out / vec (at most 256) shares one
+ *                  (model frame, row) item, the grid strides over the items and is capped at 2048
+ *   meta_by_copy   1 when B > 256                                                                                              */
+typedef struct amdspeech_frame_stack_plan_info {
+    int t_out, d_out, vec, workgroups, meta_by_copy;
+} amdspeech_frame_stack_plan_info;
+int amdspeech_frame_stack_num_frames(int n_frames, int skip);
+int amdspeech_frame_stack(void* stream, const float* x, const int* n_frames, int B, int D, int t_in, int stack, int skip,
+                          float* out, int* n_out);
+int amdspeech_frame_stack_plan(int B, int D, int t_in, int stack, int skip, amdspeech_frame_stack_plan_info* out);
+
 /* ------------------------------------------------------------- profiling ----
  * Optional HIP-event timing of the recurrence kernels (no reference counterpart;
  * feeds bench.py's roofline line).  When enabled, lstm_fwd / lstm_bwd bracket

@@ -69,18 +69,21 @@ class AcousticDataset(object):
     every feature every epoch.  Here a producer thread decodes the NEXT `prefetch` mini-batches (native
     decoders on a thread pool, GIL released) while the GPU trains on the current one, and -- optionally --
     the features of file items are kept in host memory after their first use (`feature_cache_mb` > 0), so
-    later epochs skip decode, resampling and the front end altogether."""
+    later epochs skip decode, resampling and the front end altogether.
+
+    frame_stack / frame_skip: low frame rate input (AudioProcessor).  max_input_seq_length stays in SOURCE frames; the batches,
+    their lengths, T and the feature cache are in MODEL frames (T = audio.out_seq_length rows of audio.feature_size values)."""
 
     def __init__(self, input_set, batch_size, max_input_seq_length, max_target_seq_length,
                  signal_processing, char_map, n_mfcc=20, device="cuda", prefetch=2, feature_cache_mb=0,
-                 sample_rate=22050):
+                 sample_rate=22050, frame_stack=1, frame_skip=1):
         self.items = [(it[0], it[1]) for it in input_set]
         self.batch_size = batch_size
-        self.T = max_input_seq_length
         self.U = max_target_seq_length
         self.char_map = char_map
         self.audio = AudioProcessor(max_input_seq_length, signal_processing, n_mfcc=n_mfcc, device=device,
-                                    load_sr=sample_rate)
+                                    load_sr=sample_rate, frame_stack=frame_stack, frame_skip=frame_skip)
+        self.T = self.audio.out_seq_length
         self.prefetch = int(prefetch)
         self._signal_processing, self._n_mfcc = signal_processing, n_mfcc
         self._cache = {} if feature_cache_mb > 0 else None
@@ -89,9 +92,10 @@ class AcousticDataset(object):
     def with_items(self, input_set):
         """The same dataset over a re-ordered / re-shuffled item list, sharing the feature cache (the
         reference builds a fresh tf.data pipeline at every epoch, stt.py:198-207)."""
-        other = AcousticDataset(input_set, self.batch_size, self.T, self.U, self._signal_processing, self.char_map,
-                                n_mfcc=self._n_mfcc, device=self.audio.device, prefetch=self.prefetch,
-                                sample_rate=self.audio.load_sr)
+        other = AcousticDataset(input_set, self.batch_size, self.audio.max_input_seq_length, self.U, self._signal_processing,
+                                self.char_map, n_mfcc=self._n_mfcc, device=self.audio.device, prefetch=self.prefetch,
+                                sample_rate=self.audio.load_sr, frame_stack=self.audio.frame_stack,
+                                frame_skip=self.audio.frame_skip)
         other._cache, other._room = self._cache, self._room
         return other
 
@@ -497,6 +501,10 @@ class AcousticModel(object):
         self.precision = "f32"             # "bf16x3": opt-in split-precision MFMA in the recurrence (config key `precision`)
         self.bidirectional = False         # config key `bidirectional` (BASELINE configs[4]; the reference is unidirectional)
         self.bidirectional_mode = "top"    # config key `bidirectional_mode`: top (two stacks) | layer (stack_bidirectional_dynamic_rnn)
+        # config keys `frame_stack` / `frame_skip`: low frame rate input.  The model itself only sees their effect -- it is constructed
+        # with the MODEL length (AudioProcessor.out_seq_length) and input_dim = AudioProcessor.feature_size; evaluate_full builds
+        # its AudioProcessor from them
+        self.frame_stack = self.frame_skip = 1
         self.sync_batch_norm = False       # config key `sync_batch_norm`: data-parallel batch-norm moments over ALL ranks (deviation)
         self.save_tf_bundle = False        # also write <stem>.index / .data-00000-of-00001 on save()
         self.save_optimizer_state = True   # native .npz also carries Adam m/v/step and the RNN state
@@ -690,10 +698,13 @@ class AcousticModel(object):
     # ---- input plumbing ----------------------------------------------------------
     @staticmethod
     def build_dataset(input_set, batch_size, max_input_seq_length, max_target_seq_length,
-                      signal_processing, char_map, n_mfcc=20, prefetch=2, feature_cache_mb=0, sample_rate=22050):
+                      signal_processing, char_map, n_mfcc=20, prefetch=2, feature_cache_mb=0, sample_rate=22050,
+                      frame_stack=1, frame_skip=1):
+        """max_input_seq_length in SOURCE frames, whatever frame_stack / frame_skip (the dataset's T is in model frames)."""
         return AcousticDataset(input_set, batch_size, max_input_seq_length, max_target_seq_length,
                                signal_processing, char_map, n_mfcc=n_mfcc, prefetch=prefetch,
-                               feature_cache_mb=feature_cache_mb, sample_rate=sample_rate)
+                               feature_cache_mb=feature_cache_mb, sample_rate=sample_rate,
+                               frame_stack=frame_stack, frame_skip=frame_skip)
 
     def add_dataset_input(self, dataset):
         self._single_iter = DatasetIterator(dataset)
@@ -1075,7 +1086,9 @@ class AcousticModel(object):
 
     def evaluate_full(self, sess, eval_dataset, input_seq_length, signal_processing, char_map,
                       run_options=None, run_metadata=None, n_mfcc=20, sample_rate=22050):
-        audio = AudioProcessor(input_seq_length, signal_processing, n_mfcc=n_mfcc, load_sr=sample_rate)
+        """input_seq_length: max_input_seq_length, in SOURCE frames (the model's own length is in model frames)."""
+        audio = AudioProcessor(input_seq_length, signal_processing, n_mfcc=n_mfcc, load_sr=sample_rate,
+                               frame_stack=self.frame_stack, frame_skip=self.frame_skip)
         wer_list, cer_list = [], []
         feats, lens, texts = [], [], []
         B, T, D = self.batch_size, self.max_input_seq_length, audio.feature_size

@@ -16,10 +16,16 @@ DEFAULT_LOAD_SR = 22050   # librosa.load default used by the reference's file pa
 
 
 class AudioProcessor(object):
-    def __init__(self, max_input_seq_length, feature_type="mfcc", n_mfcc=20, device="cuda", load_sr=DEFAULT_LOAD_SR):
+    def __init__(self, max_input_seq_length, feature_type="mfcc", n_mfcc=20, device="cuda", load_sr=DEFAULT_LOAD_SR,
+                 frame_stack=1, frame_skip=1):
         """feature_type: 'mfcc' (n_mfcc-dim, reference default 20) or 'fbank' (120-dim).  load_sr: the rate audio
         FILES are resampled to before feature extraction (config.ini `sample_rate`; the reference's librosa.load
-        default, 22,050 Hz) -- set it to the corpus rate (16,000 for LibriSpeech) to skip resampling."""
+        default, 22,050 Hz) -- set it to the corpus rate (16,000 for LibriSpeech) to skip resampling.
+        frame_stack / frame_skip (1 .. 16; 1 / 1 is the reference's behaviour): low frame rate input -- `frame_stack` consecutive
+        frames are concatenated into one MODEL frame and every `frame_skip`-th one is kept (ops.frame_stack).
+        max_input_seq_length stays in SOURCE frames (audio is truncated as without the option); what the process_* calls return
+        is out_seq_length = ceil(max_input_seq_length / frame_skip) model frames of feature_size = frame_stack * D values, and
+        lengths of ceil(n / frame_skip)."""
         self.max_input_seq_length = max_input_seq_length
         self.load_sr = int(load_sr)
         self.feature_type = feature_type
@@ -32,9 +38,20 @@ class AudioProcessor(object):
             raise ValueError("{0} is not a valid extraction function, only fbank and mfcc are accepted."
                              .format(feature_type))
         self.n_mfcc = int(n_mfcc)
+        self.frame_stack, self.frame_skip = int(frame_stack), int(frame_skip)
+        for name, v in (("frame_stack", self.frame_stack), ("frame_skip", self.frame_skip)):
+            if not 1 <= v <= 16:
+                raise ValueError("%s must be in 1 .. 16, not %r" % (name, v))
+        self.source_feature_size = self.feature_size            # what the front end emits per 10 ms frame
+        self.feature_size *= self.frame_stack                   # ... and the model reads per model frame
+        if self.feature_size > 4096:
+            raise ValueError("frame_stack * feature width = %d exceeds 4096" % self.feature_size)
+        self.out_seq_length = -(-int(max_input_seq_length) // self.frame_skip)
         # samples between the starts of two frames (csrc/frontend.hip: 10 ms, rounded half to even, in both modes): frame t of a
         # file starts t * hop_samples / load_sr seconds in
         self.hop_samples = int(round(self.load_sr * 0.01))
+        # ... and between the starts of two MODEL frames: model frame j starts with source frame j * frame_skip
+        self.frame_hop_samples = self.hop_samples * self.frame_skip
 
     @staticmethod
     def get_mfcc_length_from_duration(duration):
@@ -44,12 +61,12 @@ class AudioProcessor(object):
     # ---- reference surface ----------------------------------------------------
     def process_audio_file(self, file_name):
         feat, lengths = self.process_files([file_name])
-        n = min(lengths[0], self.max_input_seq_length)
+        n = min(lengths[0], self.out_seq_length)
         return feat[:n, 0, :].cpu().numpy(), lengths[0]
 
     def process_signal(self, sig, sr):
         feat, lengths = self.process_batch([np.asarray(sig, dtype=np.float32)], sr)
-        n = min(lengths[0], self.max_input_seq_length)
+        n = min(lengths[0], self.out_seq_length)
         return feat[:n, 0, :].cpu().numpy(), lengths[0]
 
     # ---- batched device path ----------------------------------------------------
@@ -76,15 +93,32 @@ class AudioProcessor(object):
         block, n = self.stage(signals, rows)
         return self._upload_staged(block), n
 
+    def _source_t_max(self, t_max):
+        """t_max counts the frames a process_* call RETURNS (model frames); the front end runs every source frame their windows
+        reach, never more than max_input_seq_length (so at most out_seq_length model frames come back)."""
+        if t_max is None:
+            return self.max_input_seq_length
+        if self.frame_stack == 1 and self.frame_skip == 1:
+            return int(t_max)
+        return max(1, min((int(t_max) - 1) * self.frame_skip + self.frame_stack, self.max_input_seq_length))
+
+    def _stacked(self, feat, lengths, t_max):
+        """Low frame rate input behind the front end; at (1, 1) the front end's own tensor, no copy and no launch."""
+        if self.frame_stack == 1 and self.frame_skip == 1:
+            return feat, lengths
+        out, n_out = ops.frame_stack(feat, lengths, self.frame_stack, self.frame_skip)
+        return (out if t_max is None or out.shape[0] <= t_max else out[:int(t_max)]), n_out
+
     def process_batch(self, signals, sr, t_max=None, staged=None):
-        """signals: list of 1-D float arrays, all at sample rate `sr`.  Returns (feat [t_max, B, D] device
-        float32, zero past each utterance; list of UNtruncated frame counts).  staged: (block, n) from stage()."""
-        t_max = self.max_input_seq_length if t_max is None else t_max
+        """signals: list of 1-D float arrays, all at sample rate `sr`.  Returns (feat [t_max, B, feature_size] device
+        float32, zero past each utterance; list of UNtruncated frame counts) -- model frames under low frame rate input,
+        t_max defaulting to out_seq_length.  staged: (block, n) from stage()."""
+        t_out, t_max = t_max, self._source_t_max(t_max)
         if staged is not None:
             pcm, n = self._upload_staged(staged[0]), staged[1]
         else:
             pcm, n = self._upload(signals)
-        return ops.frontend(pcm, n, int(sr), self.feature_type, int(t_max), self.n_mfcc)
+        return self._stacked(*ops.frontend(pcm, n, int(sr), self.feature_type, int(t_max), self.n_mfcc), t_out)
 
     def stage_files(self, decoded):
         """stage() for decoded files, grouped by source rate as process_files uploads them: [(sr, idx, block, n)]."""
@@ -98,8 +132,8 @@ class AudioProcessor(object):
         then the extractor, util/audioprocessor.py:41-61), for a whole mini-batch: files are decoded natively
         on host threads (or passed in as `decoded` [(signal, sr), ...]), uploaded once, resampled to
         22,050 Hz on the GPU per source rate and handed to the front-end kernels without leaving HBM.
-        `rows` > len(files) pads the batch with empty utterances (length 0)."""
-        t_max = self.max_input_seq_length if t_max is None else t_max
+        `rows` > len(files) pads the batch with empty utterances (length 0).  Model frames as process_batch."""
+        t_out, t_max = t_max, self._source_t_max(t_max)
         if decoded is None:
             decoded = decode_files(file_names)
         B = rows or len(decoded)
@@ -123,7 +157,7 @@ class AudioProcessor(object):
                 for j, i in enumerate(idx):
                     n[i] = lens[j]
         # (an empty row has no frames; the front end wants > n_fft/2 samples for real ones)
-        return ops.frontend(pcm, n, self.load_sr, self.feature_type, int(t_max), self.n_mfcc)
+        return self._stacked(*ops.frontend(pcm, n, self.load_sr, self.feature_type, int(t_max), self.n_mfcc), t_out)
 
 
 class _Staged(object):

@@ -1,6 +1,6 @@
 """config.ini reader + checkpoint-side pickle logic (reference:
 /root/reference/util/hyperparams.py:17-141).  Same section/key names and defaults; a few
-optional keys are added for the MI355X build (n_mfcc, sample_rate)."""
+optional keys are added for the MI355X build (n_mfcc, sample_rate, frame_stack / frame_skip ...)."""
 import configparser
 import logging
 import os
@@ -10,11 +10,11 @@ import time
 _ACOUSTIC, _GENERAL, _TRAINING, _LOGGING = "acoustic_network_params", "general", "training", "logging"
 # a change of any of these makes an existing checkpoint unusable (the reference compares the first four,
 # util/hyperparams.py:75-92; n_mfcc / sample_rate are this build's extra keys and change the input layer's
-# shape / the features' meaning)
+# shape / the features' meaning; so do frame_stack / frame_skip, the low frame rate input)
 _STRUCTURAL = ("num_layers", "hidden_size", "signal_processing", "language", "n_mfcc", "sample_rate", "bidirectional",
-               "bidirectional_mode")
+               "bidirectional_mode", "frame_stack", "frame_skip")
 _STRUCTURAL_DEFAULTS = {"signal_processing": "mfcc", "language": "", "n_mfcc": 20, "sample_rate": 22050, "bidirectional": False,
-                        "bidirectional_mode": "top"}
+                        "bidirectional_mode": "top", "frame_stack": 1, "frame_skip": 1}
 
 
 def read_config_file(config_file):
@@ -59,6 +59,12 @@ def read_config_file(config_file):
     d["bidirectional_mode"] = cp.get(_ACOUSTIC, "bidirectional_mode", fallback="top")
     if d["bidirectional_mode"] not in ("top", "layer"):
         raise ValueError("bidirectional_mode must be 'top' or 'layer', not %r" % d["bidirectional_mode"])
+    # low frame rate input: frame_stack consecutive 10 ms frames concatenated into one model frame, every frame_skip-th kept
+    # (1 / 1: off, the reference's behaviour).  max_input_seq_length stays in source frames
+    for key in ("frame_stack", "frame_skip"):
+        d[key] = cp.getint(_ACOUSTIC, key, fallback=1)
+        if not 1 <= d[key] <= 16:
+            raise ValueError("%s must be in 1 .. 16, not %r" % (key, d[key]))
     d["sync_batch_norm"] = cp.getboolean(_TRAINING, "sync_batch_norm", fallback=False)   # DP only; deviation from the reference
     # the decoder behind the per-mini-batch training error rate: greedy (GPU) | beam (default: the reference's width-100 beam
     # decoder, models/AcousticModel.py:312-314,:641, on host threads, reported `train_decoder_lag` mini-batches late; 0 = wait)

@@ -52,6 +52,10 @@ class FrontendPlanInfo(C.Structure):     # amdspeech_frontend_plan_info (include
                                        "tiles_per_utt", "n_items", "workgroups", "dct_kernel", "dct_col_tiles", "meta_by_copy")]
 
 
+class FrameStackPlanInfo(C.Structure):     # amdspeech_frame_stack_plan_info (include/amdspeech.h): the launch geometry of a frame-stacking call, read-only
+    _fields_ = [(n, C.c_int) for n in ("t_out", "d_out", "vec", "workgroups", "meta_by_copy")]
+
+
 GEMM_FAMILIES = ("skinny_n", "skinny_k", "skinny_tn", "tn_direct", "kc_direct", "lds", "bf3", "bf16p")      # AMDSPEECH_GEMM_* (include/amdspeech.h)
 GEMM_MAP_LINEAR, GEMM_MAP_XCD, GEMM_MAP_XCD_BLOCKS, GEMM_MAP_KC_BAND = range(4)      # AMDSPEECH_GEMM_MAP_*
 GEMM_GROUP_MAX = 10                                                                 # AMDSPEECH_GEMM_GROUP_MAX
@@ -145,6 +149,9 @@ PROTOTYPES = {
     "amdspeech_frontend_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(FrontendPlanInfo)]),
     "amdspeech_frontend_mfcc": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "amdspeech_frontend_fbank": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "amdspeech_frame_stack_num_frames": (_I, [_I, _I]),
+    "amdspeech_frame_stack": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "amdspeech_frame_stack_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(FrameStackPlanInfo)]),
     "amdspeech_profile_enable": (_I, [_I]),
     "amdspeech_profile_get": (_I, [_I, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "amdspeech_profile_get_flops": (_I, [_I, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -937,3 +937,34 @@ def frontend(pcm, n_samples, sample_rate, mode, t_max, n_mfcc=20):
                                           _p(ws))
     _l.check(rc, "frontend_" + mode)
     return feat, list(nf)          # stream-ordered; the cached workspace outlives the kernels
+
+
+# ------------------------------------------------------------ low frame rate input
+def frame_stack_plan(B, D, t_in, stack, skip):
+    """The launch geometry of `frame_stack` for a shape (amdspeech.h: amdspeech_frame_stack_plan), as a dict of ints.  Read-only:
+    nothing is launched, no device is needed.  A shape the call refuses raises here too."""
+    info = _l.FrameStackPlanInfo()
+    _l.check(_l.load().amdspeech_frame_stack_plan(int(B), int(D), int(t_in), int(stack), int(skip), C.byref(info)), "frame_stack_plan")
+    return {name: int(getattr(info, name)) for name, _ in _l.FrameStackPlanInfo._fields_}
+
+
+def frame_stack(feat, n_frames, stack, skip, out=None):
+    """feat float32 [t_in, B, D] (device, the front end's output), n_frames: its UNtruncated frame counts (python ints).  Returns
+    (out [ceil(t_in / skip), B, stack * D] device, n_out list of ceil(n / skip)): `stack` consecutive frames concatenated, every
+    `skip`-th kept, zero from a row's own length on (amdspeech.h: amdspeech_frame_stack)."""
+    _chk_f32(feat, out)
+    if feat.dim() != 3:
+        raise ValueError("frame_stack: expected [t_in, B, D], got %s" % (tuple(feat.shape),))
+    lib = _l.load()
+    t_in, B, D = feat.shape
+    if len(n_frames) != B:
+        raise ValueError("frame_stack: %d lengths for %d rows" % (len(n_frames), B))
+    plan = frame_stack_plan(B, D, t_in, stack, skip)
+    if out is None:
+        out = torch.empty(plan["t_out"], B, plan["d_out"], device=feat.device, dtype=torch.float32)
+    elif tuple(out.shape) != (plan["t_out"], B, plan["d_out"]):
+        raise ValueError("frame_stack: out is %s, expected %s" % (tuple(out.shape), (plan["t_out"], B, plan["d_out"])))
+    nf = (C.c_int * B)(*[int(v) for v in n_frames])
+    no = (C.c_int * B)()
+    _l.check(lib.amdspeech_frame_stack(_stream(), _p(feat), nf, B, D, t_in, int(stack), int(skip), _p(out), no), "frame_stack")
+    return out, list(no)          # stream-ordered; the lengths were kernel arguments (or the call has waited)

@@ -42,11 +42,7 @@ def main():
     if grp.rank == 0:
         hyper_params = hyperparams.HyperParameterHandler(prog_params["config_file"]).get_hyper_params()
     hyper_params = grp.broadcast_object(hyper_params)
-    audio_processor = audioprocessor.AudioProcessor(hyper_params["max_input_seq_length"],
-                                                    hyper_params["signal_processing"],
-                                                    n_mfcc=hyper_params.get("n_mfcc", 20),
-                                                    load_sr=hyper_params.get("sample_rate", 22050))
-    hyper_params["input_dim"] = audio_processor.feature_size
+    audio_processor = build_audio_processor(hyper_params)
     speech_reco = SpeechRecognizer(hyper_params["language"])
     hyper_params["char_map"] = speech_reco.get_char_map()
     hyper_params["char_map_length"] = speech_reco.get_char_map_length()
@@ -82,24 +78,56 @@ def main():
         sys.exit("mode not supported by the MI355X build (see module docstring)")
 
 
-def build_acoustic_training_rnn(sess, hyper_params, prog_params, train_set, test_set):
-    model = AcousticModel(hyper_params["num_layers"], hyper_params["hidden_size"], hyper_params["batch_size"],
-                          hyper_params["max_input_seq_length"], hyper_params["max_target_seq_length"],
-                          hyper_params["input_dim"], hyper_params["batch_normalization"],
-                          hyper_params["char_map_length"])
-    ds_args = (hyper_params["batch_size"], hyper_params["max_input_seq_length"],
-               hyper_params["max_target_seq_length"], hyper_params["signal_processing"], hyper_params["char_map"])
+def build_audio_processor(hyper_params):
+    """The front end of every mode, from the config keys; fills in what the model is built from.  Low frame rate input (frame_stack /
+    frame_skip): the model reads input_dim = frame_stack * D values per frame and runs out_seq_length = ceil(max_input_seq_length /
+    frame_skip) frames; at 1 / 1 these are the feature width and max_input_seq_length themselves."""
+    audio_processor = audioprocessor.AudioProcessor(hyper_params["max_input_seq_length"],
+                                                    hyper_params["signal_processing"],
+                                                    n_mfcc=hyper_params.get("n_mfcc", 20),
+                                                    load_sr=hyper_params.get("sample_rate", 22050),
+                                                    frame_stack=hyper_params.get("frame_stack", 1),
+                                                    frame_skip=hyper_params.get("frame_skip", 1))
+    hyper_params["input_dim"] = audio_processor.feature_size
+    hyper_params["out_seq_length"] = audio_processor.out_seq_length
+    if hyper_params["out_seq_length"] < hyper_params["max_target_seq_length"]:
+        logging.warning("out_seq_length %d (max_input_seq_length %d at frame_skip %d) is below max_target_seq_length %d: "
+                        "a transcript with more tokens than its utterance has frames is ignored by the loss",
+                        hyper_params["out_seq_length"], hyper_params["max_input_seq_length"],
+                        hyper_params.get("frame_skip", 1), hyper_params["max_target_seq_length"])
+    return audio_processor
+
+
+def _model_length(hyper_params):
+    """Frames the model runs: max_input_seq_length in source frames, divided by frame_skip (rounded up)."""
+    return hyper_params.get("out_seq_length", -(-hyper_params["max_input_seq_length"] // hyper_params.get("frame_skip", 1)))
+
+
+def _set_model_options(model, hyper_params):
     model.precision = hyper_params.get("precision", "f32")
     model.bidirectional = hyper_params.get("bidirectional", False)
     model.bidirectional_mode = hyper_params.get("bidirectional_mode", "top")
     model.sync_batch_norm = hyper_params.get("sync_batch_norm", False)
+    model.frame_stack = hyper_params.get("frame_stack", 1)
+    model.frame_skip = hyper_params.get("frame_skip", 1)
+
+
+def build_acoustic_training_rnn(sess, hyper_params, prog_params, train_set, test_set):
+    model = AcousticModel(hyper_params["num_layers"], hyper_params["hidden_size"], hyper_params["batch_size"],
+                          _model_length(hyper_params), hyper_params["max_target_seq_length"],
+                          hyper_params["input_dim"], hyper_params["batch_normalization"],
+                          hyper_params["char_map_length"])
+    ds_args = (hyper_params["batch_size"], hyper_params["max_input_seq_length"],
+               hyper_params["max_target_seq_length"], hyper_params["signal_processing"], hyper_params["char_map"])
+    _set_model_options(model, hyper_params)
     model.train_decoder = hyper_params.get("train_decoder", "beam")
     model.train_decoder_lag = hyper_params.get("train_decoder_lag", 1)
     if hyper_params["dataset_size_ordering"] == "Bucketed":
         train_set[:] = bucketed_order(train_set, hyper_params["batch_size"])
     pipe = dict(n_mfcc=hyper_params.get("n_mfcc", 20), prefetch=hyper_params.get("prefetch_batches", 2),
                 feature_cache_mb=hyper_params.get("feature_cache_mb", 0),
-                sample_rate=hyper_params.get("sample_rate", 22050))
+                sample_rate=hyper_params.get("sample_rate", 22050),
+                frame_stack=hyper_params.get("frame_stack", 1), frame_skip=hyper_params.get("frame_skip", 1))
     train_dataset = model.build_dataset(train_set, *ds_args, **pipe)
     test_dataset = model.build_dataset(test_set, *ds_args, **pipe)
     t_iterator, v_iterator = model.add_datasets_input(train_dataset, test_dataset)
@@ -206,13 +234,10 @@ def _train_loop(model, sess, t_iterator, v_iterator, train_set, test_set, hp, pr
 
 def _forward_model(hyper_params, batch_size):
     model = AcousticModel(hyper_params["num_layers"], hyper_params["hidden_size"], batch_size,
-                          hyper_params["max_input_seq_length"], hyper_params["max_target_seq_length"],
+                          _model_length(hyper_params), hyper_params["max_target_seq_length"],
                           hyper_params["input_dim"], hyper_params["batch_normalization"],
                           hyper_params["char_map_length"])
-    model.precision = hyper_params.get("precision", "f32")
-    model.bidirectional = hyper_params.get("bidirectional", False)
-    model.bidirectional_mode = hyper_params.get("bidirectional_mode", "top")
-    model.sync_batch_norm = hyper_params.get("sync_batch_norm", False)
+    _set_model_options(model, hyper_params)
     model.create_forward_rnn()
     model.initialize(None)
     model.restore(None, hyper_params["checkpoint_dir"] + "/acoustic/")
@@ -221,7 +246,7 @@ def _forward_model(hyper_params, batch_size):
 
 def process_file(audio_processor, hyper_params, file):
     feat_vec, original_length = audio_processor.process_audio_file(file)
-    T = hyper_params["max_input_seq_length"]
+    T = audio_processor.out_seq_length
     if original_length > T:
         logging.warning("File too long: %d frames, truncated to %d", original_length, T)
     padded = np.zeros((T, 1, feat_vec.shape[1]), np.float32)
@@ -245,10 +270,10 @@ def _transcript(prog_params):
 def align_file(audio_processor, hyper_params, file, transcript):
     """--align: when was each word of a known transcript spoken?  The restored model at batch 1, the best CTC alignment of the
     transcript's tokens to the frames (AcousticModel.align), tokens grouped into words.  Prints one line per word:
-    start_s end_s confidence word -- the times of the word's first and last frame, frame t being t * hop / sample_rate into the
-    file (the front end's 10 ms hop)."""
+    start_s end_s confidence word -- the times of the word's first and last frame, frame t being t * frame_hop_samples / sample_rate
+    into the file (the front end's 10 ms hop times frame_skip: the start of the model frame's first source frame)."""
     feat_vec, original_length = audio_processor.process_audio_file(file)
-    T = hyper_params["max_input_seq_length"]
+    T = audio_processor.out_seq_length
     if original_length > T:
         logging.warning("File too long: %d frames, truncated to %d", original_length, T)
     padded = np.zeros((T, 1, feat_vec.shape[1]), np.float32)
@@ -261,11 +286,16 @@ def align_file(audio_processor, hyper_params, file, transcript):
     tokens = model.align(None, padded, [min(original_length, T)], [ids])[0]
     if not tokens:
         sys.exit("the transcript cannot be aligned to this recording (more tokens than frames?)")
-    frame_s = audio_processor.hop_samples / float(audio_processor.load_sr)
+    frame_s = frame_seconds(audio_processor)
     words = dataprocessor.DataProcessor.group_words(char_map, tokens)
     for word, first, last, conf in words:
         print("%.3f %.3f %.3f %s" % (first * frame_s, last * frame_s, conf, word))
     return words
+
+
+def frame_seconds(audio_processor):
+    """Seconds between the starts of two model frames: what --align multiplies a frame index by."""
+    return audio_processor.frame_hop_samples / float(audio_processor.load_sr)
 
 
 def evaluate(hyper_params):
