@@ -649,6 +649,60 @@ int amdspeech_frame_stack(void* stream, const float* x, const int* n_frames, int
                           float* out, int* n_out);
 int amdspeech_frame_stack_plan(int B, int D, int t_in, int stack, int skip, amdspeech_frame_stack_plan_info* out);
 
+/* ------------------------------------------------------------ SpecAugment ----
+ * Frequency and time masks on a training mini-batch's features, IN PLACE, between the front end (or the frame stacking) and the
+ * model (no reference counterpart: an opt-in deviation; time warping and speed perturbation are not part of it).  The input
+ * needs no gradient, so there is no backward call: the input Linear's weight gradient simply reads the masked tensor.
+ *   x        float [T][B][W]      time-major, contiguous; masked words become +0.0f, every other word keeps its bit pattern
+ *   lengths  int32 [B] (DEVICE)   frames of each row; n_b = min(lengths[b], T); a row with n_b <= 0 is not touched, and no
+ *                                 frame at or past n_b is written
+ * The policy:
+ *   period         P: channels of one source frame's frequency axis; W % P == 0 and channel c belongs to bin c % P
+ *                  (fbank: 40, so a mel bin is masked in the static, delta and delta-delta groups together; under frame
+ *                  stacking the source frame's bin count, so a bin is masked in every stacked sub-frame; mfcc: n_mfcc).
+ *                  1 <= P <= W <= 4096
+ *   freq_masks     F frequency masks per row, 0 .. 8;   freq_width  Fw: their largest width in bins, 0 .. P
+ *   time_masks     M time masks per row, 0 .. 16;       time_width  Tw: their largest width in frames, >= 0
+ *   time_permille  0 .. 1000: no time mask is wider than n_b * time_permille / 1000 frames (integer division)
+ *   seed           64 bits
+ * The draws, in integer arithmetic only (the host, the device and a restatement in another language agree exactly):
+ *   r(stream, idx) = mix32(mix32(idx ^ lo32(seed)) + stream * 0x9e3779b9 + hi32(seed)) >> 8          (24 bits),
+ *   mix32(v): v ^= v >> 16; v *= 0x7feb352d; v ^= v >> 15; v *= 0x846ca68b; v ^= v >> 16    (32-bit wrap-around)
+ *   mask m of row b: idx = b * 64 + m, stream = 0x5A000000 + 2 * kind + which (kind 0 frequency, 1 time; which 0 width, 1 start)
+ *   wmax   = kind == 0 ? min(Fw, P) : min(Tw, n_b * time_permille / 1000)        extent = kind == 0 ? P : n_b
+ *   width  = (r(width stream, idx) * (wmax + 1)) >> 24                 0 .. wmax             (64-bit products)
+ *   start  = (r(start stream, idx) * (extent - width + 1)) >> 24       0 .. extent - width
+ * Element (t, b, c) with t < n_b becomes +0.0f when c % P lies in a frequency span of row b or t lies in a time span of row b.
+ * The kernel is write-only: it reads the lengths and its arguments and stores zeros to the masked words; it loads nothing from x.
+ * Asynchronous on `stream`, no host copy, no synchronisation.  When neither kind can mask anything (F or Fw is 0, and M, Tw or
+ * time_permille is 0) nothing is launched.
+ * AMDSPEECH_EINVAL with a message: null pointers, non-positive T or B (or T * B >= 2^31), W outside 1 .. 4096, a period outside 1 .. W or one that
+ * does not divide W, F outside 0 .. 8, M outside 0 .. 16, Fw outside 0 .. P, a negative Tw, time_permille outside 0 .. 1000.
+ * amdspeech_spec_augment_spans: the spans of one row as the kernel draws them (host arithmetic, the same function the kernel
+ * calls): 2 * (F + M) ints, (start, width) pairs, the F frequency masks first; `n` is the row's n_b (>= 0; period, not W,
+ * bounds the frequency spans, so no W is passed and the period is only checked against 1 .. 4096).
+ * amdspeech_spec_augment_plan: the launch geometry as plain numbers, a READ-ONLY view of the plan the launch itself reads (one
+ * function decides for both); no device is needed, the shape and the policy are checked as the call checks them.
+ *   vec                 words per store of a time-masked frame: 4 when W % 4 == 0 (the query assumes a 16-byte aligned x; the
+ *                       call plans with 1 when x is not), else 1.  Frequency spans start at any word: single-word stores
+ *   lanes               threads that share one (frame, row) item: the smallest power of two that covers the W / vec stores of a
+ *                       whole frame at 4 stores per lane, at most 256
+ *   items_per_workgroup 256 / lanes
+ *   workgroups          of 256 threads, at most 2048 (the grid strides over the T * B items); 0 = nothing is launched
+ *   reps                W / period                                                                                         */
+typedef struct amdspeech_spec_augment_desc {
+    int period, freq_masks, freq_width, time_masks, time_width, time_permille;
+    unsigned long long seed;
+} amdspeech_spec_augment_desc;
+typedef struct amdspeech_spec_augment_plan_info {
+    int vec, lanes, items_per_workgroup, workgroups, reps;
+} amdspeech_spec_augment_plan_info;
+int amdspeech_spec_augment(void* stream, float* x, const int* lengths, int T, int B, int W,
+                           const amdspeech_spec_augment_desc* desc);
+int amdspeech_spec_augment_spans(const amdspeech_spec_augment_desc* desc, int row, int n, int* spans);
+int amdspeech_spec_augment_plan(int T, int B, int W, const amdspeech_spec_augment_desc* desc,
+                                amdspeech_spec_augment_plan_info* out);
+
 /* ------------------------------------------------------------- profiling ----
  * Optional HIP-event timing of the recurrence kernels (no reference counterpart;
  * feeds bench.py's roofline line).  When enabled, lstm_fwd / lstm_bwd bracket

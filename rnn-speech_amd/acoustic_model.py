@@ -505,6 +505,10 @@ class AcousticModel(object):
         # with the MODEL length (AudioProcessor.out_seq_length) and input_dim = AudioProcessor.feature_size; evaluate_full builds
         # its AudioProcessor from them
         self.frame_stack = self.frame_skip = 1
+        # config keys `spec_augment_*`: SpecAugment on TRAINING mini-batches (ops.spec_augment).  None (off: nothing is launched or
+        # cloned) or a dict with ops.SPEC_AUGMENT_KEYS and "seed" (the config's spec_augment_seed); `period` is the source frame's
+        # bin count.  Applied in run_step when gradients are computed; evaluation, process_input, align and evaluate_full never mask
+        self.spec_augment = None
         self.sync_batch_norm = False       # config key `sync_batch_norm`: data-parallel batch-norm moments over ALL ranks (deviation)
         self.save_tf_bundle = False        # also write <stem>.index / .data-00000-of-00001 on save()
         self.save_optimizer_state = True   # native .npz also carries Adam m/v/step and the RNN state
@@ -763,6 +767,13 @@ class AcousticModel(object):
         x = x.to(dev, torch.float32).contiguous()
         return x, torch.as_tensor(lengths, dtype=torch.int32).to(dev), torch.as_tensor(dense, dtype=torch.int32).to(dev)
 
+    def _spec_augment_seed(self):
+        """The 64-bit seed of this mini-batch's masks: the config's seed plus the data-parallel rank in the high word (ranks mask
+        differently), the mini-batch counter -- the dropout seed -- times an odd constant in the low word (the draw mixes
+        idx ^ lo32(seed): consecutive counters must not alias neighbouring idx values).  The same for a time-out repeat."""
+        rank = dataparallel.current().rank
+        return ((int(self.spec_augment.get("seed", 0)) + rank) << 32) | ((self._dropout_seed * 0x9E3779B1) & 0xFFFFFFFF)
+
     # ---- step orchestration (:634-703, :887-939) -----------------------------------
     @_engine_stream
     def start_batch(self, session, is_training, run_options=None, run_metadata=None):
@@ -776,11 +787,21 @@ class AcousticModel(object):
     @_engine_stream
     def run_step(self, session, compute_gradients=True, run_options=None, run_metadata=None):
         start = time.time()
+        fed = self._placeholder_batch is not None
         inputs, lengths, dense = self._next_batch()          # may raise OutOfRangeError
         x, dlen, dlab = self._to_device(inputs, lengths, dense)
         eng = self.engine
         keep = (self.input_keep_prob, self.output_keep_prob) if compute_gradients else (1.0, 1.0)
         self._dropout_seed += 1
+        if self.spec_augment is not None and compute_gradients:
+            # SpecAugment, in place on this stream, once: a time-out repeat below reuses the masked x.  No tensor a caller can
+            # reach is written: _to_device hands a contiguous float32 device tensor back as it is, so one that came through feed()
+            # is cloned first.  A dataset's mini-batch needs no clone: AcousticDataset.batches() makes a fresh tensor for every
+            # mini-batch (front end, frame stacking or _assemble), DatasetIterator.get_next() hands each out once, and the feature
+            # cache keeps host copies taken before the batch is yielded
+            if fed and torch.is_tensor(inputs) and x.data_ptr() == inputs.data_ptr():
+                x = x.clone()
+            ops.spec_augment(x, dlen, self.spec_augment, self._spec_augment_seed())
         marks = [] if self.timeline_enabled else None
         use_async = self.compute_error_rate and self.train_decoder == "beam" and compute_gradients
         if self._async_beam is not None:                      # (this forward pass overwrites the logits a copy may still read)

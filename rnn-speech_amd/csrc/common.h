@@ -137,7 +137,7 @@ int ctc_prepare_targets(hipStream_t s, const int* dense_labels, const int* lengt
 
 // Counter-based dropout multiplier shared by the LSTM kernels: returns
 // mask/keep for element `idx` of stream (`seed`, `tensor`).
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
+__host__ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
     x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
     return x;
 }
@@ -145,6 +145,13 @@ __device__ __forceinline__ float uniform01(uint64_t seed, uint32_t tensor, uint3
     uint32_t a = mix32(idx ^ (uint32_t)seed);
     uint32_t b = mix32(a + tensor * 0x9e3779b9U + (uint32_t)(seed >> 32));
     return (float)(b >> 8) * (1.0f / 16777216.0f);
+}
+// The 24-bit integer that uniform01 converts to float, for draws that must be the same number on the host and on the device
+// (spec_augment.hip: mask widths and starts in integer arithmetic only).
+__host__ __device__ __forceinline__ uint32_t random24(uint64_t seed, uint32_t stream, uint32_t idx) {
+    uint32_t a = mix32(idx ^ (uint32_t)seed);
+    uint32_t b = mix32(a + stream * 0x9e3779b9U + (uint32_t)(seed >> 32));
+    return b >> 8;
 }
 
 }  // namespace amdspeech

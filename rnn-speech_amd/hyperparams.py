@@ -1,6 +1,6 @@
 """config.ini reader + checkpoint-side pickle logic (reference:
 /root/reference/util/hyperparams.py:17-141).  Same section/key names and defaults; a few
-optional keys are added for the MI355X build (n_mfcc, sample_rate, frame_stack / frame_skip ...)."""
+optional keys are added for the MI355X build (n_mfcc, sample_rate, frame_stack / frame_skip, spec_augment_* ...)."""
 import configparser
 import logging
 import os
@@ -72,6 +72,18 @@ def read_config_file(config_file):
     if d["train_decoder"] not in ("greedy", "beam"):
         raise ValueError("train_decoder must be 'greedy' or 'beam', not %r" % d["train_decoder"])
     d["train_decoder_lag"] = cp.getint(_TRAINING, "train_decoder_lag", fallback=1)
+    # SpecAugment on training mini-batches (ops.spec_augment): masks per utterance and their largest widths, in mel / cepstral bins
+    # and in model frames; no time mask is wider than spec_augment_time_ratio of its utterance.  All 0: off.  NOT structural: the
+    # keys change the training data, not the model, and a checkpoint stays usable when they change
+    for key, top in (("spec_augment_freq_masks", 8), ("spec_augment_freq_width", 4096), ("spec_augment_time_masks", 16),
+                     ("spec_augment_time_width", 2 ** 31 - 1), ("spec_augment_seed", 2 ** 32 - 1)):
+        d[key] = cp.getint(_TRAINING, key, fallback=0)
+        if not 0 <= d[key] <= top:
+            raise ValueError("%s must be in 0 .. %d, not %r" % (key, top, d[key]))
+    ratio = cp.getfloat(_TRAINING, "spec_augment_time_ratio", fallback=1.0)
+    if not 0.0 <= ratio <= 1.0:          # (a NaN fails both comparisons)
+        raise ValueError("spec_augment_time_ratio must be in 0 .. 1, not %r" % ratio)
+    d["spec_augment_time_permille"] = int(round(1000 * ratio))
     return d
 
 

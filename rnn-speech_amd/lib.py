@@ -56,6 +56,15 @@ class FrameStackPlanInfo(C.Structure):     # amdspeech_frame_stack_plan_info (in
     _fields_ = [(n, C.c_int) for n in ("t_out", "d_out", "vec", "workgroups", "meta_by_copy")]
 
 
+class SpecAugmentDesc(C.Structure):     # amdspeech_spec_augment_desc (include/amdspeech.h): the masking policy and the seed of one call
+    _fields_ = [(n, C.c_int) for n in ("period", "freq_masks", "freq_width", "time_masks", "time_width", "time_permille")] + \
+               [("seed", C.c_uint64)]
+
+
+class SpecAugmentPlanInfo(C.Structure):     # amdspeech_spec_augment_plan_info (include/amdspeech.h): the launch geometry of a masking call, read-only
+    _fields_ = [(n, C.c_int) for n in ("vec", "lanes", "items_per_workgroup", "workgroups", "reps")]
+
+
 GEMM_FAMILIES = ("skinny_n", "skinny_k", "skinny_tn", "tn_direct", "kc_direct", "lds", "bf3", "bf16p")      # AMDSPEECH_GEMM_* (include/amdspeech.h)
 GEMM_MAP_LINEAR, GEMM_MAP_XCD, GEMM_MAP_XCD_BLOCKS, GEMM_MAP_KC_BAND = range(4)      # AMDSPEECH_GEMM_MAP_*
 GEMM_GROUP_MAX = 10                                                                 # AMDSPEECH_GEMM_GROUP_MAX
@@ -152,6 +161,9 @@ PROTOTYPES = {
     "amdspeech_frame_stack_num_frames": (_I, [_I, _I]),
     "amdspeech_frame_stack": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "amdspeech_frame_stack_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(FrameStackPlanInfo)]),
+    "amdspeech_spec_augment": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(SpecAugmentDesc)]),
+    "amdspeech_spec_augment_spans": (_I, [C.POINTER(SpecAugmentDesc), _I, _I, C.POINTER(C.c_int)]),
+    "amdspeech_spec_augment_plan": (_I, [_I, _I, _I, C.POINTER(SpecAugmentDesc), C.POINTER(SpecAugmentPlanInfo)]),
     "amdspeech_profile_enable": (_I, [_I]),
     "amdspeech_profile_get": (_I, [_I, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "amdspeech_profile_get_flops": (_I, [_I, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

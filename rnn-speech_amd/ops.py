@@ -968,3 +968,55 @@ def frame_stack(feat, n_frames, stack, skip, out=None):
     no = (C.c_int * B)()
     _l.check(lib.amdspeech_frame_stack(_stream(), _p(feat), nf, B, D, t_in, int(stack), int(skip), _p(out), no), "frame_stack")
     return out, list(no)          # stream-ordered; the lengths were kernel arguments (or the call has waited)
+
+
+# ------------------------------------------------------------ SpecAugment
+SPEC_AUGMENT_KEYS = ("period", "freq_masks", "freq_width", "time_masks", "time_width", "time_permille")
+
+
+def _spec_augment_desc(policy, seed):
+    """policy: a mapping with SPEC_AUGMENT_KEYS (amdspeech.h: amdspeech_spec_augment_desc); seed: 64 bits."""
+    missing = [k for k in SPEC_AUGMENT_KEYS if k not in policy]
+    if missing:
+        raise ValueError("spec_augment: the policy lacks %s" % ", ".join(missing))
+    return _l.SpecAugmentDesc(*[int(policy[k]) for k in SPEC_AUGMENT_KEYS], int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def spec_augment_plan(T, B, W, policy, seed=0):
+    """The launch geometry of `spec_augment` for a shape and a policy (amdspeech.h: amdspeech_spec_augment_plan), as a dict of ints;
+    workgroups == 0: nothing would be launched.  Read-only: no device is needed.  What the call refuses raises here too."""
+    info = _l.SpecAugmentPlanInfo()
+    desc = _spec_augment_desc(policy, seed)
+    _l.check(_l.load().amdspeech_spec_augment_plan(int(T), int(B), int(W), C.byref(desc), C.byref(info)), "spec_augment_plan")
+    return {name: int(getattr(info, name)) for name, _ in _l.SpecAugmentPlanInfo._fields_}
+
+
+def spec_augment_spans(policy, seed, row, n):
+    """The masks the library draws for row `row` with n = min(length, T) frames under (policy, seed), as (start, width) pairs: the
+    policy's freq_masks frequency spans (in bins of the period) first, then its time_masks time spans (in frames).  Host arithmetic."""
+    desc = _spec_augment_desc(policy, seed)
+    count = max(int(policy["freq_masks"]), 0) + max(int(policy["time_masks"]), 0)
+    out = (C.c_int * (2 * max(count, 1)))()
+    _l.check(_l.load().amdspeech_spec_augment_spans(C.byref(desc), int(row), int(n), out), "spec_augment_spans")
+    return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(count)]
+
+
+def spec_augment(x, lengths, policy, seed):
+    """x float32 [T, B, W] (device, contiguous), lengths int32 [B] ON THE DEVICE.  Masks x IN PLACE and returns it: frequency and
+    time spans of every row's first min(length, T) frames become +0.0, every other word keeps its bit pattern (amdspeech.h:
+    amdspeech_spec_augment).  Stream-ordered, no copy, no synchronisation; a policy that can mask nothing launches nothing."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+        raise ValueError("spec_augment: expected a contiguous float32 device tensor [T, B, W], got %s"
+                         % ((x.dtype, x.device, tuple(x.shape), x.stride()) if torch.is_tensor(x) else type(x),))
+    T, B, W = x.shape
+    if not (torch.is_tensor(lengths) and lengths.is_cuda and lengths.device == x.device and lengths.dtype == torch.int32
+            and tuple(lengths.shape) == (B,) and lengths.is_contiguous()):
+        raise ValueError("spec_augment: lengths must be an int32 device tensor [%d] beside x" % B)
+    desc = _spec_augment_desc(policy, seed)
+    lib = _l.load()
+    info = _l.SpecAugmentPlanInfo()
+    _l.check(lib.amdspeech_spec_augment_plan(T, B, W, C.byref(desc), C.byref(info)), "spec_augment")
+    if info.workgroups == 0:
+        return x
+    _l.check(lib.amdspeech_spec_augment(_stream(), _p(x), _p(lengths), T, B, W, C.byref(desc)), "spec_augment")
+    return x

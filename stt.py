@@ -90,12 +90,30 @@ def build_audio_processor(hyper_params):
                                                     frame_skip=hyper_params.get("frame_skip", 1))
     hyper_params["input_dim"] = audio_processor.feature_size
     hyper_params["out_seq_length"] = audio_processor.out_seq_length
+    hyper_params["spec_augment"] = spec_augment_policy(hyper_params, audio_processor)
     if hyper_params["out_seq_length"] < hyper_params["max_target_seq_length"]:
         logging.warning("out_seq_length %d (max_input_seq_length %d at frame_skip %d) is below max_target_seq_length %d: "
                         "a transcript with more tokens than its utterance has frames is ignored by the loss",
                         hyper_params["out_seq_length"], hyper_params["max_input_seq_length"],
                         hyper_params.get("frame_skip", 1), hyper_params["max_target_seq_length"])
     return audio_processor
+
+
+def spec_augment_policy(hyper_params, audio_processor):
+    """AcousticModel.spec_augment from the spec_augment_* keys: None when they mask nothing (the default: nothing is launched),
+    else the policy of ops.spec_augment plus the seed.  period: the bins of ONE source frame's frequency axis -- 40 mel bins for
+    fbank (a bin is masked in the static, delta and delta-delta groups together), n_mfcc for mfcc; under frame_stack the same bin
+    is masked in every stacked sub-frame."""
+    get = lambda key, dflt=0: hyper_params.get("spec_augment_" + key, dflt)      # noqa: E731
+    freq_on = get("freq_masks") > 0 and get("freq_width") > 0
+    time_on = get("time_masks") > 0 and get("time_width") > 0 and get("time_permille", 1000) > 0
+    if not (freq_on or time_on):
+        return None
+    period = 40 if audio_processor.feature_type == "fbank" else audio_processor.source_feature_size
+    if get("freq_width") > period:
+        raise ValueError("spec_augment_freq_width %d exceeds the %d bins of a frame" % (get("freq_width"), period))
+    return dict(period=period, freq_masks=get("freq_masks"), freq_width=get("freq_width"), time_masks=get("time_masks"),
+                time_width=get("time_width"), time_permille=get("time_permille", 1000), seed=get("seed"))
 
 
 def _model_length(hyper_params):
@@ -110,6 +128,7 @@ def _set_model_options(model, hyper_params):
     model.sync_batch_norm = hyper_params.get("sync_batch_norm", False)
     model.frame_stack = hyper_params.get("frame_stack", 1)
     model.frame_skip = hyper_params.get("frame_skip", 1)
+    model.spec_augment = hyper_params.get("spec_augment")       # (build_audio_processor; only run_step with gradients masks)
 
 
 def build_acoustic_training_rnn(sess, hyper_params, prog_params, train_set, test_set):
