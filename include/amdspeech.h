@@ -703,6 +703,66 @@ int amdspeech_spec_augment_spans(const amdspeech_spec_augment_desc* desc, int ro
 int amdspeech_spec_augment_plan(int T, int B, int W, const amdspeech_spec_augment_desc* desc,
                                 amdspeech_spec_augment_plan_info* out);
 
+/* ---------------------------------------------------- feature normalisation ---
+ * Cepstral mean and variance normalisation of the front end's features, IN PLACE, between the front end and the frame stacking
+ * (no reference counterpart: an opt-in deviation, off in mode 0, where no caller makes this call).  The input needs no gradient,
+ * so there is no backward call.
+ *   x         float [t_in][B][D]   the front end's `feat`, time-major, contiguous; D <= 4096
+ *   n_frames  int32 [B] (HOST)     the front end's UNtruncated frame counts; n = min(n_frames[b], t_in)
+ * For row b and dim d, over the frames t < n only:
+ *   mean = (1/n) sum x[t][b][d]        var = (1/n) sum (x[t][b][d] - mean)^2        (the POPULATION variance)
+ *   x[t][b][d] = float((double(x[t][b][d]) - mean) * scale),    scale = norm_vars ? 1 / sqrt(max(var, var_floor)) : 1
+ * Frames at or past n are neither read nor written; a row with n = 0 is not touched; a row with n = 1 becomes zeros.  A constant
+ * dim has var = 0 and x - mean = 0 exactly: it comes out as exact zeros.
+ * Modes (amdspeech_feature_norm_desc.mode):
+ *   AMDSPEECH_FEATURE_NORM_NONE       nothing is launched
+ *   AMDSPEECH_FEATURE_NORM_UTTERANCE  mean and var of the row itself
+ *   AMDSPEECH_FEATURE_NORM_GLOBAL     one (mean[d], scale[d]) for all rows from `table`, double [2][D] on the DEVICE (mean first);
+ *                                     norm_vars and var_floor are then already folded into the table and are not read
+ * The arithmetic (utterance mode): accumulation is in float64, shifted by the row's own first frame K[d] = x[0][b][d]:
+ *   S' = sum (x - K),  Q' = sum (x - K)^2,  mean = K + S'/n,  var = max(Q'/n - (S'/n)^2, 0)
+ * The shift is the same for every time slice of a row, so the partial sums of the `split` workgroups of a row add directly; it
+ * makes a constant dim exactly zero-variance and keeps the single pass accurate when |mean| >> std.  scale is formed in float64;
+ * the result is rounded to float ONCE.  No atomics: partial sums are combined in a fixed order, two calls give the same bits.
+ * Global mode performs the same two float64 operations and the one rounding on the table's values: bit for bit
+ * float32((float64(x) - mean) * scale).
+ * Asynchronous on `stream`; the lengths travel as kernel arguments up to 256 rows, above that through a device buffer of the
+ * call's own (the call then waits for the stream before it returns).
+ *   workspace  device, amdspeech_feature_norm_plan_info.workspace_bytes of the UTTERANCE plan (8-byte aligned), caller-allocated;
+ *              may be NULL in global mode.  Per row: `split` partials double [2][D] (S', Q') and the row's K double [D]
+ * amdspeech_feature_moments: the same sums, finished per row instead of applied -- moments is a device double [B][2][D] holding
+ * mean and M2 = sum (x - mean)^2 (zeros for n = 0); x is not written.  The building block of corpus statistics: rows merge on the
+ * host with the pairwise update.  Takes the workspace of the utterance plan.
+ * AMDSPEECH_EINVAL with a message: null pointers, non-positive sizes (or t_in * B >= 2^31), D > 4096, a mode outside 0 .. 2,
+ * var_floor <= 0, NaN or infinite, a negative count, float64 buffers that are not 8-byte aligned, and -- when D is a multiple
+ * of 4 (16-byte loads and stores) -- an x that is not 16-byte aligned: such a base is REFUSED, not run with single-word accesses.
+ * amdspeech_feature_norm_plan: the launch geometry as plain numbers, a READ-ONLY view of the plan the launches themselves read (one
+ * function decides for both); no device is needed, the shape is checked as the calls check it.
+ *   vec              words per lane and access: 4 when D % 4 == 0, else 1
+ *   split            time slices per row = workgroups per row.  Chosen from t_in, B and D alone: ceil(512 / min(B, 2048)) so that a
+ *                    small batch still covers the chip, but no more than floor(t_in / (4 * slots)) -- a slice is no shorter
+ *                    than 4 passes of the 256 / lanes frame slots, lanes = the smallest power of two that covers D / vec (at
+ *                    most 256) -- and at least 1; then re-derived as ceil(t_in / ceil(t_in / split)) so that no slice is empty
+ *   workgroups       split * min(B, 2048), of 256 threads (rows beyond 2048 are strided); 0 in mode 0
+ *   lds_bytes        static LDS of either kernel: 256 * 2 * vec doubles
+ *   meta_by_copy     1 when B > 256
+ *   workspace_bytes  B * (2 * split + 1) * D * 8 in utterance mode, 0 otherwise                                              */
+#define AMDSPEECH_FEATURE_NORM_NONE 0
+#define AMDSPEECH_FEATURE_NORM_UTTERANCE 1
+#define AMDSPEECH_FEATURE_NORM_GLOBAL 2
+typedef struct amdspeech_feature_norm_desc {
+    int mode, norm_vars;
+    double var_floor;
+} amdspeech_feature_norm_desc;
+typedef struct amdspeech_feature_norm_plan_info {
+    int vec, split, workgroups, lds_bytes, meta_by_copy, workspace_bytes;
+} amdspeech_feature_norm_plan_info;
+int amdspeech_feature_norm_plan(int B, int D, int t_in, int mode, amdspeech_feature_norm_plan_info* out);
+int amdspeech_feature_moments(void* stream, const float* x, const int* n_frames, int B, int D, int t_in, void* workspace,
+                              double* moments);
+int amdspeech_feature_norm(void* stream, float* x, const int* n_frames, int B, int D, int t_in,
+                           const amdspeech_feature_norm_desc* desc, const double* table, void* workspace);
+
 /* ------------------------------------------------------------- profiling ----
  * Optional HIP-event timing of the recurrence kernels (no reference counterpart;
  * feeds bench.py's roofline line).  When enabled, lstm_fwd / lstm_bwd bracket

@@ -72,17 +72,22 @@ class AcousticDataset(object):
     later epochs skip decode, resampling and the front end altogether.
 
     frame_stack / frame_skip: low frame rate input (AudioProcessor).  max_input_seq_length stays in SOURCE frames; the batches,
-    their lengths, T and the feature cache are in MODEL frames (T = audio.out_seq_length rows of audio.feature_size values)."""
+    their lengths, T and the feature cache are in MODEL frames (T = audio.out_seq_length rows of audio.feature_size values).
+    feature_norm / feature_norm_variance / feature_stats: feature normalisation (AudioProcessor); the batches and the feature
+    cache hold normalised features."""
 
     def __init__(self, input_set, batch_size, max_input_seq_length, max_target_seq_length,
                  signal_processing, char_map, n_mfcc=20, device="cuda", prefetch=2, feature_cache_mb=0,
-                 sample_rate=22050, frame_stack=1, frame_skip=1):
+                 sample_rate=22050, frame_stack=1, frame_skip=1, feature_norm="none", feature_norm_variance=True,
+                 feature_stats=None):
         self.items = [(it[0], it[1]) for it in input_set]
         self.batch_size = batch_size
         self.U = max_target_seq_length
         self.char_map = char_map
         self.audio = AudioProcessor(max_input_seq_length, signal_processing, n_mfcc=n_mfcc, device=device,
-                                    load_sr=sample_rate, frame_stack=frame_stack, frame_skip=frame_skip)
+                                    load_sr=sample_rate, frame_stack=frame_stack, frame_skip=frame_skip,
+                                    feature_norm=feature_norm, feature_norm_variance=feature_norm_variance,
+                                    feature_stats=feature_stats)
         self.T = self.audio.out_seq_length
         self.prefetch = int(prefetch)
         self._signal_processing, self._n_mfcc = signal_processing, n_mfcc
@@ -95,7 +100,8 @@ class AcousticDataset(object):
         other = AcousticDataset(input_set, self.batch_size, self.audio.max_input_seq_length, self.U, self._signal_processing,
                                 self.char_map, n_mfcc=self._n_mfcc, device=self.audio.device, prefetch=self.prefetch,
                                 sample_rate=self.audio.load_sr, frame_stack=self.audio.frame_stack,
-                                frame_skip=self.audio.frame_skip)
+                                frame_skip=self.audio.frame_skip, feature_norm=self.audio.feature_norm,
+                                feature_norm_variance=self.audio.feature_norm_variance, feature_stats=self.audio.feature_stats)
         other._cache, other._room = self._cache, self._room
         return other
 
@@ -505,6 +511,9 @@ class AcousticModel(object):
         # with the MODEL length (AudioProcessor.out_seq_length) and input_dim = AudioProcessor.feature_size; evaluate_full builds
         # its AudioProcessor from them
         self.frame_stack = self.frame_skip = 1
+        # config keys `feature_norm` / `feature_norm_variance` / `feature_norm_stats`: feature normalisation in front of the frame
+        # stacking (AudioProcessor).  The model only reads normalised features; evaluate_full builds its AudioProcessor from these
+        self.feature_norm, self.feature_norm_variance, self.feature_stats = "none", True, None
         # config keys `spec_augment_*`: SpecAugment on TRAINING mini-batches (ops.spec_augment).  None (off: nothing is launched or
         # cloned) or a dict with ops.SPEC_AUGMENT_KEYS and "seed" (the config's spec_augment_seed); `period` is the source frame's
         # bin count.  Applied in run_step when gradients are computed; evaluation, process_input, align and evaluate_full never mask
@@ -703,12 +712,13 @@ class AcousticModel(object):
     @staticmethod
     def build_dataset(input_set, batch_size, max_input_seq_length, max_target_seq_length,
                       signal_processing, char_map, n_mfcc=20, prefetch=2, feature_cache_mb=0, sample_rate=22050,
-                      frame_stack=1, frame_skip=1):
+                      frame_stack=1, frame_skip=1, feature_norm="none", feature_norm_variance=True, feature_stats=None):
         """max_input_seq_length in SOURCE frames, whatever frame_stack / frame_skip (the dataset's T is in model frames)."""
         return AcousticDataset(input_set, batch_size, max_input_seq_length, max_target_seq_length,
                                signal_processing, char_map, n_mfcc=n_mfcc, prefetch=prefetch,
                                feature_cache_mb=feature_cache_mb, sample_rate=sample_rate,
-                               frame_stack=frame_stack, frame_skip=frame_skip)
+                               frame_stack=frame_stack, frame_skip=frame_skip, feature_norm=feature_norm,
+                               feature_norm_variance=feature_norm_variance, feature_stats=feature_stats)
 
     def add_dataset_input(self, dataset):
         self._single_iter = DatasetIterator(dataset)
@@ -1109,7 +1119,8 @@ class AcousticModel(object):
                       run_options=None, run_metadata=None, n_mfcc=20, sample_rate=22050):
         """input_seq_length: max_input_seq_length, in SOURCE frames (the model's own length is in model frames)."""
         audio = AudioProcessor(input_seq_length, signal_processing, n_mfcc=n_mfcc, load_sr=sample_rate,
-                               frame_stack=self.frame_stack, frame_skip=self.frame_skip)
+                               frame_stack=self.frame_stack, frame_skip=self.frame_skip, feature_norm=self.feature_norm,
+                               feature_norm_variance=self.feature_norm_variance, feature_stats=self.feature_stats)
         wer_list, cer_list = [], []
         feats, lens, texts = [], [], []
         B, T, D = self.batch_size, self.max_input_seq_length, audio.feature_size

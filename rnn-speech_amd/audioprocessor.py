@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .feature_norm import MODES, FeatureStats, describe_processor
 
 FRAME_STRIDE = 0.01
 FRAME_SIZE = 0.025
@@ -17,7 +18,7 @@ DEFAULT_LOAD_SR = 22050   # librosa.load default used by the reference's file pa
 
 class AudioProcessor(object):
     def __init__(self, max_input_seq_length, feature_type="mfcc", n_mfcc=20, device="cuda", load_sr=DEFAULT_LOAD_SR,
-                 frame_stack=1, frame_skip=1):
+                 frame_stack=1, frame_skip=1, feature_norm="none", feature_norm_variance=True, feature_stats=None):
         """feature_type: 'mfcc' (n_mfcc-dim, reference default 20) or 'fbank' (120-dim).  load_sr: the rate audio
         FILES are resampled to before feature extraction (config.ini `sample_rate`; the reference's librosa.load
         default, 22,050 Hz) -- set it to the corpus rate (16,000 for LibriSpeech) to skip resampling.
@@ -25,7 +26,11 @@ class AudioProcessor(object):
         frames are concatenated into one MODEL frame and every `frame_skip`-th one is kept (ops.frame_stack).
         max_input_seq_length stays in SOURCE frames (audio is truncated as without the option); what the process_* calls return
         is out_seq_length = ceil(max_input_seq_length / frame_skip) model frames of feature_size = frame_stack * D values, and
-        lengths of ceil(n / frame_skip)."""
+        lengths of ceil(n / frame_skip).
+        feature_norm ("none": the reference's behaviour | "utterance" | "global"): mean (and, with feature_norm_variance, variance)
+        normalisation of the SOURCE frames on the GPU, between the front end and the frame stacking (ops.feature_norm) -- over the
+        frames of the utterance that survive the truncation, or with the corpus statistics in feature_stats (a FeatureStats or the
+        path of the file `stt.py --feature_stats` wrote; a file taken from other features is refused)."""
         self.max_input_seq_length = max_input_seq_length
         self.load_sr = int(load_sr)
         self.feature_type = feature_type
@@ -47,6 +52,19 @@ class AudioProcessor(object):
         if self.feature_size > 4096:
             raise ValueError("frame_stack * feature width = %d exceeds 4096" % self.feature_size)
         self.out_seq_length = -(-int(max_input_seq_length) // self.frame_skip)
+        if feature_norm not in MODES:
+            raise ValueError("feature_norm must be one of %s, not %r" % (", ".join(MODES), feature_norm))
+        self.feature_norm, self.feature_norm_variance = feature_norm, bool(feature_norm_variance)
+        self.feature_stats, self._norm_tables = None, {}
+        if feature_norm == "global":
+            if feature_stats is None:
+                raise ValueError("feature_norm 'global' needs feature_stats (the file `stt.py --feature_stats` writes)")
+            expect = describe_processor(self)
+            if not isinstance(feature_stats, FeatureStats):
+                feature_stats = FeatureStats.load(feature_stats, expect)
+            elif feature_stats.description != expect:
+                raise ValueError("feature_stats holds statistics of %r, the processor computes %r" % (feature_stats.description, expect))
+            self.feature_stats = feature_stats
         # samples between the starts of two frames (csrc/frontend.hip: 10 ms, rounded half to even, in both modes): frame t of a
         # file starts t * hop_samples / load_sr seconds in
         self.hop_samples = int(round(self.load_sr * 0.01))
@@ -102,8 +120,21 @@ class AudioProcessor(object):
             return int(t_max)
         return max(1, min((int(t_max) - 1) * self.frame_skip + self.frame_stack, self.max_input_seq_length))
 
+    def _normalised(self, feat, lengths):
+        """Feature normalisation of the front end's [t_in, B, D] tensor, in place; "none": nothing is launched."""
+        if self.feature_norm == "none":
+            return
+        table = None
+        if self.feature_norm == "global":
+            table = self._norm_tables.get(feat.device)
+            if table is None:
+                table = self._norm_tables[feat.device] = self.feature_stats.table(self.feature_norm_variance, device=feat.device)
+        ops.feature_norm(feat, lengths, self.feature_norm, self.feature_norm_variance, table=table)
+
     def _stacked(self, feat, lengths, t_max):
-        """Low frame rate input behind the front end; at (1, 1) the front end's own tensor, no copy and no launch."""
+        """Feature normalisation, then low frame rate input, behind the front end; with both off the front end's own tensor, no
+        copy and no launch."""
+        self._normalised(feat, lengths)
         if self.frame_stack == 1 and self.frame_skip == 1:
             return feat, lengths
         out, n_out = ops.frame_stack(feat, lengths, self.frame_stack, self.frame_skip)

@@ -1,6 +1,6 @@
 """config.ini reader + checkpoint-side pickle logic (reference:
 /root/reference/util/hyperparams.py:17-141).  Same section/key names and defaults; a few
-optional keys are added for the MI355X build (n_mfcc, sample_rate, frame_stack / frame_skip, spec_augment_* ...)."""
+optional keys are added for the MI355X build (n_mfcc, sample_rate, frame_stack / frame_skip, feature_norm*, spec_augment_* ...)."""
 import configparser
 import logging
 import os
@@ -10,11 +10,12 @@ import time
 _ACOUSTIC, _GENERAL, _TRAINING, _LOGGING = "acoustic_network_params", "general", "training", "logging"
 # a change of any of these makes an existing checkpoint unusable (the reference compares the first four,
 # util/hyperparams.py:75-92; n_mfcc / sample_rate are this build's extra keys and change the input layer's
-# shape / the features' meaning; so do frame_stack / frame_skip, the low frame rate input)
+# shape / the features' meaning; so do frame_stack / frame_skip, the low frame rate input, and feature_norm /
+# feature_norm_variance: a model trained on normalised features is useless on raw ones.  The statistics file's path is not)
 _STRUCTURAL = ("num_layers", "hidden_size", "signal_processing", "language", "n_mfcc", "sample_rate", "bidirectional",
-               "bidirectional_mode", "frame_stack", "frame_skip")
+               "bidirectional_mode", "frame_stack", "frame_skip", "feature_norm", "feature_norm_variance")
 _STRUCTURAL_DEFAULTS = {"signal_processing": "mfcc", "language": "", "n_mfcc": 20, "sample_rate": 22050, "bidirectional": False,
-                        "bidirectional_mode": "top", "frame_stack": 1, "frame_skip": 1}
+                        "bidirectional_mode": "top", "frame_stack": 1, "frame_skip": 1, "feature_norm": "none", "feature_norm_variance": True}
 
 
 def read_config_file(config_file):
@@ -65,6 +66,16 @@ def read_config_file(config_file):
         d[key] = cp.getint(_ACOUSTIC, key, fallback=1)
         if not 1 <= d[key] <= 16:
             raise ValueError("%s must be in 1 .. 16, not %r" % (key, d[key]))
+    # feature normalisation between the front end and the frame stacking (ops.feature_norm): none (the reference's behaviour) |
+    # utterance (mean / variance of the utterance itself) | global (of the training corpus, from the file feature_norm_stats names,
+    # which `stt.py --feature_stats` writes).  feature_norm_variance False: means only
+    d["feature_norm"] = cp.get(_ACOUSTIC, "feature_norm", fallback="none").strip()
+    if d["feature_norm"] not in ("none", "utterance", "global"):
+        raise ValueError("feature_norm must be 'none', 'utterance' or 'global', not %r" % d["feature_norm"])
+    d["feature_norm_variance"] = cp.getboolean(_ACOUSTIC, "feature_norm_variance", fallback=True)
+    d["feature_norm_stats"] = (cp.get(_ACOUSTIC, "feature_norm_stats", fallback="") or "").strip() or None
+    if d["feature_norm"] == "global" and d["feature_norm_stats"] is None:
+        raise ValueError("feature_norm : global needs feature_norm_stats, the file `stt.py --feature_stats` writes")
     d["sync_batch_norm"] = cp.getboolean(_TRAINING, "sync_batch_norm", fallback=False)   # DP only; deviation from the reference
     # the decoder behind the per-mini-batch training error rate: greedy (GPU) | beam (default: the reference's width-100 beam
     # decoder, models/AcousticModel.py:312-314,:641, on host threads, reported `train_decoder_lag` mini-batches late; 0 = wait)

@@ -65,11 +65,20 @@ class SpecAugmentPlanInfo(C.Structure):     # amdspeech_spec_augment_plan_info (
     _fields_ = [(n, C.c_int) for n in ("vec", "lanes", "items_per_workgroup", "workgroups", "reps")]
 
 
+class FeatureNormDesc(C.Structure):     # amdspeech_feature_norm_desc (include/amdspeech.h): the mode and the variance handling of one call
+    _fields_ = [("mode", C.c_int), ("norm_vars", C.c_int), ("var_floor", C.c_double)]
+
+
+class FeatureNormPlanInfo(C.Structure):     # amdspeech_feature_norm_plan_info (include/amdspeech.h): the launch geometry of a normalisation call, read-only
+    _fields_ = [(n, C.c_int) for n in ("vec", "split", "workgroups", "lds_bytes", "meta_by_copy", "workspace_bytes")]
+
+
 GEMM_FAMILIES = ("skinny_n", "skinny_k", "skinny_tn", "tn_direct", "kc_direct", "lds", "bf3", "bf16p")      # AMDSPEECH_GEMM_* (include/amdspeech.h)
 GEMM_MAP_LINEAR, GEMM_MAP_XCD, GEMM_MAP_XCD_BLOCKS, GEMM_MAP_KC_BAND = range(4)      # AMDSPEECH_GEMM_MAP_*
 GEMM_GROUP_MAX = 10                                                                 # AMDSPEECH_GEMM_GROUP_MAX
 CTC_KERNELS = ("wave", "shift", "pair", "edge")      # AMDSPEECH_CTC_KERNEL_* (include/amdspeech.h)
 LSTM_PATHS = ("flow", "big1", "big", "hoist", "diag", "diag_bf3")      # AMDSPEECH_LSTM_PATH_* (include/amdspeech.h)
+FEATURE_NORM_MODES = ("none", "utterance", "global")      # AMDSPEECH_FEATURE_NORM_* (include/amdspeech.h)
 LSTM_ARMED, LSTM_ARM_NEXT, LSTM_SAME_WS, LSTM_PER_DIAGONAL, LSTM_INJECT_TIMEOUT = 1, 2, 4, 8, 16      # amdspeech_lstm_desc.flags (include/amdspeech.h)
 
 
@@ -164,6 +173,9 @@ PROTOTYPES = {
     "amdspeech_spec_augment": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(SpecAugmentDesc)]),
     "amdspeech_spec_augment_spans": (_I, [C.POINTER(SpecAugmentDesc), _I, _I, C.POINTER(C.c_int)]),
     "amdspeech_spec_augment_plan": (_I, [_I, _I, _I, C.POINTER(SpecAugmentDesc), C.POINTER(SpecAugmentPlanInfo)]),
+    "amdspeech_feature_norm_plan": (_I, [_I, _I, _I, _I, C.POINTER(FeatureNormPlanInfo)]),
+    "amdspeech_feature_moments": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    "amdspeech_feature_norm": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(FeatureNormDesc), _P, _P]),
     "amdspeech_profile_enable": (_I, [_I]),
     "amdspeech_profile_get": (_I, [_I, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "amdspeech_profile_get_flops": (_I, [_I, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -1020,3 +1020,63 @@ def spec_augment(x, lengths, policy, seed):
         return x
     _l.check(lib.amdspeech_spec_augment(_stream(), _p(x), _p(lengths), T, B, W, C.byref(desc)), "spec_augment")
     return x
+
+
+# ------------------------------------------------------------ feature normalisation
+FEATURE_NORM_VAR_FLOOR = 1e-10
+
+
+def _feature_norm_mode(mode):
+    if mode in _l.FEATURE_NORM_MODES:
+        return _l.FEATURE_NORM_MODES.index(mode)
+    raise ValueError("feature_norm: mode %r is none of %s" % (mode, ", ".join(_l.FEATURE_NORM_MODES)))
+
+
+def feature_norm_plan(B, D, t_in, mode="utterance"):
+    """The launch geometry of `feature_norm` / `feature_moments` for a shape (amdspeech.h: amdspeech_feature_norm_plan), as a dict of
+    ints.  Read-only: nothing is launched, no device is needed.  A shape the calls refuse raises here too."""
+    info = _l.FeatureNormPlanInfo()
+    _l.check(_l.load().amdspeech_feature_norm_plan(int(B), int(D), int(t_in), _feature_norm_mode(mode), C.byref(info)), "feature_norm_plan")
+    return {name: int(getattr(info, name)) for name, _ in _l.FeatureNormPlanInfo._fields_}
+
+
+def _feature_norm_args(what, feat, n_frames):
+    if not (torch.is_tensor(feat) and feat.is_cuda and feat.dtype == torch.float32 and feat.dim() == 3 and feat.is_contiguous()):
+        raise ValueError("%s: expected a contiguous float32 device tensor [t_in, B, D], got %s"
+                         % (what, (feat.dtype, feat.device, tuple(feat.shape), feat.stride()) if torch.is_tensor(feat) else type(feat)))
+    t_in, B, D = feat.shape
+    if len(n_frames) != B:
+        raise ValueError("%s: %d lengths for %d rows" % (what, len(n_frames), B))
+    plan = feature_norm_plan(B, D, t_in, "utterance")
+    ws = torch.empty(max(plan["workspace_bytes"], 8), device=feat.device, dtype=torch.uint8)
+    return t_in, B, D, (C.c_int * B)(*[int(v) for v in n_frames]), ws
+
+
+def feature_moments(feat, n_frames):
+    """feat float32 [t_in, B, D] (device, the front end's output), n_frames: its UNtruncated frame counts (python ints).  Returns a
+    float64 device tensor [B, 2, D]: per row the mean and M2 = sum (x - mean)^2 over its first min(n, t_in) frames, zeros for an
+    empty row (amdspeech.h: amdspeech_feature_moments).  feat is not written."""
+    t_in, B, D, nf, ws = _feature_norm_args("feature_moments", feat, n_frames)
+    out = torch.empty(B, 2, D, device=feat.device, dtype=torch.float64)
+    _l.check(_l.load().amdspeech_feature_moments(_stream(), _p(feat), nf, B, D, t_in, _p(ws), _p(out)), "feature_moments")
+    return out          # stream-ordered; the lengths were kernel arguments (or the call has waited)
+
+
+def feature_norm(feat, n_frames, mode, norm_vars=True, var_floor=FEATURE_NORM_VAR_FLOOR, table=None):
+    """Normalises feat float32 [t_in, B, D] (device, the front end's output) IN PLACE over each row's first min(n, t_in) frames and
+    returns it (amdspeech.h: amdspeech_feature_norm).  mode "utterance": mean and population variance of the row itself; "global":
+    table, a float64 device tensor [2, D] of means and scales (FeatureStats.table) -- norm_vars and var_floor are then part of the
+    table; "none": nothing is launched.  Frames at or past a row's length are neither read nor written."""
+    imode = _feature_norm_mode(mode)
+    if imode == 0:
+        return feat
+    t_in, B, D, nf, ws = _feature_norm_args("feature_norm", feat, n_frames)
+    if imode == 2:
+        if not (torch.is_tensor(table) and table.is_cuda and table.device == feat.device and table.dtype == torch.float64
+                and tuple(table.shape) == (2, D) and table.is_contiguous()):
+            raise ValueError("feature_norm: global mode needs a float64 device table [2, %d] beside feat" % D)
+    elif table is not None:
+        raise ValueError("feature_norm: a table belongs to global mode only")
+    desc = _l.FeatureNormDesc(imode, int(bool(norm_vars)), float(var_floor))
+    _l.check(_l.load().amdspeech_feature_norm(_stream(), _p(feat), nf, B, D, t_in, C.byref(desc), _p(table), _p(ws)), "feature_norm")
+    return feat

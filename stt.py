@@ -1,8 +1,9 @@
 # coding=utf-8
 """Command line of the speech recogniser -- same flags and loop semantics as the reference's
 stt.py (argument parser :360-404, train loop + LR plateau rule :171-236, file / evaluate modes
-:239-324), driving the MI355X-native AcousticModel instead of a TensorFlow session.  One mode is this build's own:
---align AUDIO --transcript "text" prints when each word of a known transcript was spoken (forced CTC alignment).
+:239-324), driving the MI355X-native AcousticModel instead of a TensorFlow session.  Two modes are this build's own:
+--align AUDIO --transcript "text" prints when each word of a known transcript was spoken (forced CTC alignment), and
+--feature_stats writes the corpus statistics that `feature_norm : global` normalises with.
 
 Not kept (out of the hot-path scope): --train_language / --generate_text (the
 reference's language model is an unfinished stub), --record (pyaudio), --XLA (no tracing
@@ -42,7 +43,8 @@ def main():
     if grp.rank == 0:
         hyper_params = hyperparams.HyperParameterHandler(prog_params["config_file"]).get_hyper_params()
     hyper_params = grp.broadcast_object(hyper_params)
-    audio_processor = build_audio_processor(hyper_params)
+    # (--feature_stats writes the file a `feature_norm : global` processor would want to read: it builds its own, unnormalised)
+    audio_processor = None if prog_params["feature_stats"] else build_audio_processor(hyper_params)
     speech_reco = SpeechRecognizer(hyper_params["language"])
     hyper_params["char_map"] = speech_reco.get_char_map()
     hyper_params["char_map_length"] = speech_reco.get_char_map_length()
@@ -74,6 +76,13 @@ def main():
         evaluate(hyper_params)
     elif prog_params["align"] is not None:
         align_file(audio_processor, hyper_params, prog_params["align"], _transcript(prog_params))
+    elif prog_params["feature_stats"]:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            sys.exit("--feature_stats runs in one process: statistics are not accumulated across data-parallel ranks")
+        train_set, _ = speech_reco.load_acoustic_dataset(
+            hyper_params["training_dataset_dirs"], hyper_params["test_dataset_dirs"], hyper_params["training_filelist_cache"],
+            hyper_params["dataset_size_ordering"] in ("True", "First_run_only"), hyper_params["train_frac"])
+        feature_stats(train_set, hyper_params)
     else:
         sys.exit("mode not supported by the MI355X build (see module docstring)")
 
@@ -87,7 +96,8 @@ def build_audio_processor(hyper_params):
                                                     n_mfcc=hyper_params.get("n_mfcc", 20),
                                                     load_sr=hyper_params.get("sample_rate", 22050),
                                                     frame_stack=hyper_params.get("frame_stack", 1),
-                                                    frame_skip=hyper_params.get("frame_skip", 1))
+                                                    frame_skip=hyper_params.get("frame_skip", 1),
+                                                    **_feature_norm_options(hyper_params))
     hyper_params["input_dim"] = audio_processor.feature_size
     hyper_params["out_seq_length"] = audio_processor.out_seq_length
     hyper_params["spec_augment"] = spec_augment_policy(hyper_params, audio_processor)
@@ -97,6 +107,13 @@ def build_audio_processor(hyper_params):
                         hyper_params["out_seq_length"], hyper_params["max_input_seq_length"],
                         hyper_params.get("frame_skip", 1), hyper_params["max_target_seq_length"])
     return audio_processor
+
+
+def _feature_norm_options(hyper_params):
+    """AudioProcessor's feature normalisation arguments from the config keys; the statistics file is read in global mode only."""
+    mode = hyper_params.get("feature_norm", "none")
+    return dict(feature_norm=mode, feature_norm_variance=hyper_params.get("feature_norm_variance", True),
+                feature_stats=hyper_params.get("feature_norm_stats") if mode == "global" else None)
 
 
 def spec_augment_policy(hyper_params, audio_processor):
@@ -129,6 +146,9 @@ def _set_model_options(model, hyper_params):
     model.frame_stack = hyper_params.get("frame_stack", 1)
     model.frame_skip = hyper_params.get("frame_skip", 1)
     model.spec_augment = hyper_params.get("spec_augment")       # (build_audio_processor; only run_step with gradients masks)
+    norm = _feature_norm_options(hyper_params)
+    model.feature_norm, model.feature_norm_variance, model.feature_stats = (norm["feature_norm"], norm["feature_norm_variance"],
+                                                                            norm["feature_stats"])
 
 
 def build_acoustic_training_rnn(sess, hyper_params, prog_params, train_set, test_set):
@@ -146,7 +166,8 @@ def build_acoustic_training_rnn(sess, hyper_params, prog_params, train_set, test
     pipe = dict(n_mfcc=hyper_params.get("n_mfcc", 20), prefetch=hyper_params.get("prefetch_batches", 2),
                 feature_cache_mb=hyper_params.get("feature_cache_mb", 0),
                 sample_rate=hyper_params.get("sample_rate", 22050),
-                frame_stack=hyper_params.get("frame_stack", 1), frame_skip=hyper_params.get("frame_skip", 1))
+                frame_stack=hyper_params.get("frame_stack", 1), frame_skip=hyper_params.get("frame_skip", 1),
+                **_feature_norm_options(hyper_params))
     train_dataset = model.build_dataset(train_set, *ds_args, **pipe)
     test_dataset = model.build_dataset(test_set, *ds_args, **pipe)
     t_iterator, v_iterator = model.add_datasets_input(train_dataset, test_dataset)
@@ -340,13 +361,40 @@ def evaluate(hyper_params):
     return wer, cer
 
 
+def feature_stats(train_set, hyper_params):
+    """--feature_stats: mean and variance of every feature dim over the training set, for `feature_norm : global`.  One walk through
+    the dataset path the training takes (decode, resample, front end, truncation at max_input_seq_length) with the normalisation,
+    the frame stacking and the feature cache OFF whatever the config says: the statistics are those of the raw 10 ms frames.  Per
+    mini-batch the GPU reduces every row to its moments (ops.feature_moments) and the host merges them in float64.  Writes the
+    file feature_norm_stats names and prints the number of frames."""
+    from rnn_speech_amd.feature_norm import FeatureStats, describe_processor
+    path = hyper_params.get("feature_norm_stats")
+    if not path:
+        sys.exit("--feature_stats needs feature_norm_stats (the file to write) in the configuration file")
+    dataset = AcousticModel.build_dataset(train_set, hyper_params["batch_size"], hyper_params["max_input_seq_length"],
+                                          hyper_params["max_target_seq_length"], hyper_params["signal_processing"],
+                                          hyper_params["char_map"], n_mfcc=hyper_params.get("n_mfcc", 20),
+                                          prefetch=hyper_params.get("prefetch_batches", 2),
+                                          sample_rate=hyper_params.get("sample_rate", 22050))
+    stats = FeatureStats(describe_processor(dataset.audio))
+    for feat, lengths, _ in dataset.batches():
+        stats.accumulate(feat, lengths)
+    if not stats.count > 0:
+        sys.exit("--feature_stats: the training set holds no frame")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    stats.save(path)
+    print("feature statistics of %d frames (%d dims) written to %s" % (stats.count, stats.mean.shape[0], path))
+    return stats
+
+
 _MODES = (("train_acoustic", "store_true", "train the acoustic model"),
           ("train_language", "store_true", "reference stub -- not supported here"),
           ("file", str, "transcribe one wav file"),
           ("record", "store_true", "live microphone mode -- not supported here"),
           ("evaluate", "store_true", "WER / CER of the restored model on the test manifest"),
           ("generate_text", "store_true", "reference stub -- not supported here"),
-          ("align", str, "align a known transcript (--transcript / --transcript_file) to one audio file: a line per word"))
+          ("align", str, "align a known transcript (--transcript / --transcript_file) to one audio file: a line per word"),
+          ("feature_stats", "store_true", "write the training set's feature means and variances to feature_norm_stats (feature_norm : global)"))
 
 
 def parse_args():
