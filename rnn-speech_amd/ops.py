@@ -621,6 +621,14 @@ class BidirWorkspace(object):
         c = torch.as_strided(self.buf, (L, B, H), (stride, H, 1), self._offset(_l.BIDIR_WS_CFINAL))
         return h, c
 
+    def layer_outputs(self):
+        """(y_fw [L,T,B,H], y_bw [L,T,B,H]): read-only views of every layer's outputs in forward time; the top layer's are
+        ytop_fw / ytop_bw, layer l lies L - 1 - l layer strides below them (amdspeech_lstm_bidir_layer_stride)."""
+        stride = self.lib.amdspeech_lstm_bidir_layer_stride(C.byref(self.desc))
+        T, B, H, L = self.T, self.B, self.H, self.L
+        return tuple(torch.as_strided(self.buf, (L, T, B, H), (stride, B * H, H, 1), self._offset(which) - (L - 1) * stride)
+                     for which in (_l.BIDIR_WS_YTOP_FW, _l.BIDIR_WS_YTOP_BW))
+
 
 def _ptr_array(ts):
     return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
