@@ -562,6 +562,63 @@ int amdspeech_resample_num_samples(int n_samples, int rate_in, int rate_out);
 int amdspeech_resample(void* stream, const float* pcm, const int* n_samples, int B, int n_max, int rate_in,
                        int rate_out, float* out, int out_max, void* ws);
 
+/* ------------------------------------------- per-row resampler / speed perturbation ---
+ * The resampler above with a ratio of its own for every row, in ONE launch (no reference counterpart: an opt-in deviation, the
+ * three-way speed perturbation of Ko et al. 2015 on the waveform, in front of the front end; off unless a caller makes this call).
+ * A signal played f times faster is the signal resampled from rate * f to rate, so rate conversion and speed change are one pass.
+ *   pcm            float [B][n_max] (DEVICE);  out  float [B][out_max] (DEVICE)
+ *   n_samples      int32 [B] (HOST) valid samples per row, 0 .. n_max
+ *   speed_permille int32 [B] (HOST) the row's speed in thousandths, 500 .. 2000 (0.5x .. 2.0x); 1000 = rate conversion only
+ * Speed.  num = rate_out * 1000 and den = rate_in * speed_permille as 64-bit integers; ratio = (double)num / (double)den, ONE
+ * double division of the two integers (at 1000 permille the same double as amdspeech_resample's rate_out / rate_in).
+ * Row lengths.  Row b receives n_total = ceil(n * num / den) samples, in exact integer arithmetic
+ * (amdspeech_resample_rows_num_samples); a call with n_max * num >= 2^53 is refused.  Under that limit this equals
+ * amdspeech_resample_num_samples' ceil((double)n * rate_out / rate_in) at 1000 permille.
+ * Output arithmetic.  The first n_out = (int)((double)n * ratio) samples of a row are resampy's "kaiser_best" interpolation exactly
+ * as amdspeech_resample computes it -- the same table win[j], delta[j] (here stored WITHOUT the gain), scale = min(1, ratio),
+ * step = (int)(scale * 512), and for output t:  tr = (double)t / ratio, k = (int)tr, frac = scale * (tr - k), off = (int)(frac * 512),
+ * eta = frac * 512 - off; the left wing sums (win[off + i step] + eta delta[off + i step]) * x[k - i] over i < min(k + 1,
+ * (32769 - off) / step), the right wing the same with frac' = scale - frac over x[k + 1 + i], i < min(n - k - 1, (32769 - off') / step)
+ * -- the wing counts are clipped at both ends of the row; the two wing sums, each in tap order, are added and multiplied by the
+ * row's gain (float)scale.  The remaining 0 or 1 samples up to n_total are +0.0f, and so are all samples from n_total to out_max.
+ * Writes and reads.  The kernel writes EVERY word of out, so out may be uninitialised; it reads no input word at or past
+ * n_samples[b], which may hold anything.
+ * Copy rule.  A row with num == den (22,050 -> 22,050 at 1000, but also 44,100 -> 22,050 at 500) is COPIED bit for bit:
+ * infinities, -0.0, denormals and NaN payloads arrive unchanged (the interpolation at ratio 1 is a low-pass, not the identity).
+ * No atomics and no dependence on the launch order: two calls give the same bits.  Asynchronous on `stream`; lengths and speeds
+ * travel as kernel arguments of one-block launches, 512 values each (2 B values: the lengths, then the speeds).
+ *   ws   device, amdspeech_resample_rows_workspace_bytes(B) bytes, 256-byte aligned, caller-allocated: the table and the 2 B values
+ * AMDSPEECH_EINVAL with a message: null pointers, non-positive B, n_max, out_max or rates, B > 65535, n_max * num >= 2^53, a
+ * negative count or n > n_max, a permille outside 500 .. 2000, an out_max below a row's n_total, a ratio outside 1/16 .. 16, pcm and
+ * out ranges that overlap.
+ * amdspeech_resample_rows_plan: the launch geometry as plain numbers, a READ-ONLY view of the plan the call itself reads (one
+ * function decides for both); no device is needed, the arguments are checked as the call checks them.
+ *   tile           outputs per workgroup (1024: 256 threads of 4);  tiles_per_row = ceil(out_max / tile)
+ *   workgroups     tiles_per_row * B: workgroup (x, b) owns outputs x * tile .. of row b.  A tile at or past n_total stores zeros,
+ *                  a tile of a copy row copies (both branches are uniform over the workgroup), every other tile stages the input
+ *                  span of its outputs in LDS once, then the table in chunks, and reads its taps and its table words from there
+ *   span_max       the longest staged span in samples: over the rows with n > 0 and num != den the maximum of
+ *                  min(n, (int)((tile - 1) / ratio) + 2 * (32769 / step) + 4);  0 when no row interpolates
+ *   table_chunk    table entries (8 bytes each) a staged chunk holds: 4097, the taps i0 .. i0 + 4096 / step - 1 of every output;
+ *                  0 when no row interpolates
+ *   lds_bytes      dynamic LDS of the launch: 4 * span_max rounded up to 16, + 8 * table_chunk (37 KB at ratio 1, 51 KB at 1/4,
+ *                  104 KB at the 1/16 bound)
+ *   any_copy       1 when some row has num == den
+ *   meta_launches  ceil(2 B / 512)
+ * amdspeech_speed_perturb_draw: the speed of one utterance, host arithmetic with SpecAugment's integer hash (see there):
+ *   idx = lo32(index) + hi32(index) * 0x9E3779B1 (32-bit wrap),  choice = (r(0x5B000000, idx) * count) >> 24,
+ * returns factors_permille[choice] (count 1 .. 8, every factor 500 .. 2000; anything else is AMDSPEECH_EINVAL).             */
+typedef struct amdspeech_resample_rows_plan_info {
+    int tile, tiles_per_row, workgroups, span_max, table_chunk, lds_bytes, any_copy, meta_launches;
+} amdspeech_resample_rows_plan_info;
+int amdspeech_resample_rows_num_samples(int n_samples, int rate_in, int rate_out, int speed_permille);
+size_t amdspeech_resample_rows_workspace_bytes(int B);
+int amdspeech_resample_rows(void* stream, const float* pcm, const int* n_samples, const int* speed_permille, int B, int n_max,
+                            int rate_in, int rate_out, float* out, int out_max, void* ws);
+int amdspeech_resample_rows_plan(const int* n_samples, const int* speed_permille, int B, int n_max, int rate_in, int rate_out,
+                                 int out_max, amdspeech_resample_rows_plan_info* out);
+int amdspeech_speed_perturb_draw(unsigned long long seed, unsigned long long index, const int* factors_permille, int count);
+
 /* ------------------------------------------------------------- optimiser ----
  * Replaces tf.clip_by_global_norm + tf.train.AdamOptimizer.apply_gradients over
  * the flat parameter vector, models/AcousticModel.py:388 and :404-406.
@@ -651,7 +708,7 @@ int amdspeech_frame_stack_plan(int B, int D, int t_in, int stack, int skip, amds
 
 /* ------------------------------------------------------------ SpecAugment ----
  * Frequency and time masks on a training mini-batch's features, IN PLACE, between the front end (or the frame stacking) and the
- * model (no reference counterpart: an opt-in deviation; time warping and speed perturbation are not part of it).  The input
+ * model (no reference counterpart: an opt-in deviation; time warping is not part of it, speed perturbation is amdspeech_resample_rows).  The input
  * needs no gradient, so there is no backward call: the input Linear's weight gradient simply reads the masked tensor.
  *   x        float [T][B][W]      time-major, contiguous; masked words become +0.0f, every other word keeps its bit pattern
  *   lengths  int32 [B] (DEVICE)   frames of each row; n_b = min(lengths[b], T); a row with n_b <= 0 is not touched, and no

@@ -74,12 +74,18 @@ class AcousticDataset(object):
     frame_stack / frame_skip: low frame rate input (AudioProcessor).  max_input_seq_length stays in SOURCE frames; the batches,
     their lengths, T and the feature cache are in MODEL frames (T = audio.out_seq_length rows of audio.feature_size values).
     feature_norm / feature_norm_variance / feature_stats: feature normalisation (AudioProcessor); the batches and the feature
-    cache hold normalised features."""
+    cache hold normalised features.
+    speed_perturb: None (off: nothing is launched), or (factors_permille, seed) -- speed perturbation of the waveform on the GPU
+    (ops.resample_rows).  The factor of an item is ops.speed_perturb_draw(seed64, (epoch_serial << 32) | position in self.items,
+    factors) with seed64 = (seed + data-parallel rank) << 32; epoch_serial is a counter shared with the with_items siblings that
+    advances once per batches() pass, so a re-shuffled epoch draws afresh and a run is reproducible.  Durations used for bucketing
+    stay the unperturbed ones; a row made longer than max_input_seq_length is truncated like any over-long file.  Cached features
+    would freeze the draw: feature_cache_mb > 0 beside it is refused."""
 
     def __init__(self, input_set, batch_size, max_input_seq_length, max_target_seq_length,
                  signal_processing, char_map, n_mfcc=20, device="cuda", prefetch=2, feature_cache_mb=0,
                  sample_rate=22050, frame_stack=1, frame_skip=1, feature_norm="none", feature_norm_variance=True,
-                 feature_stats=None):
+                 feature_stats=None, speed_perturb=None):
         self.items = [(it[0], it[1]) for it in input_set]
         self.batch_size = batch_size
         self.U = max_target_seq_length
@@ -93,6 +99,33 @@ class AcousticDataset(object):
         self._signal_processing, self._n_mfcc = signal_processing, n_mfcc
         self._cache = {} if feature_cache_mb > 0 else None
         self._room = [int(feature_cache_mb) << 20]          # shared (by reference) with reordered siblings
+        self._speed = self._speed_option(speed_perturb, feature_cache_mb)
+        self._epoch = [0]                                   # speed perturbation's epoch_serial, shared in the same way
+        # the data-parallel rank, resolved HERE on the caller's thread: the draws run on the decode-ahead thread
+        self._rank = dataparallel.current().rank if self._speed is not None else 0
+
+    @staticmethod
+    def _speed_option(speed_perturb, feature_cache_mb):
+        if speed_perturb is None:
+            return None
+        factors, seed = speed_perturb
+        factors = tuple(int(f) for f in factors)
+        if not 1 <= len(factors) <= 8 or any(not 500 <= f <= 2000 for f in factors):
+            raise ValueError("speed_perturb: 1 .. 8 factors of 500 .. 2000 permille, not %r" % (factors,))
+        if factors == (1000,):
+            return None
+        if feature_cache_mb > 0:
+            raise ValueError("speed_perturb with feature_cache_mb > 0: cached features would freeze the draw; set feature_cache_mb : 0")
+        return factors, int(seed)
+
+    def speed_draws(self, epoch_serial, start=0, count=None):
+        """The speed factors (permille) of items start .. start + count of pass `epoch_serial`; None when the option is off."""
+        if self._speed is None:
+            return None
+        factors, seed = self._speed
+        seed64 = ((seed + self._rank) << 32) & 0xFFFFFFFFFFFFFFFF
+        stop = len(self.items) if count is None else min(start + count, len(self.items))
+        return [ops.speed_perturb_draw(seed64, (int(epoch_serial) << 32) | pos, factors) for pos in range(start, stop)]
 
     def with_items(self, input_set):
         """The same dataset over a re-ordered / re-shuffled item list, sharing the feature cache (the
@@ -101,18 +134,19 @@ class AcousticDataset(object):
                                 self.char_map, n_mfcc=self._n_mfcc, device=self.audio.device, prefetch=self.prefetch,
                                 sample_rate=self.audio.load_sr, frame_stack=self.audio.frame_stack,
                                 frame_skip=self.audio.frame_skip, feature_norm=self.audio.feature_norm,
-                                feature_norm_variance=self.audio.feature_norm_variance, feature_stats=self.audio.feature_stats)
-        other._cache, other._room = self._cache, self._room
+                                feature_norm_variance=self.audio.feature_norm_variance, feature_stats=self.audio.feature_stats,
+                                speed_perturb=self._speed)
+        other._cache, other._room, other._epoch, other._rank = self._cache, self._room, self._epoch, self._rank
         return other
 
     # ---- producer side (host only) -------------------------------------------------
     def _chunks(self):
         B = self.batch_size
         for start in range(0, len(self.items), B):
-            yield self.items[start:start + B]
+            yield start, self.items[start:start + B]
 
-    def _prepare(self, chunk):
-        """Host half of one mini-batch: cached features or decoded waveforms per item."""
+    def _prepare(self, chunk, speeds=None):
+        """Host half of one mini-batch: cached features or decoded waveforms per item.  speeds: the items' speed factors."""
         from .audioprocessor import decode_files
         cache = self._cache
         need = [a for a, _ in chunk if isinstance(a, str) and (cache is None or a not in cache)]
@@ -138,13 +172,13 @@ class AcousticDataset(object):
             sigs = [p[0] for _, p in parts] + [np.zeros(0, np.float32)] * (B - len(parts))
             staged = ("batch", self.audio.stage(sigs), parts[0][1][1])
         elif "cached" not in kinds:
-            staged = ("files", self.audio.stage_files([p for _, p in parts]))
-        return chunk, parts, dense, staged
+            staged = ("files", self.audio.stage_files([p for _, p in parts], speeds))
+        return chunk, parts, dense, staged, speeds
 
-    def _prepared(self):
+    def _prepared(self, epoch_serial=0):
         if self.prefetch <= 0:
-            for chunk in self._chunks():
-                yield self._prepare(chunk)
+            for start, chunk in self._chunks():
+                yield self._prepare(chunk, self.speed_draws(epoch_serial, start, len(chunk)))
             return
         import queue
         import threading
@@ -153,10 +187,10 @@ class AcousticDataset(object):
 
         def produce():
             try:
-                for chunk in self._chunks():
+                for start, chunk in self._chunks():
                     if stop.is_set():
                         return
-                    q.put(("ok", self._prepare(chunk)))
+                    q.put(("ok", self._prepare(chunk, self.speed_draws(epoch_serial, start, len(chunk)))))
                 q.put(("end", None))
             except BaseException as exc:            # surfaced in the consumer
                 q.put(("error", exc))
@@ -193,13 +227,17 @@ class AcousticDataset(object):
     # ---- consumer side (device) -----------------------------------------------------
     def batches(self):
         B, T = self.batch_size, self.T
-        for chunk, parts, dense, staged in self._prepared():
+        epoch_serial = self._epoch[0]              # this pass's draws of the speed perturbation; the next pass draws afresh
+        self._epoch[0] += 1
+        for chunk, parts, dense, staged, speeds in self._prepared(epoch_serial):
             if staged is not None and staged[0] == "batch":
                 # in-memory signals at one rate: the process_signal convention (no resampling)
-                feat, lengths = self.audio.process_batch(None, staged[2], t_max=T, staged=staged[1])
+                feat, lengths = self.audio.process_batch(None, staged[2], t_max=T, staged=staged[1],
+                                                         speed_permille=None if speeds is None else speeds + [1000] * (B - len(speeds)))
             elif staged is not None:
                 # files: librosa.load semantics (22,050 Hz); a short final batch is padded with empty rows
-                feat, lengths = self.audio.process_files(None, t_max=T, rows=B, decoded=[p for _, p in parts], staged=staged[1])
+                feat, lengths = self.audio.process_files(None, t_max=T, rows=B, decoded=[p for _, p in parts], staged=staged[1],
+                                                         speed_permille=speeds)
             else:
                 feat, lengths = self._assemble(parts)
             if self._cache is not None:
@@ -712,13 +750,16 @@ class AcousticModel(object):
     @staticmethod
     def build_dataset(input_set, batch_size, max_input_seq_length, max_target_seq_length,
                       signal_processing, char_map, n_mfcc=20, prefetch=2, feature_cache_mb=0, sample_rate=22050,
-                      frame_stack=1, frame_skip=1, feature_norm="none", feature_norm_variance=True, feature_stats=None):
-        """max_input_seq_length in SOURCE frames, whatever frame_stack / frame_skip (the dataset's T is in model frames)."""
+                      frame_stack=1, frame_skip=1, feature_norm="none", feature_norm_variance=True, feature_stats=None,
+                      speed_perturb=None):
+        """max_input_seq_length in SOURCE frames, whatever frame_stack / frame_skip (the dataset's T is in model frames).
+        speed_perturb: None, or (factors_permille, seed): speed perturbation of the waveforms (AcousticDataset)."""
         return AcousticDataset(input_set, batch_size, max_input_seq_length, max_target_seq_length,
                                signal_processing, char_map, n_mfcc=n_mfcc, prefetch=prefetch,
                                feature_cache_mb=feature_cache_mb, sample_rate=sample_rate,
                                frame_stack=frame_stack, frame_skip=frame_skip, feature_norm=feature_norm,
-                               feature_norm_variance=feature_norm_variance, feature_stats=feature_stats)
+                               feature_norm_variance=feature_norm_variance, feature_stats=feature_stats,
+                               speed_perturb=speed_perturb)
 
     def add_dataset_input(self, dataset):
         self._single_iter = DatasetIterator(dataset)

@@ -140,40 +140,77 @@ class AudioProcessor(object):
         out, n_out = ops.frame_stack(feat, lengths, self.frame_stack, self.frame_skip)
         return (out if t_max is None or out.shape[0] <= t_max else out[:int(t_max)]), n_out
 
-    def process_batch(self, signals, sr, t_max=None, staged=None):
+    @staticmethod
+    def _speeds(speed_permille, rows):
+        """Per-row speed factors (permille, 500 .. 2000) of a process_* call, checked; None: no speed change."""
+        if speed_permille is None:
+            return None
+        speeds = [int(v) for v in speed_permille]
+        if len(speeds) != rows:
+            raise ValueError("speed_permille: %d factors for %d rows" % (len(speeds), rows))
+        for v in speeds:
+            if not 500 <= v <= 2000:
+                raise ValueError("speed_permille: %d outside 500 .. 2000" % v)
+        return speeds
+
+    @staticmethod
+    def _resampled(pcm, n, speeds, rate_in, rate_out):
+        """One ops.resample_rows call for a group of rows at one source rate: rate conversion and speed change together.  A group
+        whose rows all have ratio exactly 1 (rate_out * 1000 == rate_in * speed) makes no call."""
+        rows = len(n)
+        speeds = list(speeds) + [1000] * (pcm.shape[0] - rows)       # (padding rows are empty)
+        n = list(n) + [0] * (pcm.shape[0] - rows)
+        if all(int(rate_out) * 1000 == int(rate_in) * v for v in speeds[:rows]):
+            return pcm, n[:rows]
+        out, n_out = ops.resample_rows(pcm, n, speeds, rate_in, rate_out)
+        return out, n_out[:rows]
+
+    def process_batch(self, signals, sr, t_max=None, staged=None, speed_permille=None):
         """signals: list of 1-D float arrays, all at sample rate `sr`.  Returns (feat [t_max, B, feature_size] device
         float32, zero past each utterance; list of UNtruncated frame counts) -- model frames under low frame rate input,
-        t_max defaulting to out_seq_length.  staged: (block, n) from stage()."""
+        t_max defaulting to out_seq_length.  staged: (block, n) from stage().  speed_permille: a speed factor per signal (speed
+        perturbation, ops.resample_rows: a row played f times faster has 1 / f of its samples); None or all 1000: nothing is launched."""
         t_out, t_max = t_max, self._source_t_max(t_max)
         if staged is not None:
             pcm, n = self._upload_staged(staged[0]), staged[1]
         else:
             pcm, n = self._upload(signals)
+        speeds = self._speeds(speed_permille, len(n))
+        if speeds is not None:
+            pcm, n = self._resampled(pcm, n, speeds, int(sr), int(sr))
         return self._stacked(*ops.frontend(pcm, n, int(sr), self.feature_type, int(t_max), self.n_mfcc), t_out)
 
-    def stage_files(self, decoded):
-        """stage() for decoded files, grouped by source rate as process_files uploads them: [(sr, idx, block, n)]."""
+    def stage_files(self, decoded, speed_permille=None):
+        """stage() for decoded files, grouped by source rate as process_files uploads them: [(sr, idx, block, n)].  speed_permille
+        (a factor per file, handed to process_files with the result) is checked here, on the producer's thread."""
+        self._speeds(speed_permille, len(decoded))
         by_rate = {}
         for i, (_, sr) in enumerate(decoded):
             by_rate.setdefault(int(sr), []).append(i)
         return [(sr, idx) + self.stage([decoded[i][0] for i in idx]) for sr, idx in by_rate.items()]
 
-    def process_files(self, file_names, t_max=None, rows=None, decoded=None, staged=None):
+    def process_files(self, file_names, t_max=None, rows=None, decoded=None, staged=None, speed_permille=None):
         """What the reference's dataset map does per file (process_audio_file: librosa.load at 22,050 Hz,
         then the extractor, util/audioprocessor.py:41-61), for a whole mini-batch: files are decoded natively
         on host threads (or passed in as `decoded` [(signal, sr), ...]), uploaded once, resampled to
         22,050 Hz on the GPU per source rate and handed to the front-end kernels without leaving HBM.
-        `rows` > len(files) pads the batch with empty utterances (length 0).  Model frames as process_batch."""
+        `rows` > len(files) pads the batch with empty utterances (length 0).  Model frames as process_batch.
+        speed_permille: a speed factor per file (speed perturbation); per source rate ONE ops.resample_rows call then does the rate
+        conversion and the speed change together, and a group whose rows all have ratio 1 makes no call.  A row made longer than
+        max_input_seq_length is truncated by the front end like any over-long file."""
         t_out, t_max = t_max, self._source_t_max(t_max)
         if decoded is None:
             decoded = decode_files(file_names)
         B = rows or len(decoded)
+        speeds = self._speeds(speed_permille, len(decoded))
         if staged is None:
             staged = self.stage_files(decoded)
         parts, lengths = [], [0] * B
         for sr, idx, block, n in staged:
             pcm = self._upload_staged(block)
-            if sr != self.load_sr:
+            if speeds is not None:
+                pcm, n = self._resampled(pcm, n, [speeds[i] for i in idx], sr, self.load_sr)
+            elif sr != self.load_sr:
                 pcm, n = ops.resample(pcm, n, sr, self.load_sr)
             parts.append((idx, pcm, n))
         width = max(max(p[1].shape[1] for p in parts), 1) if parts else 1

@@ -1,6 +1,7 @@
 """config.ini reader + checkpoint-side pickle logic (reference:
 /root/reference/util/hyperparams.py:17-141).  Same section/key names and defaults; a few
-optional keys are added for the MI355X build (n_mfcc, sample_rate, frame_stack / frame_skip, feature_norm*, spec_augment_* ...)."""
+optional keys are added for the MI355X build (n_mfcc, sample_rate, frame_stack / frame_skip, feature_norm*, spec_augment_*,
+speed_perturb_* ...)."""
 import configparser
 import logging
 import os
@@ -95,7 +96,28 @@ def read_config_file(config_file):
     if not 0.0 <= ratio <= 1.0:          # (a NaN fails both comparisons)
         raise ValueError("spec_augment_time_ratio must be in 0 .. 1, not %r" % ratio)
     d["spec_augment_time_permille"] = int(round(1000 * ratio))
+    # speed perturbation of the TRAINING waveforms (ops.resample_rows): a comma-separated list of speed factors, each rounded to
+    # permille, one of which is drawn per utterance and epoch.  Absent, empty or 1.0 alone: off.  NOT structural, like SpecAugment
+    d["speed_perturb_factors"] = parse_speed_factors(cp.get(_TRAINING, "speed_perturb_factors", fallback=""))
+    d["speed_perturb_seed"] = cp.getint(_TRAINING, "speed_perturb_seed", fallback=0)
+    if not 0 <= d["speed_perturb_seed"] <= 2 ** 32 - 1:
+        raise ValueError("speed_perturb_seed must be in 0 .. %d, not %r" % (2 ** 32 - 1, d["speed_perturb_seed"]))
     return d
+
+
+def parse_speed_factors(text):
+    """"0.9, 1.0, 1.1" -> [900, 1000, 1100]: at most 8 decimals of 0.5 .. 2.0, each rounded to permille; [] (off) for an empty
+    list or 1.0 alone."""
+    try:
+        factors = [int(round(1000 * float(tok))) for tok in (text or "").split(",") if tok.strip()]
+    except (ValueError, OverflowError):          # (int() of a NaN / of an infinity)
+        raise ValueError("speed_perturb_factors must be a comma-separated list of decimals, not %r" % text)
+    if len(factors) > 8:
+        raise ValueError("speed_perturb_factors holds %d factors, at most 8" % len(factors))
+    for f in factors:
+        if not 500 <= f <= 2000:
+            raise ValueError("speed_perturb_factors: %g outside 0.5 .. 2.0" % (f / 1000.0))
+    return [] if factors == [1000] else factors
 
 
 class HyperParameterHandler(object):

@@ -73,6 +73,10 @@ class FeatureNormPlanInfo(C.Structure):     # amdspeech_feature_norm_plan_info (
     _fields_ = [(n, C.c_int) for n in ("vec", "split", "workgroups", "lds_bytes", "meta_by_copy", "workspace_bytes")]
 
 
+class ResampleRowsPlanInfo(C.Structure):     # amdspeech_resample_rows_plan_info (include/amdspeech.h): the launch geometry of a per-row resampling call, read-only
+    _fields_ = [(n, C.c_int) for n in ("tile", "tiles_per_row", "workgroups", "span_max", "table_chunk", "lds_bytes", "any_copy", "meta_launches")]
+
+
 GEMM_FAMILIES = ("skinny_n", "skinny_k", "skinny_tn", "tn_direct", "kc_direct", "lds", "bf3", "bf16p")      # AMDSPEECH_GEMM_* (include/amdspeech.h)
 GEMM_MAP_LINEAR, GEMM_MAP_XCD, GEMM_MAP_XCD_BLOCKS, GEMM_MAP_KC_BAND = range(4)      # AMDSPEECH_GEMM_MAP_*
 GEMM_GROUP_MAX = 10                                                                 # AMDSPEECH_GEMM_GROUP_MAX
@@ -158,6 +162,12 @@ PROTOTYPES = {
     "amdspeech_resample_workspace_bytes": (_SZ, [C.c_int]),
     "amdspeech_resample_num_samples": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "amdspeech_resample": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "amdspeech_resample_rows_num_samples": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "amdspeech_resample_rows_workspace_bytes": (_SZ, [C.c_int]),
+    "amdspeech_resample_rows": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "amdspeech_resample_rows_plan": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.POINTER(ResampleRowsPlanInfo)]),
+    "amdspeech_speed_perturb_draw": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.c_int]),
     "amdspeech_audio_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]),
     "amdspeech_audio_decode": (C.c_int, [C.c_char_p, _P, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_int), C.c_int]),
     "amdspeech_optim_workspace_bytes": (_SZ, [_L]),

@@ -907,6 +907,75 @@ def resample(pcm, n_samples, rate_in, rate_out):
     return out, n_out
 
 
+_resample_rows_ws = {}
+
+
+def _int_array(values, what, B):
+    if len(values) != B:
+        raise ValueError("%s: %d values for %d rows" % (what, len(values), B))
+    return (C.c_int * max(B, 1))(*[int(v) for v in values])
+
+
+def resample_rows_num_samples(n, rate_in, rate_out, speed_permille=1000):
+    """Samples a row of n samples becomes: ceil(n * rate_out * 1000 / (rate_in * speed_permille)), exact integer arithmetic on the
+    host (amdspeech.h: amdspeech_resample_rows_num_samples)."""
+    got = _l.load().amdspeech_resample_rows_num_samples(int(n), int(rate_in), int(rate_out), int(speed_permille))
+    if got < 0:
+        _l.check(got, "resample_rows_num_samples")
+    return got
+
+
+def resample_rows_plan(n_samples, speed_permille, n_max, rate_in, rate_out, out_max=None):
+    """The launch geometry of `resample_rows` for these rows (amdspeech.h: amdspeech_resample_rows_plan), as a dict of ints.
+    out_max None: the longest output row, as resample_rows sizes it.  Read-only: nothing is launched, no device is needed.  What
+    the call refuses raises here too."""
+    B = len(n_samples)
+    ns, pm = _int_array(n_samples, "resample_rows_plan", B), _int_array(speed_permille, "resample_rows_plan", B)
+    if out_max is None:
+        out_max = max([resample_rows_num_samples(n, rate_in, rate_out, s) for n, s in zip(n_samples, speed_permille)] + [1])
+    info = _l.ResampleRowsPlanInfo()
+    _l.check(_l.load().amdspeech_resample_rows_plan(ns, pm, B, int(n_max), int(rate_in), int(rate_out), int(out_max), C.byref(info)),
+             "resample_rows_plan")
+    return {name: int(getattr(info, name)) for name, _ in _l.ResampleRowsPlanInfo._fields_}
+
+
+def resample_rows(pcm, n_samples, speed_permille, rate_in, rate_out, out=None):
+    """pcm float32 [B, n_max] (device), n_samples and speed_permille python ints per row -> (out [B, out_max] device, new lengths):
+    every row resampled from rate_in * speed / 1000 to rate_out in ONE launch -- rate conversion and speed change together
+    (amdspeech.h: amdspeech_resample_rows).  A row whose ratio is exactly 1 is copied bit for bit.  Every word of out is written;
+    input words at or past a row's length are not read.  out: an [B, out_max] tensor to fill (out_max at least the longest row)."""
+    _chk_f32(pcm, out)
+    if pcm.dim() != 2:
+        raise ValueError("resample_rows: expected [B, n_max], got %s" % (tuple(pcm.shape),))
+    lib = _l.load()
+    B, n_max = pcm.shape
+    ns, pm = _int_array(n_samples, "resample_rows", B), _int_array(speed_permille, "resample_rows", B)
+    n_out = [resample_rows_num_samples(n, rate_in, rate_out, s) for n, s in zip(n_samples, speed_permille)]
+    if out is None:
+        out = torch.empty(B, max(max(n_out), 1), device=pcm.device, dtype=torch.float32)
+    elif out.dim() != 2 or out.shape[0] != B or out.device != pcm.device:
+        raise ValueError("resample_rows: out is %s on %s, expected [%d, out_max] beside pcm" % (tuple(out.shape), out.device, B))
+    key = (B, pcm.device)
+    ws = _resample_rows_ws.get(key)
+    if ws is None:
+        if len(_resample_rows_ws) > 8:
+            _resample_rows_ws.clear()
+        ws = _resample_rows_ws[key] = torch.empty(lib.amdspeech_resample_rows_workspace_bytes(B), device=pcm.device, dtype=torch.uint8)
+    _l.check(lib.amdspeech_resample_rows(_stream(), _p(pcm), ns, pm, B, n_max, int(rate_in), int(rate_out), _p(out), out.shape[1],
+                                         _p(ws)), "resample_rows")
+    return out, n_out          # stream-ordered; lengths and speeds were kernel arguments, the cached workspace outlives the kernels
+
+
+def speed_perturb_draw(seed, index, factors_permille):
+    """The speed (permille) of utterance `index` under `seed`, one of factors_permille (1 .. 8 values in 500 .. 2000): SpecAugment's
+    integer hash on the host (amdspeech.h: amdspeech_speed_perturb_draw)."""
+    f = (C.c_int * max(len(factors_permille), 1))(*[int(v) for v in factors_permille])
+    got = _l.load().amdspeech_speed_perturb_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(index) & 0xFFFFFFFFFFFFFFFF, f, len(factors_permille))
+    if got < 0:
+        _l.check(got, "speed_perturb_draw")
+    return got
+
+
 def frontend_plan(mode, sample_rate, n_mfcc, B, n_max, t_max):
     """The kernels `frontend` takes for a call (amdspeech.h: amdspeech_frontend_plan), as a dict of ints.  mode "mfcc" / "fbank".
     Read-only: nothing is launched, no device is needed.  A call the front end refuses raises here too."""

@@ -133,6 +133,15 @@ def spec_augment_policy(hyper_params, audio_processor):
                 time_width=get("time_width"), time_permille=get("time_permille", 1000), seed=get("seed"))
 
 
+def speed_perturb_option(hyper_params):
+    """AcousticDataset's speed_perturb from the speed_perturb_* keys: None when they are off (the default: nothing is launched),
+    else (factors in permille, seed)."""
+    factors = list(hyper_params.get("speed_perturb_factors") or [])
+    if not factors or factors == [1000]:
+        return None
+    return factors, int(hyper_params.get("speed_perturb_seed", 0))
+
+
 def _model_length(hyper_params):
     """Frames the model runs: max_input_seq_length in source frames, divided by frame_skip (rounded up)."""
     return hyper_params.get("out_seq_length", -(-hyper_params["max_input_seq_length"] // hyper_params.get("frame_skip", 1)))
@@ -168,7 +177,8 @@ def build_acoustic_training_rnn(sess, hyper_params, prog_params, train_set, test
                 sample_rate=hyper_params.get("sample_rate", 22050),
                 frame_stack=hyper_params.get("frame_stack", 1), frame_skip=hyper_params.get("frame_skip", 1),
                 **_feature_norm_options(hyper_params))
-    train_dataset = model.build_dataset(train_set, *ds_args, **pipe)
+    # speed perturbation: the TRAINING dataset only
+    train_dataset = model.build_dataset(train_set, *ds_args, speed_perturb=speed_perturb_option(hyper_params), **pipe)
     test_dataset = model.build_dataset(test_set, *ds_args, **pipe)
     t_iterator, v_iterator = model.add_datasets_input(train_dataset, test_dataset)
     sess.run(t_iterator.initializer)
