@@ -556,26 +556,34 @@ int amdspeech_audio_decode(const char* path, float* out, long capacity, long* fr
  * sinc interpolation with resampy's "kaiser_best" filter, on the GPU so that decoded PCM goes
  * H2D once and never comes back.  pcm [B, n_max] and out [B, out_max] are DEVICE buffers, n_samples a
  * HOST array; row b receives ceil(n_samples[b] * rate_out / rate_in) samples (amdspeech_resample_num_samples),
- * zero padded to out_max.                                                                          */
+ * zero padded to out_max.
+ * amdspeech_resample IS amdspeech_resample_rows (below: the definition of the arithmetic, the kernel and the workspace) with every
+ * row at 1000 permille; amdspeech_resample_workspace_bytes(B) is amdspeech_resample_rows_workspace_bytes(B).  What follows from
+ * that: a call with rate_in == rate_out COPIES its rows bit for bit and does not filter them; input at or past n_samples[b] is
+ * not read and may hold anything; and the call refuses, with that call's messages, what that call refuses -- in particular a
+ * ratio rate_out / rate_in outside 1/16 .. 16 (8 kHz .. 192 kHz audio into 16 or 22.05 kHz lies inside) and pcm / out ranges
+ * that overlap.  Until the two calls shared a kernel this one had a kernel of its own that summed the same taps in another order: the
+ * bits of resampled audio differ from that kernel's in the last places (either is within 2e-5 of the float64 oracle).            */
 size_t amdspeech_resample_workspace_bytes(int B);
 int amdspeech_resample_num_samples(int n_samples, int rate_in, int rate_out);
 int amdspeech_resample(void* stream, const float* pcm, const int* n_samples, int B, int n_max, int rate_in,
                        int rate_out, float* out, int out_max, void* ws);
 
 /* ------------------------------------------- per-row resampler / speed perturbation ---
- * The resampler above with a ratio of its own for every row, in ONE launch (no reference counterpart: an opt-in deviation, the
- * three-way speed perturbation of Ko et al. 2015 on the waveform, in front of the front end; off unless a caller makes this call).
+ * The resampler: one kernel, a ratio of its own for every row, in ONE launch.  amdspeech_resample above is this call with every row
+ * at 1000 permille; other speeds have no reference counterpart (an opt-in deviation, the three-way speed perturbation of Ko et al.
+ * 2015 on the waveform, in front of the front end; off unless a caller asks for it).
  * A signal played f times faster is the signal resampled from rate * f to rate, so rate conversion and speed change are one pass.
  *   pcm            float [B][n_max] (DEVICE);  out  float [B][out_max] (DEVICE)
  *   n_samples      int32 [B] (HOST) valid samples per row, 0 .. n_max
  *   speed_permille int32 [B] (HOST) the row's speed in thousandths, 500 .. 2000 (0.5x .. 2.0x); 1000 = rate conversion only
  * Speed.  num = rate_out * 1000 and den = rate_in * speed_permille as 64-bit integers; ratio = (double)num / (double)den, ONE
- * double division of the two integers (at 1000 permille the same double as amdspeech_resample's rate_out / rate_in).
+ * double division of the two integers (at 1000 permille the same double as rate_out / rate_in).
  * Row lengths.  Row b receives n_total = ceil(n * num / den) samples, in exact integer arithmetic
  * (amdspeech_resample_rows_num_samples); a call with n_max * num >= 2^53 is refused.  Under that limit this equals
  * amdspeech_resample_num_samples' ceil((double)n * rate_out / rate_in) at 1000 permille.
- * Output arithmetic.  The first n_out = (int)((double)n * ratio) samples of a row are resampy's "kaiser_best" interpolation exactly
- * as amdspeech_resample computes it -- the same table win[j], delta[j] (here stored WITHOUT the gain), scale = min(1, ratio),
+ * Output arithmetic.  The first n_out = (int)((double)n * ratio) samples of a row are resampy's "kaiser_best" interpolation: the
+ * table win[j] = kaiser(j) * rolloff * sinc(rolloff * j / 512), delta[j] = win[j + 1] - win[j] (stored WITHOUT the gain), scale = min(1, ratio),
  * step = (int)(scale * 512), and for output t:  tr = (double)t / ratio, k = (int)tr, frac = scale * (tr - k), off = (int)(frac * 512),
  * eta = frac * 512 - off; the left wing sums (win[off + i step] + eta delta[off + i step]) * x[k - i] over i < min(k + 1,
  * (32769 - off) / step), the right wing the same with frac' = scale - frac over x[k + 1 + i], i < min(n - k - 1, (32769 - off') / step)

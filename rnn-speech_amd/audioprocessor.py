@@ -195,23 +195,20 @@ class AudioProcessor(object):
         on host threads (or passed in as `decoded` [(signal, sr), ...]), uploaded once, resampled to
         22,050 Hz on the GPU per source rate and handed to the front-end kernels without leaving HBM.
         `rows` > len(files) pads the batch with empty utterances (length 0).  Model frames as process_batch.
-        speed_permille: a speed factor per file (speed perturbation); per source rate ONE ops.resample_rows call then does the rate
-        conversion and the speed change together, and a group whose rows all have ratio 1 makes no call.  A row made longer than
+        speed_permille: a speed factor per file (speed perturbation, None: 1000 each); per source rate ONE ops.resample_rows call does
+        the rate conversion and the speed change together, and a group whose rows all have ratio 1 makes no call.  A row made longer than
         max_input_seq_length is truncated by the front end like any over-long file."""
         t_out, t_max = t_max, self._source_t_max(t_max)
         if decoded is None:
             decoded = decode_files(file_names)
         B = rows or len(decoded)
-        speeds = self._speeds(speed_permille, len(decoded))
+        speeds = self._speeds(speed_permille, len(decoded)) or [1000] * len(decoded)
         if staged is None:
             staged = self.stage_files(decoded)
         parts, lengths = [], [0] * B
         for sr, idx, block, n in staged:
             pcm = self._upload_staged(block)
-            if speeds is not None:
-                pcm, n = self._resampled(pcm, n, [speeds[i] for i in idx], sr, self.load_sr)
-            elif sr != self.load_sr:
-                pcm, n = ops.resample(pcm, n, sr, self.load_sr)
+            pcm, n = self._resampled(pcm, n, [speeds[i] for i in idx], sr, self.load_sr)
             parts.append((idx, pcm, n))
         width = max(max(p[1].shape[1] for p in parts), 1) if parts else 1
         if len(parts) == 1 and len(parts[0][0]) == B:

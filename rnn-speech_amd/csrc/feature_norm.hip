@@ -20,20 +20,18 @@
 // fixed 4096 V bytes of static LDS whatever D (no dynamic LDS, no attribute call).  V = 4: 16-byte loads and stores.
 // No atomics: the slots' partials meet in LDS and are summed in slot order, the slices' in slice order -- two runs give the same
 // bits.  Frames at or past n are neither read nor written; a row with n = 0 is not touched.
-#include "common.h"
+#include "row_args.h"
 
 #include <cmath>
 
 
 namespace amdspeech {
 
-constexpr int FN_META_MAX = 256;          // rows whose lengths travel as kernel arguments (frame_stack.hip: FS_META_MAX)
 constexpr int FN_THREADS = 256;
 constexpr int FN_MAX_WGS = 2048;          // cap of the grid, as the sibling kernels cap theirs; rows beyond it are strided
 constexpr int FN_TARGET_WGS = 512;        // two workgroups per CU: what `split` aims for when the rows alone are fewer
 constexpr int FN_MIN_PASSES = 4;          // a slice is no shorter than this many frame-slot passes
 constexpr int FN_MAX_WIDTH = 4096;        // D (frame_stack.hip: FS_MAX_WIDTH)
-struct FnLenArg { int v[FN_META_MAX]; };
 
 typedef amdspeech_feature_norm_plan_info FnPlan;
 typedef amdspeech_feature_norm_desc FnDesc;
@@ -58,7 +56,7 @@ static __device__ inline void fn_load(const float* p, float (&v)[V]) {
 }
 
 template <int V, bool LEN_ARG>
-__global__ __launch_bounds__(FN_THREADS) void feature_moments_kernel(const float* __restrict__ x, FnLenArg len_arg,
+__global__ __launch_bounds__(FN_THREADS) void feature_moments_kernel(const float* __restrict__ x, RowArgs len_arg,
                                                                      const int* __restrict__ len_dev, int B, int D, int t_in, int slice,
                                                                      int lanes, double* __restrict__ ws) {
     __shared__ double red[FN_THREADS * 2 * V];             // [slot][lane][S' x V, Q' x V]
@@ -66,7 +64,7 @@ __global__ __launch_bounds__(FN_THREADS) void feature_moments_kernel(const float
     const int slot = threadIdx.x / lanes, lane = threadIdx.x - slot * lanes;
     const int s = blockIdx.x, split = gridDim.x;
     for (int b = blockIdx.y; b < B; b += gridDim.y) {
-        int n = LEN_ARG ? len_arg.v[b] : len_dev[b];
+        int n = row_arg<LEN_ARG>(len_arg, len_dev, b);
         n = n < t_in ? n : t_in;                           // (the front end's counts are not clipped to its t_max)
         const int t0 = s * slice;
         int t1 = t0 + slice;
@@ -115,7 +113,7 @@ __global__ __launch_bounds__(FN_THREADS) void feature_moments_kernel(const float
 }
 
 template <int V, bool GLOBAL, bool LEN_ARG>
-__global__ __launch_bounds__(FN_THREADS) void feature_norm_apply_kernel(float* __restrict__ x, FnLenArg len_arg,
+__global__ __launch_bounds__(FN_THREADS) void feature_norm_apply_kernel(float* __restrict__ x, RowArgs len_arg,
                                                                         const int* __restrict__ len_dev, int B, int D, int t_in,
                                                                         int slice, int lanes, const double* __restrict__ src,
                                                                         int norm_vars, double var_floor) {
@@ -124,7 +122,7 @@ __global__ __launch_bounds__(FN_THREADS) void feature_norm_apply_kernel(float* _
     const int slot = threadIdx.x / lanes, lane = threadIdx.x - slot * lanes;
     const int s = blockIdx.x, split = gridDim.x;
     for (int b = blockIdx.y; b < B; b += gridDim.y) {
-        int n = LEN_ARG ? len_arg.v[b] : len_dev[b];
+        int n = row_arg<LEN_ARG>(len_arg, len_dev, b);
         n = n < t_in ? n : t_in;
         const int t0 = s * slice;
         int t1 = t0 + slice;
@@ -183,13 +181,13 @@ __global__ __launch_bounds__(FN_THREADS) void feature_norm_apply_kernel(float* _
 
 // moments[b] = [mean[D], M2[D]],  M2 = sum (x - mean)^2 = Q' - S'^2 / n;  zeros for n = 0.  One thread per (row, dim).
 template <bool LEN_ARG>
-__global__ __launch_bounds__(FN_THREADS) void feature_moments_finish_kernel(const double* __restrict__ ws, FnLenArg len_arg,
+__global__ __launch_bounds__(FN_THREADS) void feature_moments_finish_kernel(const double* __restrict__ ws, RowArgs len_arg,
                                                                             const int* __restrict__ len_dev, int B, int D, int t_in,
                                                                             int split, double* __restrict__ moments) {
     const long total = (long)B * D;
     for (long e = (long)blockIdx.x * FN_THREADS + threadIdx.x; e < total; e += (long)gridDim.x * FN_THREADS) {
         const int b = (int)(e / D), d = (int)(e - (long)b * D);
-        int n = LEN_ARG ? len_arg.v[b] : len_dev[b];
+        int n = row_arg<LEN_ARG>(len_arg, len_dev, b);
         n = n < t_in ? n : t_in;
         double mean = 0.0, m2 = 0.0;
         if (n > 0) {
@@ -225,7 +223,7 @@ static int plan_feature_norm(int B, int D, int t_in, int mode, FnPlan* p) {
     p->split = ceil_div(t_in, slice);                               // (no empty slice)
     p->workgroups = mode == AMDSPEECH_FEATURE_NORM_NONE ? 0 : p->split * rows;
     p->lds_bytes = FN_THREADS * 2 * p->vec * (int)sizeof(double);
-    p->meta_by_copy = B > FN_META_MAX ? 1 : 0;
+    p->meta_by_copy = B > ROW_ARGS_MAX ? 1 : 0;
     const long bytes = mode == AMDSPEECH_FEATURE_NORM_UTTERANCE ? (long)B * fn_row_doubles(p->split, D) * (long)sizeof(double) : 0;
     AS_CHECK_ARG(bytes < (1L << 31), "feature_norm: the workspace of B %d, D %d would take %ld bytes", B, D, bytes);
     p->workspace_bytes = (int)bytes;
@@ -243,7 +241,7 @@ static int check_lengths(const int* n_frames, int B) {
 enum { FN_UTTERANCE = 0, FN_GLOBAL = 1, FN_MOMENTS = 2 };
 
 template <int V, bool LEN_ARG>
-static hipError_t launch_feature_norm(hipStream_t s, int what, const FnPlan& pl, float* x, const FnLenArg& la, const int* d_len, int B, int D,
+static hipError_t launch_feature_norm(hipStream_t s, int what, const FnPlan& pl, float* x, const RowArgs& la, const int* d_len, int B, int D,
                                       int t_in, const FnDesc* desc, const double* table, double* ws, double* moments) {
     const int rows = B < FN_MAX_WGS ? B : FN_MAX_WGS;
     const dim3 grid(pl.split, rows), block(FN_THREADS);
@@ -277,27 +275,12 @@ static int run_feature_norm(hipStream_t s, int what, float* x, const int* n_fram
                  "feature_norm: the float64 buffers must be 8-byte aligned");
     if (int rc = check_lengths(n_frames, B)) return rc;
 
-    FnLenArg la;
-    int* d_len = nullptr;
-    if (!pl.meta_by_copy) {
-        for (int b = 0; b < FN_META_MAX; ++b) la.v[b] = b < B ? n_frames[b] : 0;
-        AS_CHECK_HIP(pl.vec == 4 ? (launch_feature_norm<4, true>(s, what, pl, x, la, d_len, B, D, t_in, desc, table, ws, moments))
-                                 : (launch_feature_norm<1, true>(s, what, pl, x, la, d_len, B, D, t_in, desc, table, ws, moments)));
-        return AMDSPEECH_OK;
-    }
-    // more rows than the argument block holds: the lengths go through a device buffer of the call's own, and the call waits for
-    // the kernels before it gives the buffer back (frame_stack.hip does the same)
-    for (int b = 0; b < FN_META_MAX; ++b) la.v[b] = 0;
-    AS_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&d_len), (size_t)B * sizeof(int)));
-    hipError_t e = hipMemcpyAsync(d_len, n_frames, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = pl.vec == 4 ? launch_feature_norm<4, false>(s, what, pl, x, la, d_len, B, D, t_in, desc, table, ws, moments)
-                        : launch_feature_norm<1, false>(s, what, pl, x, la, d_len, B, D, t_in, desc, table, ws, moments);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    const hipError_t ef = hipFree(d_len);
-    AS_CHECK_HIP(e);
-    AS_CHECK_HIP(ef);
-    return AMDSPEECH_OK;
+    // (more rows than the argument block holds: with_row_args waits for the kernels, as frame_stack.hip's call does)
+    return with_row_args(s, n_frames, B, [&](auto by_arg, const RowArgs& la, const int* d_len) {
+        constexpr bool LEN_ARG = decltype(by_arg)::value;
+        return pl.vec == 4 ? launch_feature_norm<4, LEN_ARG>(s, what, pl, x, la, d_len, B, D, t_in, desc, table, ws, moments)
+                           : launch_feature_norm<1, LEN_ARG>(s, what, pl, x, la, d_len, B, D, t_in, desc, table, ws, moments);
+    });
 }
 
 }  // namespace amdspeech

@@ -8,19 +8,16 @@
 // under a grid-stride loop, no LDS, no atomics.  The words travel as unsigned integers: whatever bit pattern the front end wrote
 // (-0.0, denormals, infinities, NaN payloads) arrives unchanged.  The kernel masks by the row's own length and never reads a
 // source frame at or past it, so what the source holds there does not matter; it writes EVERY word of `out`.
-#include "common.h"
-
+#include "row_args.h"
 
 namespace amdspeech {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int FS_META_MAX = 256;          // rows whose lengths travel as kernel arguments (frontend.hip: META_MAX)
 constexpr int FS_THREADS = 256;
 constexpr int FS_MAX_WGS = 2048;          // a streaming kernel: cap the grid and stride the rest
 constexpr int FS_MAX_FACTOR = 16;         // stack, skip
 constexpr int FS_MAX_WIDTH = 4096;        // stack * D
-struct FsLenArg { int v[FS_META_MAX]; };
 
 // Lanes that share one (model frame, row) item: the smallest power of two that covers its `units` vector words, at most a workgroup.
 static __host__ __device__ inline int fs_lanes_per_item(int units) {
@@ -32,7 +29,7 @@ static __host__ __device__ inline int fs_lanes_per_item(int units) {
 // One item = the d_out words of out[j][b]; FS_THREADS / lanes items per workgroup and pass.  V: words per lane and access (4 or 1).
 template <int V, bool LEN_ARG>
 __global__ __launch_bounds__(FS_THREADS) void frame_stack_kernel(const unsigned* __restrict__ x, unsigned* __restrict__ out,
-                                                                 FsLenArg len_arg, const int* __restrict__ len_dev, int B, int D,
+                                                                 RowArgs len_arg, const int* __restrict__ len_dev, int B, int D,
                                                                  int t_in, int stack, int skip, int t_out, int lanes) {
     const int dv = D / V;                          // vector words per source frame
     const int units = stack * dv;                  // ... per item
@@ -41,7 +38,7 @@ __global__ __launch_bounds__(FS_THREADS) void frame_stack_kernel(const unsigned*
     const long n_items = (long)t_out * B;
     for (long item = (long)blockIdx.x * per_wg + sub; item < n_items; item += (long)gridDim.x * per_wg) {
         const int j = (int)(item / B), b = (int)(item - (long)j * B);
-        int n = LEN_ARG ? len_arg.v[b] : len_dev[b];
+        int n = row_arg<LEN_ARG>(len_arg, len_dev, b);
         n = n < t_in ? n : t_in;                   // (the front end's counts are not clipped to its t_max)
         const int t0 = j * skip;
         unsigned* o = out + item * ((long)units * V);
@@ -76,7 +73,7 @@ static int plan_frame_stack(int B, int D, int t_in, int stack, int skip, FsPlan*
     const int per_wg = FS_THREADS / fs_lanes_per_item(p->d_out / p->vec);
     const long wgs = ((long)p->t_out * B + per_wg - 1) / per_wg;
     p->workgroups = (int)(wgs < FS_MAX_WGS ? wgs : FS_MAX_WGS);
-    p->meta_by_copy = B > FS_META_MAX ? 1 : 0;
+    p->meta_by_copy = B > ROW_ARGS_MAX ? 1 : 0;
     return AMDSPEECH_OK;
 }
 
@@ -96,38 +93,17 @@ static int run_frame_stack(hipStream_t s, const float* x, const int* n_frames, i
     const unsigned* xs = reinterpret_cast<const unsigned*>(x);
     unsigned* os = reinterpret_cast<unsigned*>(out);
     const int lanes = fs_lanes_per_item(pl.d_out / pl.vec);
-    FsLenArg la;
-    int* d_len = nullptr;
-    if (!pl.meta_by_copy) {
-        for (int b = 0; b < FS_META_MAX; ++b) la.v[b] = b < B ? n_frames[b] : 0;
+    // (more rows than the argument block holds: with_row_args waits for the kernel, as the front end's wide-batch path does)
+    return with_row_args(s, n_frames, B, [&](auto by_arg, const RowArgs& la, const int* d_len) {
+        constexpr bool LEN_ARG = decltype(by_arg)::value;
         if (pl.vec == 4)
-            hipLaunchKernelGGL((frame_stack_kernel<4, true>), dim3(pl.workgroups), dim3(FS_THREADS), 0, s, xs, os, la, d_len, B, D, t_in,
+            hipLaunchKernelGGL((frame_stack_kernel<4, LEN_ARG>), dim3(pl.workgroups), dim3(FS_THREADS), 0, s, xs, os, la, d_len, B, D, t_in,
                                stack, skip, pl.t_out, lanes);
         else
-            hipLaunchKernelGGL((frame_stack_kernel<1, true>), dim3(pl.workgroups), dim3(FS_THREADS), 0, s, xs, os, la, d_len, B, D, t_in,
+            hipLaunchKernelGGL((frame_stack_kernel<1, LEN_ARG>), dim3(pl.workgroups), dim3(FS_THREADS), 0, s, xs, os, la, d_len, B, D, t_in,
                                stack, skip, pl.t_out, lanes);
-        AS_CHECK_LAUNCH();
-        return AMDSPEECH_OK;
-    }
-    // more rows than the argument block holds: the lengths go through a device buffer of the call's own, and the call waits for
-    // the kernel before it gives the buffer back (the front end's wide-batch path synchronises the stream too)
-    for (int b = 0; b < FS_META_MAX; ++b) la.v[b] = 0;
-    AS_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&d_len), (size_t)B * sizeof(int)));
-    hipError_t e = hipMemcpyAsync(d_len, n_frames, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        if (pl.vec == 4)
-            hipLaunchKernelGGL((frame_stack_kernel<4, false>), dim3(pl.workgroups), dim3(FS_THREADS), 0, s, xs, os, la, d_len, B, D, t_in,
-                               stack, skip, pl.t_out, lanes);
-        else
-            hipLaunchKernelGGL((frame_stack_kernel<1, false>), dim3(pl.workgroups), dim3(FS_THREADS), 0, s, xs, os, la, d_len, B, D, t_in,
-                               stack, skip, pl.t_out, lanes);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    const hipError_t ef = hipFree(d_len);
-    AS_CHECK_HIP(e);
-    AS_CHECK_HIP(ef);
-    return AMDSPEECH_OK;
+        return hipGetLastError();
+    });
 }
 
 }  // namespace amdspeech

@@ -11,7 +11,7 @@
 // utterance maximum for mfcc, per-filter mean for fbank) force a second pass, which
 // also applies the DCT (mfcc) or the 9-tap Savitzky-Golay deltas (fbank) and writes
 // the time-major [T, B, D] batch the LSTM consumes.
-#include "common.h"
+#include "row_args.h"
 #include <math.h>
 #include <map>
 #include <mutex>
@@ -685,11 +685,20 @@ __global__ void fbank_pass_kernel(float* __restrict__ logmel, float* __restrict_
 }
 
 // Host-side length vectors reach the device as KERNEL ARGUMENTS of a one-block kernel (no pageable
-// H2D copy, no stream synchronisation on the hot path); batches wider than META_MAX fall back to a copy.
-constexpr int META_MAX = 256;
-struct MetaArg { int v[2 * META_MAX]; };
+// H2D copy, no stream synchronisation on the hot path), two values per row of row_args.h's block a launch; the front end's own
+// batches wider than ROW_ARGS_MAX fall back to a copy.
+struct MetaArg { int v[2 * ROW_ARGS_MAX]; };
 __global__ void write_meta_kernel(MetaArg m, int* dst, int n) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = m.v[i];
+}
+// dst[0 .. count) = src[0 .. count), stream-ordered: one launch per 2 * ROW_ARGS_MAX values
+static void write_ints(hipStream_t s, int* dst, const int* src, int count) {
+    for (int i0 = 0; i0 < count; i0 += 2 * ROW_ARGS_MAX) {
+        MetaArg m;
+        const int cnt = count - i0 < 2 * ROW_ARGS_MAX ? count - i0 : 2 * ROW_ARGS_MAX;
+        for (int i = 0; i < cnt; ++i) m.v[i] = src[i0 + i];
+        hipLaunchKernelGGL(write_meta_kernel, dim3(1), dim3(256), 0, s, m, dst + i0, cnt);
+    }
 }
 
 // ---- the plan: which kernels a call takes and their launch geometry, as plain numbers (amdspeech.h: amdspeech_frontend_plan_info).
@@ -734,7 +743,7 @@ static int plan_frontend(int mode, int sr, int n_mfcc, int B, int n_max, int t_m
     }
     p->dct_kernel = mode == MODE_FBANK ? -1 : on_mfma ? 1 : 0;
     p->dct_col_tiles = p->dct_kernel == 1 ? (n_mfcc + 15) / 16 : 0;
-    p->meta_by_copy = B > META_MAX ? 1 : 0;
+    p->meta_by_copy = B > ROW_ARGS_MAX ? 1 : 0;
     return AMDSPEECH_OK;
 }
 
@@ -770,9 +779,7 @@ static int run_frontend(hipStream_t s, int mode, const float* pcm, const int* n_
     }
     int* d_n = reinterpret_cast<int*>(w + lo.total);          // workspace_bytes() reserves 2*B ints past `total`
     if (!pl.meta_by_copy) {
-        MetaArg ma;
-        for (int i = 0; i < 2 * B; ++i) ma.v[i] = meta[i];
-        hipLaunchKernelGGL(write_meta_kernel, dim3(1), dim3(256), 0, s, ma, d_n, 2 * B);
+        write_ints(s, d_n, meta.data(), 2 * B);
     } else {
         AS_CHECK_HIP(hipMemcpyAsync(d_n, meta.data(), 2 * B * sizeof(int), hipMemcpyHostToDevice, s));
         AS_CHECK_HIP(hipStreamSynchronize(s));                  // `meta` is a stack-scoped staging buffer
@@ -867,116 +874,20 @@ __device__ double bessel_i0(double x) {
     return sum;
 }
 
-// win[i] = kaiser(i) * rolloff * sinc(rolloff * i / 512), scaled by min(1, ratio); delta[i] = win[i+1] - win[i]
-__global__ void resample_table_kernel(float* __restrict__ win, float* __restrict__ delta, double gain) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= RS_NWIN) return;
-    auto tap = [&](int j) -> double {
-        if (j >= RS_NWIN) return 0.0;
-        const double r = (double)j / (double)(RS_NWIN - 1);
-        const double kaiser = bessel_i0(RS_BETA * sqrt(fmax(0.0, 1.0 - r * r))) / bessel_i0(RS_BETA);
-        const double z = RS_ROLLOFF * (double)j / (double)RS_TABLE * M_PI;
-        const double sinc = j == 0 ? 1.0 : sin(z) / z;
-        return gain * RS_ROLLOFF * sinc * kaiser;
-    };
-    const double w0 = tap(i), w1 = tap(i + 1);
-    win[i] = (float)w0;
-    delta[i] = i + 1 < RS_NWIN ? (float)(w1 - w0) : 0.0f;
-}
-
-__global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x, const int* __restrict__ n_in,
-                                                       int in_stride, float* __restrict__ y, int out_stride,
-                                                       double ratio, const float* __restrict__ win,
-                                                       const float* __restrict__ delta) {
-    const int b = blockIdx.y;
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= out_stride) return;
-    const int n_orig = n_in[b];
-    const int n_out = (int)((double)n_orig * ratio);           // samples resampy computes; the rest is padding
-    float acc = 0.0f;
-    if (t < n_out) {
-        const float* xb = x + (size_t)b * in_stride;
-        const double scale = ratio < 1.0 ? ratio : 1.0;
-        const int step = (int)(scale * RS_TABLE);
-        const double tr = (double)t / ratio;
-        const int n = (int)tr;
-        double frac = scale * (tr - (double)n);
-        double idx = frac * RS_TABLE;
-        int off = (int)idx;
-        float eta = (float)(idx - (double)off);
-        int cnt = min(n + 1, (RS_NWIN - off) / step);
-        for (int i = 0; i < cnt; ++i) {                        // left wing: x[n], x[n-1], ...
-            const int j = off + i * step;
-            acc += (win[j] + eta * delta[j]) * xb[n - i];
-        }
-        frac = scale - frac;
-        idx = frac * RS_TABLE;
-        off = (int)idx;
-        eta = (float)(idx - (double)off);
-        cnt = min(n_orig - n - 1, (RS_NWIN - off) / step);
-        for (int k = 0; k < cnt; ++k) {                        // right wing: x[n+1], x[n+2], ...
-            const int j = off + k * step;
-            acc += (win[j] + eta * delta[j]) * xb[n + k + 1];
-        }
-    }
-    y[(size_t)b * out_stride + t] = acc;
-}
-}  // namespace amdspeech
-
-extern "C" size_t amdspeech_resample_workspace_bytes(int B) {
-    return B > 0 ? amdspeech::align_up((size_t)2 * amdspeech::RS_NWIN * sizeof(float), 256) + amdspeech::align_up((size_t)B * 4, 256) : 0;
-}
-
-extern "C" int amdspeech_resample_num_samples(int n_samples, int rate_in, int rate_out) {
-    if (n_samples < 0 || rate_in <= 0 || rate_out <= 0) return AMDSPEECH_EINVAL;
-    return (int)ceil((double)n_samples * (double)rate_out / (double)rate_in);
-}
-
-extern "C" int amdspeech_resample(void* stream, const float* pcm, const int* n_samples, int B, int n_max, int rate_in,
-                                  int rate_out, float* out, int out_max, void* ws) {
-    using namespace amdspeech;
-    AS_CHECK_ARG(pcm && n_samples && out && ws, "resample: null pointer");
-    AS_CHECK_ARG(B > 0 && n_max > 0 && out_max > 0 && rate_in > 0 && rate_out > 0, "resample: bad shape");
-    const double ratio = (double)rate_out / (double)rate_in;
-    for (int b = 0; b < B; ++b) {
-        AS_CHECK_ARG(n_samples[b] >= 0 && n_samples[b] <= n_max, "resample: n_samples[%d] = %d exceeds n_max %d", b, n_samples[b], n_max);
-        AS_CHECK_ARG((int)ceil((double)n_samples[b] * ratio) <= out_max, "resample: output row %d needs more than %d samples", b, out_max);
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float* win = static_cast<float*>(ws);
-    float* delta = win + RS_NWIN;
-    int* n_dev = reinterpret_cast<int*>(static_cast<char*>(ws) + align_up((size_t)2 * RS_NWIN * sizeof(float), 256));
-    hipLaunchKernelGGL(resample_table_kernel, dim3(ceil_div(RS_NWIN, 256)), dim3(256), 0, s, win, delta,
-                       ratio < 1.0 ? ratio : 1.0);
-    // lengths travel as kernel arguments of a one-block kernel (stream-ordered, no host sync)
-    for (int b0 = 0; b0 < B; b0 += 2 * META_MAX) {
-        MetaArg m;
-        const int cnt = B - b0 < 2 * META_MAX ? B - b0 : 2 * META_MAX;
-        for (int i = 0; i < cnt; ++i) m.v[i] = n_samples[b0 + i];
-        hipLaunchKernelGGL(write_meta_kernel, dim3(1), dim3(256), 0, s, m, n_dev + b0, cnt);
-    }
-    hipLaunchKernelGGL(resample_kernel, dim3(ceil_div(out_max, 256), B), dim3(256), 0, s, pcm, n_dev, n_max, out, out_max,
-                       ratio, win, delta);
-    AS_CHECK_LAUNCH();
-    return AMDSPEECH_OK;
-}
-
-// ------------------------------------------------------------------- per-row resampler (speed perturbation)
-// The resampler above with a ratio per ROW in one launch (amdspeech.h: amdspeech_resample_rows): a row's speed in permille scales
-// its input rate, ratio = (rate_out * 1000) / (rate_in * permille).  Same arithmetic per tap as resample_kernel; what differs:
+// One kernel, a ratio per ROW in one launch (amdspeech.h: amdspeech_resample_rows; amdspeech_resample is that call with every row at
+// 1000 permille): a row's speed in permille scales its input rate, ratio = (rate_out * 1000) / (rate_in * permille).
 //   - the table holds (win, delta) PAIRS without the gain; a row's gain min(1, ratio) multiplies the finished sum;
 //   - a workgroup owns RR_TILE consecutive outputs of one row (RR_OUTS per thread) and stages the input span they reach in LDS once
 //     (consecutive outputs share all but one or two of their ~128 / min(1, ratio) taps): the taps read LDS, not global memory;
-//   - the table goes through LDS too.  resample_kernel gathers it from global memory -- 64 lanes, 64 phases, up to 32 cache lines per
-//     load -- and that gather is where its time goes.  Tap i of either wing of every output of a row reads table[off + i * step] with
+//   - the table goes through LDS too.  Gathered from global memory -- 64 lanes, 64 phases, up to 32 cache lines per load -- it is
+//     where a thread-per-output kernel's time goes.  Tap i of either wing of every output of a row reads table[off + i * step] with
 //     off in 0 .. step, so the taps i0 .. i0 + ch - 1 of ALL outputs of a tile lie in the ch * step + 1 entries from i0 * step on: the
 //     workgroup stages that chunk with coalesced loads (ch = RR_CHUNK / step taps, at most RR_CHUNK + 1 entries = 32 KiB), every
 //     thread gathers its taps of both wings from LDS, and the next chunk follows: the whole table once per tile of 1024 outputs;
 //   - a row with num == den is copied bit for bit, a tile at or past the row's length stores zeros: both branches are uniform over
 //     the workgroup.  Every word of `out` is written, no input word at or past the row's length is read.
 // The two wings of an output are summed separately, each in tap order, and added.  No atomics, no order between workgroups: two
-// calls give the same bits.  Measured: 334 us per launch against resample_kernel's 1579 us on the same rows.
-namespace amdspeech {
+// calls give the same bits.  Measured: 334 us per launch against 1579 us of the thread-per-output kernel it replaced.
 constexpr int RR_THREADS = 256, RR_OUTS = 4;       // threads per workgroup, outputs per thread
 constexpr int RR_TILE = RR_THREADS * RR_OUTS;      // outputs per workgroup
 constexpr int RR_CHUNK = 4096;                     // table entries per staged chunk (+ 1)
@@ -1007,7 +918,7 @@ static inline int rr_span(int n, const RowRatio& r) {
     return (int)(s < n ? s : n);
 }
 
-// table[i] = (win[i], delta[i]) of resample_table_kernel at gain 1
+// table[i] = (win[i], delta[i]): win[i] = kaiser(i) * rolloff * sinc(rolloff * i / 512), delta[i] = win[i+1] - win[i]
 __global__ void resample_rows_table_kernel(float2* __restrict__ table) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= RS_NWIN) return;
@@ -1156,7 +1067,33 @@ static int plan_resample_rows(const int* n_samples, const int* permille, int B, 
     p->table_chunk = span > 0 ? RR_CHUNK + 1 : 0;
     p->lds_bytes = (span + 3) / 4 * 16 + p->table_chunk * 8;
     p->any_copy = any_copy;
-    p->meta_launches = ceil_div(2L * B, 2 * META_MAX);
+    p->meta_launches = ceil_div(2L * B, 2 * ROW_ARGS_MAX);
+    return AMDSPEECH_OK;
+}
+
+static int run_resample_rows(hipStream_t s, const float* pcm, const int* n_samples, const int* speed_permille, int B, int n_max,
+                             int rate_in, int rate_out, float* out, int out_max, void* ws) {
+    AS_CHECK_ARG(pcm && n_samples && speed_permille && out && ws, "resample_rows: null pointer");
+    RowsPlan pl;
+    if (int rc = plan_resample_rows(n_samples, speed_permille, B, n_max, rate_in, rate_out, out_max, &pl)) return rc;
+    const uintptr_t p0 = reinterpret_cast<uintptr_t>(pcm), p1 = p0 + (size_t)B * n_max * 4;
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + (size_t)B * out_max * 4;
+    AS_CHECK_ARG(p1 <= o0 || o1 <= p0, "resample_rows: pcm and out overlap");
+    float2* table = static_cast<float2*>(ws);
+    int* meta = reinterpret_cast<int*>(static_cast<char*>(ws) + align_up((size_t)RS_NWIN * sizeof(float2), 256));
+    hipLaunchKernelGGL(resample_rows_table_kernel, dim3(ceil_div(RS_NWIN, 256)), dim3(256), 0, s, table);
+    // lengths, then speeds, as kernel arguments of one-block kernels (stream-ordered, no host sync), 512 values each
+    std::vector<int> host_meta(n_samples, n_samples + B);
+    host_meta.insert(host_meta.end(), speed_permille, speed_permille + B);
+    write_ints(s, meta, host_meta.data(), 2 * B);
+    static unsigned long long rows_lds_seen = 0;
+    if (DeviceOnce once{&rows_lds_seen}) {
+        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(resample_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, RR_LDS_MAX));
+        once.done();
+    }
+    hipLaunchKernelGGL(resample_rows_kernel, dim3(pl.tiles_per_row, B), dim3(RR_THREADS), (size_t)pl.lds_bytes, s, pcm, meta, B, n_max,
+                       out, out_max, rate_in, rate_out, table, pl.span_max);
+    AS_CHECK_LAUNCH();
     return AMDSPEECH_OK;
 }
 }  // namespace amdspeech
@@ -1186,33 +1123,24 @@ extern "C" int amdspeech_resample_rows_plan(const int* n_samples, const int* spe
 
 extern "C" int amdspeech_resample_rows(void* stream, const float* pcm, const int* n_samples, const int* speed_permille, int B,
                                        int n_max, int rate_in, int rate_out, float* out, int out_max, void* ws) {
-    using namespace amdspeech;
-    AS_CHECK_ARG(pcm && n_samples && speed_permille && out && ws, "resample_rows: null pointer");
-    RowsPlan pl;
-    if (int rc = plan_resample_rows(n_samples, speed_permille, B, n_max, rate_in, rate_out, out_max, &pl)) return rc;
-    const uintptr_t p0 = reinterpret_cast<uintptr_t>(pcm), p1 = p0 + (size_t)B * n_max * 4;
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + (size_t)B * out_max * 4;
-    AS_CHECK_ARG(p1 <= o0 || o1 <= p0, "resample_rows: pcm and out overlap");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float2* table = static_cast<float2*>(ws);
-    int* meta = reinterpret_cast<int*>(static_cast<char*>(ws) + align_up((size_t)RS_NWIN * sizeof(float2), 256));
-    hipLaunchKernelGGL(resample_rows_table_kernel, dim3(ceil_div(RS_NWIN, 256)), dim3(256), 0, s, table);
-    // lengths, then speeds, as kernel arguments of one-block kernels (stream-ordered, no host sync), 512 values each
-    for (int v0 = 0; v0 < 2 * B; v0 += 2 * META_MAX) {
-        MetaArg m;
-        const int cnt = 2 * B - v0 < 2 * META_MAX ? 2 * B - v0 : 2 * META_MAX;
-        for (int i = 0; i < cnt; ++i) m.v[i] = v0 + i < B ? n_samples[v0 + i] : speed_permille[v0 + i - B];
-        hipLaunchKernelGGL(write_meta_kernel, dim3(1), dim3(256), 0, s, m, meta + v0, cnt);
-    }
-    static unsigned long long rows_lds_seen = 0;
-    if (DeviceOnce once{&rows_lds_seen}) {
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(resample_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, RR_LDS_MAX));
-        once.done();
-    }
-    hipLaunchKernelGGL(resample_rows_kernel, dim3(pl.tiles_per_row, B), dim3(RR_THREADS), (size_t)pl.lds_bytes, s, pcm, meta, B, n_max,
-                       out, out_max, rate_in, rate_out, table, pl.span_max);
-    AS_CHECK_LAUNCH();
-    return AMDSPEECH_OK;
+    return run_resample_rows(static_cast<hipStream_t>(stream), pcm, n_samples, speed_permille, B, n_max, rate_in, rate_out, out,
+                             out_max, ws);
+}
+
+// ---- the uniform call: every row at 1000 permille
+extern "C" size_t amdspeech_resample_workspace_bytes(int B) { return amdspeech_resample_rows_workspace_bytes(B); }
+
+extern "C" int amdspeech_resample_num_samples(int n_samples, int rate_in, int rate_out) {
+    if (n_samples < 0 || rate_in <= 0 || rate_out <= 0) return AMDSPEECH_EINVAL;
+    return (int)ceil((double)n_samples * (double)rate_out / (double)rate_in);
+}
+
+extern "C" int amdspeech_resample(void* stream, const float* pcm, const int* n_samples, int B, int n_max, int rate_in,
+                                  int rate_out, float* out, int out_max, void* ws) {
+    AS_CHECK_ARG(B > 0, "resample: bad shape");
+    const std::vector<int> permille((size_t)B, 1000);
+    return run_resample_rows(static_cast<hipStream_t>(stream), pcm, n_samples, permille.data(), B, n_max, rate_in, rate_out, out,
+                             out_max, ws);
 }
 
 extern "C" int amdspeech_speed_perturb_draw(unsigned long long seed, unsigned long long index, const int* factors_permille, int count) {

@@ -44,14 +44,51 @@ def _chk_i32(*ts):
             raise ValueError("expected a contiguous int32 device tensor")
 
 
+def _chk_f32_3d(what, x, dims):
+    """x is a contiguous float32 device tensor of three dimensions (`dims` names them in the message); returns its shape."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+        raise ValueError("%s: expected a contiguous float32 device tensor %s, got %s"
+                         % (what, dims, (x.dtype, x.device, tuple(x.shape), x.stride()) if torch.is_tensor(x) else type(x)))
+    return x.shape
+
+
+def _c_ints(values, B, what):
+    """One C int per row from python ints."""
+    if len(values) != B:
+        raise ValueError("%s: %d values for %d rows" % (what, len(values), B))
+    return (C.c_int * max(B, 1))(*[int(v) for v in values])
+
+
+def _plan_dict(info):
+    """A plan struct of lib.py as a dict of ints."""
+    return {name: int(getattr(info, name)) for name, _ in info._fields_}
+
+
+def _gemm_dims(a_shape, b_shape, trans_a, trans_b):
+    """(M, N, K) of op(A) @ op(B) from the (rows, cols) of the two operands as stored."""
+    M, K = (a_shape[1], a_shape[0]) if trans_a else a_shape
+    K2, N = (b_shape[1], b_shape[0]) if trans_b else b_shape
+    assert K == K2, (tuple(a_shape), tuple(b_shape))
+    return M, N, K
+
+
+def _cached_ws(cache, key, nbytes):
+    """The uint8 device workspace cached under key (its last element is the device); nbytes() sizes a new one.  A cache holds the
+    few shapes a job alternates between: past 8 entries it starts again."""
+    ws = cache.get(key)
+    if ws is None:
+        if len(cache) > 8:
+            cache.clear()
+        ws = cache[key] = torch.empty(nbytes(), device=key[-1], dtype=torch.uint8)
+    return ws
+
+
 # ------------------------------------------------------------------ GEMM / Linear
 def gemm(a, b, trans_a=False, trans_b=False, bias=None, out=None, accumulate=False):
     """C = op(A) @ op(B) (+ bias).  a is [M,K] (or [K,M] if trans_a), b [K,N] (or [N,K])."""
     _chk_f32(bias)
     _chk_f32_rows(a, b, out)
-    M, K = (a.shape[1], a.shape[0]) if trans_a else a.shape
-    K2, N = (b.shape[1], b.shape[0]) if trans_b else b.shape
-    assert K == K2, (a.shape, b.shape)
+    M, N, K = _gemm_dims(a.shape, b.shape, trans_a, trans_b)
     if out is None:
         out = torch.empty(M, N, device=a.device, dtype=torch.float32)
     _l.check(_l.load().amdspeech_gemm_f32(_stream(), int(trans_a), int(trans_b), M, N, K, _p(a), a.stride(0),
@@ -65,9 +102,7 @@ def gemm_bf16x3(a, b, trans_a=False, trans_b=False, bias=None, out=None, accumul
     single=True: plain bf16 operands (one bf16 per value, one MFMA per term: precision = "bf16")."""
     _chk_f32(bias)
     _chk_f32_rows(a, b, out)
-    M, K = (a.shape[1], a.shape[0]) if trans_a else a.shape
-    K2, N = (b.shape[1], b.shape[0]) if trans_b else b.shape
-    assert K == K2, (a.shape, b.shape)
+    M, N, K = _gemm_dims(a.shape, b.shape, trans_a, trans_b)
     if out is None:
         out = torch.empty(M, N, device=a.device, dtype=torch.float32)
     fn = _l.load().amdspeech_gemm_bf16 if single else _l.load().amdspeech_gemm_bf16x3
@@ -97,16 +132,14 @@ def gemm_plan(a, b, trans_a=False, trans_b=False, bias=None, out=None, accumulat
     address, True (an aligned one) or None; colsum: with linear_bwd's fused column sums; count >= 2: gemm_tn_group()."""
     pa, ar, ac, lda = _plan_operand(a)
     pb, br, bc, ldb = _plan_operand(b)
-    M, K = (ac, ar) if trans_a else (ar, ac)
-    K2, N = (bc, br) if trans_b else (br, bc)
-    assert K == K2, ((ar, ac), (br, bc))
+    M, N, K = _gemm_dims((ar, ac), (br, bc), trans_a, trans_b)
     pc, _, _, ldc = _plan_operand(out if out is not None else (M, N))
     pbias = 0 if bias is None or bias is False else (4096 if bias is True else (bias.data_ptr() if torch.is_tensor(bias) else int(bias)))
     info = _l.GemmPlanInfo()
     _l.check(_l.load().amdspeech_gemm_plan(int(precision), int(trans_a), int(trans_b), M, N, K, C.c_void_p(pa), lda, C.c_void_p(pb), ldb,
                                            C.c_void_p(pc), ldc, C.c_void_p(pbias), int(accumulate), int(colsum), int(count), C.byref(info)),
              "gemm_plan")
-    plan = {name: int(getattr(info, name)) for name, _ in _l.GemmPlanInfo._fields_}
+    plan = _plan_dict(info)
     plan["family"] = _l.GEMM_FAMILIES[plan["family"]]
     return plan
 
@@ -147,9 +180,7 @@ def gemm_bf16_packed(a, b, trans_a=False, trans_b=False, bias=None, out=None, ac
     used as given (256-byte aligned, at least the bytes amdspeech_gemm_bf16_packed_scratch_bytes names); None allocates one."""
     _chk_f32(bias)
     _chk_f32_rows(a, b, out)
-    M, K = (a.shape[1], a.shape[0]) if trans_a else a.shape
-    K2, N = (b.shape[1], b.shape[0]) if trans_b else b.shape
-    assert K == K2, (a.shape, b.shape)
+    M, N, K = _gemm_dims(a.shape, b.shape, trans_a, trans_b)
     lib = _l.load()
     n = lib.amdspeech_gemm_bf16_packed_scratch_bytes(int(trans_a), int(trans_b), M, N, K, a.stride(0), b.stride(0))
     if n == 0:
@@ -170,12 +201,10 @@ def gemm_bf16_packed_plan(a, b, trans_a=False, trans_b=False):
     family "bf16p".  a, b: tensors or shapes as _plan_operand takes them.  A shape that is not taken raises."""
     _, ar, ac, lda = _plan_operand(a)
     _, br, bc, ldb = _plan_operand(b)
-    M, K = (ac, ar) if trans_a else (ar, ac)
-    K2, N = (bc, br) if trans_b else (br, bc)
-    assert K == K2, ((ar, ac), (br, bc))
+    M, N, K = _gemm_dims((ar, ac), (br, bc), trans_a, trans_b)
     info = _l.GemmPlanInfo()
     _l.check(_l.load().amdspeech_gemm_bf16_packed_plan(int(trans_a), int(trans_b), M, N, K, lda, ldb, C.byref(info)), "gemm_bf16_packed_plan")
-    plan = {name: int(getattr(info, name)) for name, _ in _l.GemmPlanInfo._fields_}
+    plan = _plan_dict(info)
     plan["family"] = _l.GEMM_FAMILIES[plan["family"]]
     return plan
 
@@ -403,7 +432,7 @@ def lstm_plan(ws, head=None, per_diagonal=False):
                     _l.LSTM_PER_DIAGONAL if per_diagonal else 0)
     info = _l.LstmPlanInfo()
     _l.check(ws.lib.amdspeech_lstm_plan(C.byref(d), c_u[0], c_u[1], C.byref(info)), "lstm_plan")
-    out = {name: int(getattr(info, name)) for name, _ in _l.LstmPlanInfo._fields_}
+    out = _plan_dict(info)
     out["fwd_path"], out["bwd_path"] = _l.LSTM_PATHS[out["fwd_path"]], _l.LSTM_PATHS[out["bwd_path"]]
     return out
 
@@ -703,7 +732,7 @@ def ctc_plan(T, B, C_, U):
     name ("wave", "shift", "pair", "edge").  Read-only: nothing is launched.  A shape the call refuses raises here too."""
     info = _l.CtcPlanInfo()
     _l.check(_l.load().amdspeech_ctc_plan(int(T), int(B), int(C_), int(U), C.byref(info)), "ctc_plan")
-    out = {name: int(getattr(info, name)) for name, _ in _l.CtcPlanInfo._fields_}
+    out = _plan_dict(info)
     out["kernel"] = _l.CTC_KERNELS[out["kernel"]]
     return out
 
@@ -751,7 +780,7 @@ def ctc_align_plan(T, B, C_, U):
     """The recursion kernel ctc_align takes for a shape (amdspeech.h: amdspeech_ctc_align_plan), as ctc_plan reports the loss's."""
     info = _l.CtcPlanInfo()
     _l.check(_l.load().amdspeech_ctc_align_plan(int(T), int(B), int(C_), int(U), C.byref(info)), "ctc_align_plan")
-    out = {name: int(getattr(info, name)) for name, _ in _l.CtcPlanInfo._fields_}
+    out = _plan_dict(info)
     out["kernel"] = _l.CTC_KERNELS[out["kernel"]]
     return out
 
@@ -882,38 +911,13 @@ def audio_decode(path, verify=False):
     return out[:got.value], sr.value
 
 
-_resample_ws = {}
-
-
 def resample(pcm, n_samples, rate_in, rate_out):
     """pcm float32 [B, n_max] (device), n_samples python ints -> (out [B, out_max] device, new lengths):
-    librosa.load's resampling step (resampy kaiser_best semantics), on the GPU."""
-    _chk_f32(pcm)
-    lib = _l.load()
-    B, n_max = pcm.shape
-    n_out = [lib.amdspeech_resample_num_samples(int(n), int(rate_in), int(rate_out)) for n in n_samples]
-    out_max = max(max(n_out), 1)
-    key = (B, pcm.device)
-    ws = _resample_ws.get(key)
-    if ws is None:
-        if len(_resample_ws) > 8:
-            _resample_ws.clear()
-        ws = _resample_ws[key] = torch.empty(lib.amdspeech_resample_workspace_bytes(B), device=pcm.device,
-                                             dtype=torch.uint8)
-    out = torch.empty(B, out_max, device=pcm.device, dtype=torch.float32)
-    ns = (C.c_int * B)(*[int(v) for v in n_samples])
-    _l.check(lib.amdspeech_resample(_stream(), _p(pcm), ns, B, n_max, int(rate_in), int(rate_out), _p(out), out_max,
-                                    _p(ws)), "resample")
-    return out, n_out
+    librosa.load's resampling step (resampy kaiser_best semantics), on the GPU: resample_rows with every row at 1000 permille."""
+    return resample_rows(pcm, n_samples, [1000] * len(n_samples), rate_in, rate_out)
 
 
 _resample_rows_ws = {}
-
-
-def _int_array(values, what, B):
-    if len(values) != B:
-        raise ValueError("%s: %d values for %d rows" % (what, len(values), B))
-    return (C.c_int * max(B, 1))(*[int(v) for v in values])
 
 
 def resample_rows_num_samples(n, rate_in, rate_out, speed_permille=1000):
@@ -930,13 +934,13 @@ def resample_rows_plan(n_samples, speed_permille, n_max, rate_in, rate_out, out_
     out_max None: the longest output row, as resample_rows sizes it.  Read-only: nothing is launched, no device is needed.  What
     the call refuses raises here too."""
     B = len(n_samples)
-    ns, pm = _int_array(n_samples, "resample_rows_plan", B), _int_array(speed_permille, "resample_rows_plan", B)
+    ns, pm = _c_ints(n_samples, B, "resample_rows_plan"), _c_ints(speed_permille, B, "resample_rows_plan")
     if out_max is None:
         out_max = max([resample_rows_num_samples(n, rate_in, rate_out, s) for n, s in zip(n_samples, speed_permille)] + [1])
     info = _l.ResampleRowsPlanInfo()
     _l.check(_l.load().amdspeech_resample_rows_plan(ns, pm, B, int(n_max), int(rate_in), int(rate_out), int(out_max), C.byref(info)),
              "resample_rows_plan")
-    return {name: int(getattr(info, name)) for name, _ in _l.ResampleRowsPlanInfo._fields_}
+    return _plan_dict(info)
 
 
 def resample_rows(pcm, n_samples, speed_permille, rate_in, rate_out, out=None):
@@ -949,18 +953,13 @@ def resample_rows(pcm, n_samples, speed_permille, rate_in, rate_out, out=None):
         raise ValueError("resample_rows: expected [B, n_max], got %s" % (tuple(pcm.shape),))
     lib = _l.load()
     B, n_max = pcm.shape
-    ns, pm = _int_array(n_samples, "resample_rows", B), _int_array(speed_permille, "resample_rows", B)
+    ns, pm = _c_ints(n_samples, B, "resample_rows"), _c_ints(speed_permille, B, "resample_rows")
     n_out = [resample_rows_num_samples(n, rate_in, rate_out, s) for n, s in zip(n_samples, speed_permille)]
     if out is None:
         out = torch.empty(B, max(max(n_out), 1), device=pcm.device, dtype=torch.float32)
     elif out.dim() != 2 or out.shape[0] != B or out.device != pcm.device:
         raise ValueError("resample_rows: out is %s on %s, expected [%d, out_max] beside pcm" % (tuple(out.shape), out.device, B))
-    key = (B, pcm.device)
-    ws = _resample_rows_ws.get(key)
-    if ws is None:
-        if len(_resample_rows_ws) > 8:
-            _resample_rows_ws.clear()
-        ws = _resample_rows_ws[key] = torch.empty(lib.amdspeech_resample_rows_workspace_bytes(B), device=pcm.device, dtype=torch.uint8)
+    ws = _cached_ws(_resample_rows_ws, (B, pcm.device), lambda: lib.amdspeech_resample_rows_workspace_bytes(B))
     _l.check(lib.amdspeech_resample_rows(_stream(), _p(pcm), ns, pm, B, n_max, int(rate_in), int(rate_out), _p(out), out.shape[1],
                                          _p(ws)), "resample_rows")
     return out, n_out          # stream-ordered; lengths and speeds were kernel arguments, the cached workspace outlives the kernels
@@ -969,7 +968,7 @@ def resample_rows(pcm, n_samples, speed_permille, rate_in, rate_out, out=None):
 def speed_perturb_draw(seed, index, factors_permille):
     """The speed (permille) of utterance `index` under `seed`, one of factors_permille (1 .. 8 values in 500 .. 2000): SpecAugment's
     integer hash on the host (amdspeech.h: amdspeech_speed_perturb_draw)."""
-    f = (C.c_int * max(len(factors_permille), 1))(*[int(v) for v in factors_permille])
+    f = _c_ints(factors_permille, len(factors_permille), "speed_perturb_draw")
     got = _l.load().amdspeech_speed_perturb_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(index) & 0xFFFFFFFFFFFFFFFF, f, len(factors_permille))
     if got < 0:
         _l.check(got, "speed_perturb_draw")
@@ -983,7 +982,7 @@ def frontend_plan(mode, sample_rate, n_mfcc, B, n_max, t_max):
     imode = {"mfcc": MODE_MFCC, "fbank": MODE_FBANK}.get(mode, mode)
     _l.check(_l.load().amdspeech_frontend_plan(int(imode), int(sample_rate), int(n_mfcc), int(B), int(n_max), int(t_max), C.byref(info)),
              "frontend_plan")
-    return {name: int(getattr(info, name)) for name, _ in _l.FrontendPlanInfo._fields_}
+    return _plan_dict(info)
 
 
 def frontend(pcm, n_samples, sample_rate, mode, t_max, n_mfcc=20):
@@ -994,17 +993,16 @@ def frontend(pcm, n_samples, sample_rate, mode, t_max, n_mfcc=20):
     B, n_max = pcm.shape
     imode = MODE_MFCC if mode == "mfcc" else MODE_FBANK
     D = n_mfcc if imode == MODE_MFCC else 120
-    key = (imode, B, n_max, sample_rate, pcm.device)
-    ws = _frontend_ws.get(key)
-    if ws is None:
-        nbytes = lib.amdspeech_frontend_workspace_bytes(imode, B, n_max, sample_rate)
-        if nbytes == 0:
+
+    def nbytes():
+        n = lib.amdspeech_frontend_workspace_bytes(imode, B, n_max, sample_rate)
+        if n == 0:
             raise _l.AmdSpeechError("frontend workspace: bad arguments")
-        if len(_frontend_ws) > 8:
-            _frontend_ws.clear()
-        ws = _frontend_ws[key] = torch.empty(nbytes, device=pcm.device, dtype=torch.uint8)
+        return n
+
+    ws = _cached_ws(_frontend_ws, (imode, B, n_max, sample_rate, pcm.device), nbytes)
     feat = torch.empty(t_max, B, D, device=pcm.device, dtype=torch.float32)
-    ns = (C.c_int * B)(*[int(v) for v in n_samples])
+    ns = _c_ints(n_samples, B, "frontend")
     nf = (C.c_int * B)()
     if imode == MODE_MFCC:
         rc = lib.amdspeech_frontend_mfcc(_stream(), _p(pcm), ns, B, n_max, sample_rate, n_mfcc, t_max, _p(feat),
@@ -1022,26 +1020,22 @@ def frame_stack_plan(B, D, t_in, stack, skip):
     nothing is launched, no device is needed.  A shape the call refuses raises here too."""
     info = _l.FrameStackPlanInfo()
     _l.check(_l.load().amdspeech_frame_stack_plan(int(B), int(D), int(t_in), int(stack), int(skip), C.byref(info)), "frame_stack_plan")
-    return {name: int(getattr(info, name)) for name, _ in _l.FrameStackPlanInfo._fields_}
+    return _plan_dict(info)
 
 
 def frame_stack(feat, n_frames, stack, skip, out=None):
     """feat float32 [t_in, B, D] (device, the front end's output), n_frames: its UNtruncated frame counts (python ints).  Returns
     (out [ceil(t_in / skip), B, stack * D] device, n_out list of ceil(n / skip)): `stack` consecutive frames concatenated, every
     `skip`-th kept, zero from a row's own length on (amdspeech.h: amdspeech_frame_stack)."""
-    _chk_f32(feat, out)
-    if feat.dim() != 3:
-        raise ValueError("frame_stack: expected [t_in, B, D], got %s" % (tuple(feat.shape),))
+    _chk_f32(out)
+    t_in, B, D = _chk_f32_3d("frame_stack", feat, "[t_in, B, D]")
     lib = _l.load()
-    t_in, B, D = feat.shape
-    if len(n_frames) != B:
-        raise ValueError("frame_stack: %d lengths for %d rows" % (len(n_frames), B))
+    nf = _c_ints(n_frames, B, "frame_stack")
     plan = frame_stack_plan(B, D, t_in, stack, skip)
     if out is None:
         out = torch.empty(plan["t_out"], B, plan["d_out"], device=feat.device, dtype=torch.float32)
     elif tuple(out.shape) != (plan["t_out"], B, plan["d_out"]):
         raise ValueError("frame_stack: out is %s, expected %s" % (tuple(out.shape), (plan["t_out"], B, plan["d_out"])))
-    nf = (C.c_int * B)(*[int(v) for v in n_frames])
     no = (C.c_int * B)()
     _l.check(lib.amdspeech_frame_stack(_stream(), _p(feat), nf, B, D, t_in, int(stack), int(skip), _p(out), no), "frame_stack")
     return out, list(no)          # stream-ordered; the lengths were kernel arguments (or the call has waited)
@@ -1065,7 +1059,7 @@ def spec_augment_plan(T, B, W, policy, seed=0):
     info = _l.SpecAugmentPlanInfo()
     desc = _spec_augment_desc(policy, seed)
     _l.check(_l.load().amdspeech_spec_augment_plan(int(T), int(B), int(W), C.byref(desc), C.byref(info)), "spec_augment_plan")
-    return {name: int(getattr(info, name)) for name, _ in _l.SpecAugmentPlanInfo._fields_}
+    return _plan_dict(info)
 
 
 def spec_augment_spans(policy, seed, row, n):
@@ -1082,10 +1076,7 @@ def spec_augment(x, lengths, policy, seed):
     """x float32 [T, B, W] (device, contiguous), lengths int32 [B] ON THE DEVICE.  Masks x IN PLACE and returns it: frequency and
     time spans of every row's first min(length, T) frames become +0.0, every other word keeps its bit pattern (amdspeech.h:
     amdspeech_spec_augment).  Stream-ordered, no copy, no synchronisation; a policy that can mask nothing launches nothing."""
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
-        raise ValueError("spec_augment: expected a contiguous float32 device tensor [T, B, W], got %s"
-                         % ((x.dtype, x.device, tuple(x.shape), x.stride()) if torch.is_tensor(x) else type(x),))
-    T, B, W = x.shape
+    T, B, W = _chk_f32_3d("spec_augment", x, "[T, B, W]")
     if not (torch.is_tensor(lengths) and lengths.is_cuda and lengths.device == x.device and lengths.dtype == torch.int32
             and tuple(lengths.shape) == (B,) and lengths.is_contiguous()):
         raise ValueError("spec_augment: lengths must be an int32 device tensor [%d] beside x" % B)
@@ -1114,19 +1105,15 @@ def feature_norm_plan(B, D, t_in, mode="utterance"):
     ints.  Read-only: nothing is launched, no device is needed.  A shape the calls refuse raises here too."""
     info = _l.FeatureNormPlanInfo()
     _l.check(_l.load().amdspeech_feature_norm_plan(int(B), int(D), int(t_in), _feature_norm_mode(mode), C.byref(info)), "feature_norm_plan")
-    return {name: int(getattr(info, name)) for name, _ in _l.FeatureNormPlanInfo._fields_}
+    return _plan_dict(info)
 
 
 def _feature_norm_args(what, feat, n_frames):
-    if not (torch.is_tensor(feat) and feat.is_cuda and feat.dtype == torch.float32 and feat.dim() == 3 and feat.is_contiguous()):
-        raise ValueError("%s: expected a contiguous float32 device tensor [t_in, B, D], got %s"
-                         % (what, (feat.dtype, feat.device, tuple(feat.shape), feat.stride()) if torch.is_tensor(feat) else type(feat)))
-    t_in, B, D = feat.shape
-    if len(n_frames) != B:
-        raise ValueError("%s: %d lengths for %d rows" % (what, len(n_frames), B))
+    t_in, B, D = _chk_f32_3d(what, feat, "[t_in, B, D]")
+    nf = _c_ints(n_frames, B, what)
     plan = feature_norm_plan(B, D, t_in, "utterance")
     ws = torch.empty(max(plan["workspace_bytes"], 8), device=feat.device, dtype=torch.uint8)
-    return t_in, B, D, (C.c_int * B)(*[int(v) for v in n_frames]), ws
+    return t_in, B, D, nf, ws
 
 
 def feature_moments(feat, n_frames):

@@ -215,6 +215,21 @@ def test_null_pointers_overlap_and_bad_queries_are_refused(handle):
         ops.resample_rows_plan([10, 10], [1000], 10, 16000, 22050)                                         # a factor per row
 
 
+def test_uniform_resample_is_the_per_row_call_at_1000_permille(handle):
+    """amdspeech_resample plans as amdspeech_resample_rows does (a ratio outside 1/16 .. 16 is refused before anything is launched)
+    and shares its workspace size and, at 1000 permille, its lengths."""
+    for rate_in, rate_out in ((1000, 17000), (17000, 1000)):
+        rc = handle.amdspeech_resample(None, ctypes.c_void_p(1 << 20), _ints([10]), 1, 10, rate_in, rate_out, ctypes.c_void_p(1 << 30),
+                                       1000, ctypes.c_void_p(1 << 40))
+        assert rc == -1 and b"outside 1/16" in handle.amdspeech_last_error(), handle.amdspeech_last_error()
+    for B in (1, 256, 257):
+        assert handle.amdspeech_resample_workspace_bytes(B) == handle.amdspeech_resample_rows_workspace_bytes(B) > 0
+    for rate_in, rate_out in ((16000, 22050), (44100, 22050), (8000, 22050), (22050, 16000)):
+        for n in range(3001):
+            assert handle.amdspeech_resample_num_samples(n, rate_in, rate_out) == \
+                handle.amdspeech_resample_rows_num_samples(n, rate_in, rate_out, 1000) == ref.n_total(n, rate_in, rate_out, 1000)
+
+
 # ------------------------------------------------------------------------------------------------ the config keys
 def _config(tmp_path, factors=None, seed=None, cache=None):
     src = open(os.path.join(ROOT, "config.ini")).read()

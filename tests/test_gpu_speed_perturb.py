@@ -1,5 +1,5 @@
 """The per-row resampler / speed perturbation on the GPU (csrc/frontend.hip: resample_rows_kernel) against the float64 oracle of
-tests/speed_perturb_ref.py: every produced sample within the bound the existing resampler test holds amdspeech_resample to, poison
+tests/speed_perturb_ref.py: every produced sample within the bound the resampler test of test_gpu_frontend.py holds amdspeech_resample to, poison
 past every input row and in the output buffer, bit-exact copy rows; then the layers above it up to a config-built training dataset."""
 import os
 import sys
@@ -60,24 +60,32 @@ def test_rows_match_the_float64_oracle(name):
     assert worst < ref.BOUND, (name, worst)
 
 
-def test_two_calls_give_the_same_bits_and_the_old_resampler_agrees():
-    """Determinism; and at permille 1000 both resamplers meet the bound on the same rows (the sum order may differ: no equality)."""
+def test_two_calls_give_the_same_bits_and_resample_is_resample_rows_at_1000_permille():
+    """Determinism; and ops.resample is ops.resample_rows with every row at 1000 permille: the same lengths and the same bits, on input
+    that is NaN past every row, within the oracle's bound."""
     from rnn_speech_amd import ops
-    first, n_out, (rate_in, rate_out, n, pm, host, refs) = _run("edges16k")
+    first, _, _ = _run("edges16k")
     second, _, _ = _run("edges16k")
     assert np.array_equal(bits(first), bits(second))
-    clean = np.where(np.isnan(host), np.float32(0), host)           # (the old kernel's contract: rows zero-padded)
-    new, n_new = ops.resample_rows(torch.from_numpy(host).cuda(), n, [1000] * len(n), rate_in, rate_out)
-    old, n_old = ops.resample(torch.from_numpy(clean).cuda(), n, rate_in, rate_out)
-    assert n_new == n_old and new.shape == old.shape
-    new, old = new.cpu().numpy(), old.cpu().numpy()
-    for b in range(len(n)):
-        if n[b] == 0:
-            continue
-        want = ref.reference_row(host[b, :n[b]], rate_in, rate_out, 1000) if pm[b] != 1000 else refs[b]
-        e_new, e_old = np.abs(new[b, :n_new[b]] - want).max(), np.abs(old[b, :n_old[b]] - want).max()
-        print("row %d (n %d): resample_rows %.3g, resample %.3g" % (b, n[b], e_new, e_old))
-        assert e_new < ref.BOUND and e_old < ref.BOUND, (b, e_new, e_old)
+    for name, rows in (("edges16k", None), ("down", [3]), ("wide", None)):
+        rate_in, rate_out, n, pm, host, refs = ref.built(name)
+        rows = list(range(len(n))) if rows is None else rows
+        assert name != "down" or [pm[b] for b in rows] == [1000]
+        pcm = torch.from_numpy(np.ascontiguousarray(host[rows])).cuda()
+        n_rows = [n[b] for b in rows]
+        new, n_new = ops.resample_rows(pcm, n_rows, [1000] * len(rows), rate_in, rate_out)
+        old, n_old = ops.resample(pcm, n_rows, rate_in, rate_out)
+        assert n_new == n_old == [ref.n_total(k, rate_in, rate_out, 1000) for k in n_rows] and new.shape == old.shape
+        new, old = new.cpu().numpy(), old.cpu().numpy()
+        assert not np.isnan(new).any() and np.array_equal(bits(new), bits(old)), name
+        worst = 0.0
+        for i, b in enumerate(rows):
+            if n[b] == 0 or (name == "wide" and pm[b] != 1000):       # (wide: the rows whose 1000-permille reference the table holds)
+                continue
+            want = refs[b] if pm[b] == 1000 else ref.reference_row(host[b, :n[b]], rate_in, rate_out, 1000)
+            worst = max(worst, float(np.abs(new[i, :n_new[i]] - want).max()))
+        print("resample at 1000 permille, %s: max |error| %.3g" % (name, worst))
+        assert worst < ref.BOUND, (name, worst)
 
 
 # ------------------------------------------------------------------------------------------------ AudioProcessor
@@ -126,6 +134,9 @@ def test_process_files_with_per_row_factors(tmp_path):
     same, same_len = ap.process_files(files, rows=6, speed_permille=None)
     assert plain_len == same_len and np.array_equal(bits(plain.cpu().numpy()), bits(same.cpu().numpy()))
     assert lengths[2] == plain_len[2] and np.array_equal(bits(feat[:, 2].cpu().numpy()), bits(plain[:, 2].cpu().numpy()))
+    unit, unit_len = ap.process_files(files, speed_permille=[1000] * len(files))       # a factor of 1 is no factor: the same kernel, the same bits
+    bare, bare_len = ap.process_files(files)
+    assert unit_len == bare_len and np.array_equal(bits(unit.cpu().numpy()), bits(bare.cpu().numpy()))
     # in-memory signals at one rate: the factor alone
     sig16 = [s for s, sr in sigs if sr == 16000]
     fb, lb = ap.process_batch(sig16, 16000, speed_permille=[1100, 1000, 900])
