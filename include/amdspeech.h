@@ -627,6 +627,102 @@ int amdspeech_resample_rows_plan(const int* n_samples, const int* speed_permille
                                  int out_max, amdspeech_resample_rows_plan_info* out);
 int amdspeech_speed_perturb_draw(unsigned long long seed, unsigned long long index, const int* factors_permille, int count);
 
+/* ------------------------------------------------ noise and reverberation augmentation ---
+ * Multi-condition training data (Ko et al. 2017) on the waveform, between the resampler and the front end, in the recipe's order:
+ * speed perturbation -> reverberation by a room impulse response (RIR) -> additive noise at a drawn SNR -> features.  No reference
+ * counterpart: an opt-in deviation, off unless a caller asks for it.  Three launches, all asynchronous on `stream`; the host-side
+ * per-row values travel as kernel arguments of one-block launches, 512 values each (the resampler's hand-off), into `ws`.
+ *
+ * amdspeech_reverb_rows: a FIR with an impulse response of its own for every row, the whole batch in ONE launch.
+ *   pcm        float [B][n_max] (DEVICE);  out  float [B][n_max] (DEVICE), a range that overlaps pcm (or rir_bank) is refused
+ *   n_samples  int32 [B] (HOST)  valid samples per row, 0 .. n_max
+ *   rir_bank   float [R][taps_max] (DEVICE)  row r holds h_r[0 .. rir_taps[r]); words past that are not read
+ *   rir_taps   int32 [R] (HOST)  L, 1 .. taps_max;  taps_max <= 8192
+ *   rir_delay  int32 [R] (HOST)  d, 0 .. L - 1: the position of the direct path, so that speech stays aligned with its labels
+ *   rir_index  int32 [B] (HOST)  -1 .. R - 1: the row's impulse response, -1 = none
+ * For a row with r = rir_index[b] >= 0 and 0 <= t < n:   out[b][t] = sum_{k = 0 .. L - 1} h_r[k] * x_b[t + d - k]   over the terms
+ * with 0 <= t + d - k < n only.  The output is as long as the input (the reverberant tail past n is dropped), out[b][n .. n_max) is
+ * +0.0f, input words at or past n_samples[b] are not read and may hold anything, every word of out is written.  A row with
+ * rir_index -1 is COPIED bit for bit (NaN payloads, -0.0).
+ * Arithmetic.  The sum is a matrix product on the f32 matrix cores (v_mfma_f32_32x32x2_f32, exact f32: an fmaf chain).  For a tile
+ * of 1024 outputs t = t0 + 32 i + j:  Y[i][j] = sum_q X[i][q] G[q][j] with X[i][q] = x[t0 + d - (L - 1) + 32 i + q] and
+ * G[q][j] = h[j + L - 1 - q] (0 outside 0 .. L - 1), q = 0 .. 32 * k_chunks - 1.  q runs in chunks of 32; the four waves of the
+ * workgroup take the chunks round-robin (wave w: chunks w, w + 4, ..), each summing its terms in q order from +0.0f, and the four
+ * partial sums are added ((w0 + w1) + w2) + w3.  So the order is fixed -- no atomics, no dependence on the launch order, two calls
+ * give the same bits -- and every output is within (L + 2) * 2^-24 * sum_k |h[k] x[t + d - k]| of the exact sum.  The zero frame of
+ * G multiplies staged samples up to 31 positions beyond an output's own reach: the samples of a filtered row must be FINITE (an
+ * infinity inside a row turns outputs within L + 31 of it into NaN, 31 more than the sum itself would).
+ *   ws   device, amdspeech_reverb_rows_workspace_bytes(B) bytes, 256-byte aligned, caller-allocated: 4 B values
+ * AMDSPEECH_EINVAL with a message: null pointers, non-positive B, n_max, R or taps_max, B > 65535, n_max > 2^30, taps_max > 8192, taps
+ * outside 1 .. taps_max, a delay outside 0 .. taps - 1, a negative count or n > n_max, an index outside -1 .. R - 1, overlapping ranges.
+ * amdspeech_reverb_rows_plan: the launch geometry as plain numbers, a READ-ONLY view of the plan the call itself reads (one function
+ * decides for both); no device is needed, the arguments are checked as the call checks them.
+ *   tile           outputs per workgroup (1024: 32 x 32, one MFMA tile);  tiles_per_row = ceil(n_max / tile)
+ *   workgroups     tiles_per_row * B: workgroup (x, b) owns outputs x * tile .. of row b.  A tile at or past n stores zeros, a tile
+ *                  of a copy row copies (both branches are uniform over the workgroup)
+ *   taps           the longest impulse response among the rows with an index >= 0 and n > 0;  0: every row copies
+ *   k_chunk        32: values of q per step of a wave;  k_chunks = ceil((taps + 31) / 32)
+ *   span_max       staged input samples of a tile: tile - 32 + 32 * k_chunks (0 when taps is 0)
+ *   lds_bytes      dynamic LDS of the launch: the span with one pad word per 32, rounded up to 16 bytes and at least 16 KB (the four
+ *                  partial tiles reuse it), then 32 * k_chunks + 32 reversed, zero-framed taps (69 KB at 8192 taps: two
+ *                  workgroups a CU; 37 KB at 4096)
+ *   copy_rows      rows with rir_index -1
+ *   meta_launches  ceil(4 B / 512)
+ *
+ * amdspeech_row_sumsq: sumsq[b] = sum_{t < n} x[b][t]^2 as float64 (DEVICE, [B]); pcm, n_samples as above, words at or past n are
+ * not read.  Fixed tiles, fixed order, no atomics: the row is cut into tiles of 4096 samples, workgroup s of the row's 64 takes tiles
+ * s, s + 64, .. in order, thread i of 256 adding x^2 (fma in double) of words i, i + 256, .. of each tile to its own sum; the 256 sums
+ * are added pairwise (i with i + 128, then + 64, ..), and so are the 64 partial sums.  The bits depend on the row and n alone, not on
+ * B, n_max or the call.  n = 0 gives 0.0.  ws: amdspeech_row_sumsq_workspace_bytes(B) bytes (64 B doubles, B values), 256-byte aligned.
+ * EINVAL: null pointers, non-positive B or n_max, B > 65535, n_max > 2^30, a negative count or n > n_max.
+ *
+ * amdspeech_noise_mix_rows: one launch; out == pcm (in place) is allowed, a partial overlap is refused.
+ *   noise_bank   float [M][m_max] (DEVICE);  noise_len  int32 [M] (HOST) 1 .. m_max;  noise_sumsq  double [M] (DEVICE), the
+ *                amdspeech_row_sumsq of the clips
+ *   row_sumsq    double [B] (DEVICE), the amdspeech_row_sumsq of pcm
+ *   noise_index  int32 [B] (HOST) -1 .. M - 1, -1 = none;  noise_offset  int32 [B] (HOST) 0 .. len - 1;
+ *   snr_decidb   int32 [B] (HOST) -200 .. 600: the signal-to-noise ratio in tenths of a dB (offset and SNR of a -1 row are not read)
+ * For a row with m >= 0, n > 0, row_sumsq[b] > 0 and noise_sumsq[m] > 0 the gain is computed in double and rounded once,
+ *   g = (float) sqrt((row_sumsq[b] / n) / (noise_sumsq[m] / len_m) * p),   p = pow(10.0, -snr_decidb / 100.0) on the HOST,
+ * and  out[b][t] = fmaf(g, noise_m[(offset + t) mod len_m], x[b][t])  for t < n: a short clip wraps around.  Every other row is
+ * copied bit for bit (left alone when in place).  Words at or past n are not read; out of place they are written +0.0f, in place
+ * they are left alone (the zeros the resampler or the reverberation left stay).
+ *   ws   amdspeech_noise_mix_rows_workspace_bytes(B) bytes, 256-byte aligned: 6 B values
+ * EINVAL: null pointers, non-positive B, n_max, M or m_max, B > 65535, n_max or m_max > 2^30, a length outside 1 .. m_max, a negative
+ * count or n > n_max, an index outside -1 .. M - 1, an offset outside 0 .. len - 1, an SNR outside -200 .. 600, overlapping ranges.
+ * amdspeech_noise_mix_rows_plan: as above;  tile 1024 (256 threads of 4), tiles_per_row, workgroups = tiles_per_row * B, lds_bytes 0,
+ * copy_rows the rows with noise_index -1, meta_launches ceil(6 B / 512).
+ *
+ * amdspeech_augment_draw: what happens to one utterance, host arithmetic with SpecAugment's integer hash r (see there):
+ *   idx = lo32(index) + hi32(index) * 0x9E3779B1 (32-bit wrap),   u(s, count) = (r(0x5C000000 + s, idx) * count) >> 24  (64-bit product)
+ *   out[0] rir_index     R > 0 and u(0, 1000) < reverb_permille ?  u(1, R)  : -1
+ *   out[1] noise_index   M > 0 and u(2, 1000) < noise_permille  ?  u(3, M)  : -1
+ *   out[2] noise_offset  u(4, noise_len[noise_index]);   out[3] snr_decidb  snr_lo + u(5, snr_hi - snr_lo + 1)   (both 0 without noise)
+ * EINVAL: a null out (or noise_len with M > 0), a probability outside 0 .. 1000 permille, a negative R or M, a length below 1, an SNR
+ * range that is empty or outside -200 .. 600.                                                                                  */
+typedef struct amdspeech_reverb_rows_plan_info {
+    int tile, tiles_per_row, workgroups, taps, span_max, k_chunk, k_chunks, lds_bytes, copy_rows, meta_launches;
+} amdspeech_reverb_rows_plan_info;
+typedef struct amdspeech_noise_mix_rows_plan_info {
+    int tile, tiles_per_row, workgroups, lds_bytes, copy_rows, meta_launches;
+} amdspeech_noise_mix_rows_plan_info;
+size_t amdspeech_reverb_rows_workspace_bytes(int B);
+int amdspeech_reverb_rows(void* stream, const float* pcm, const int* n_samples, int B, int n_max, const float* rir_bank,
+                          const int* rir_taps, const int* rir_delay, int R, int taps_max, const int* rir_index, float* out, void* ws);
+int amdspeech_reverb_rows_plan(const int* n_samples, int B, int n_max, const int* rir_taps, const int* rir_delay, int R, int taps_max,
+                               const int* rir_index, amdspeech_reverb_rows_plan_info* out);
+size_t amdspeech_row_sumsq_workspace_bytes(int B);
+int amdspeech_row_sumsq(void* stream, const float* pcm, const int* n_samples, int B, int n_max, double* sumsq, void* ws);
+size_t amdspeech_noise_mix_rows_workspace_bytes(int B);
+int amdspeech_noise_mix_rows(void* stream, const float* pcm, const int* n_samples, int B, int n_max, const float* noise_bank,
+                             const int* noise_len, const double* noise_sumsq, int M, int m_max, const double* row_sumsq,
+                             const int* noise_index, const int* noise_offset, const int* snr_decidb, float* out, void* ws);
+int amdspeech_noise_mix_rows_plan(const int* n_samples, int B, int n_max, const int* noise_len, int M, int m_max,
+                                  const int* noise_index, const int* noise_offset, const int* snr_decidb,
+                                  amdspeech_noise_mix_rows_plan_info* out);
+int amdspeech_augment_draw(unsigned long long seed, unsigned long long index, int reverb_permille, int R, int noise_permille, int M,
+                           const int* noise_len, int snr_lo_decidb, int snr_hi_decidb, int* out);
+
 /* ------------------------------------------------------------- optimiser ----
  * Replaces tf.clip_by_global_norm + tf.train.AdamOptimizer.apply_gradients over
  * the flat parameter vector, models/AcousticModel.py:388 and :404-406.

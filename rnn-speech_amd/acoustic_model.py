@@ -80,20 +80,26 @@ class AcousticDataset(object):
     factors) with seed64 = (seed + data-parallel rank) << 32; epoch_serial is a counter shared with the with_items siblings that
     advances once per batches() pass, so a re-shuffled epoch draws afresh and a run is reproducible.  Durations used for bucketing
     stay the unperturbed ones; a row made longer than max_input_seq_length is truncated like any over-long file.  Cached features
-    would freeze the draw: feature_cache_mb > 0 beside it is refused."""
+    would freeze the draw: feature_cache_mb > 0 beside it is refused.
+    augment: None (off: nothing is launched, nothing is allocated), or (bank, reverb_permille, noise_permille, (snr_lo, snr_hi) in
+    tenths of a dB, seed) -- reverberation and additive noise on the waveform on the GPU, behind the speed change
+    (AudioProcessor._augmented); bank is an audioprocessor.AugmentBank at sample_rate, shared with the with_items siblings.  The draw
+    of an item is ops.augment_draw with the seed64 / epoch_serial / position scheme of the speed draw (and its rank handling), on
+    the producer thread.  feature_cache_mb > 0 beside it is refused for the same reason."""
 
     def __init__(self, input_set, batch_size, max_input_seq_length, max_target_seq_length,
                  signal_processing, char_map, n_mfcc=20, device="cuda", prefetch=2, feature_cache_mb=0,
                  sample_rate=22050, frame_stack=1, frame_skip=1, feature_norm="none", feature_norm_variance=True,
-                 feature_stats=None, speed_perturb=None):
+                 feature_stats=None, speed_perturb=None, augment=None):
         self.items = [(it[0], it[1]) for it in input_set]
         self.batch_size = batch_size
         self.U = max_target_seq_length
         self.char_map = char_map
+        self._augment = self._augment_option(augment, feature_cache_mb)
         self.audio = AudioProcessor(max_input_seq_length, signal_processing, n_mfcc=n_mfcc, device=device,
                                     load_sr=sample_rate, frame_stack=frame_stack, frame_skip=frame_skip,
                                     feature_norm=feature_norm, feature_norm_variance=feature_norm_variance,
-                                    feature_stats=feature_stats)
+                                    feature_stats=feature_stats, augment_bank=None if self._augment is None else self._augment[0])
         self.T = self.audio.out_seq_length
         self.prefetch = int(prefetch)
         self._signal_processing, self._n_mfcc = signal_processing, n_mfcc
@@ -102,7 +108,7 @@ class AcousticDataset(object):
         self._speed = self._speed_option(speed_perturb, feature_cache_mb)
         self._epoch = [0]                                   # speed perturbation's epoch_serial, shared in the same way
         # the data-parallel rank, resolved HERE on the caller's thread: the draws run on the decode-ahead thread
-        self._rank = dataparallel.current().rank if self._speed is not None else 0
+        self._rank = dataparallel.current().rank if (self._speed is not None or self._augment is not None) else 0
 
     @staticmethod
     def _speed_option(speed_perturb, feature_cache_mb):
@@ -127,6 +133,38 @@ class AcousticDataset(object):
         stop = len(self.items) if count is None else min(start + count, len(self.items))
         return [ops.speed_perturb_draw(seed64, (int(epoch_serial) << 32) | pos, factors) for pos in range(start, stop)]
 
+    @staticmethod
+    def _augment_option(augment, feature_cache_mb):
+        if augment is None:
+            return None
+        bank, reverb_permille, noise_permille, snr, seed = augment
+        reverb_permille, noise_permille, snr = int(reverb_permille), int(noise_permille), (int(snr[0]), int(snr[1]))
+        if not (0 <= reverb_permille <= 1000 and 0 <= noise_permille <= 1000):
+            raise ValueError("augment: probabilities of 0 .. 1000 permille, not %r, %r" % (reverb_permille, noise_permille))
+        if not -200 <= snr[0] <= snr[1] <= 600:
+            raise ValueError("augment: an SNR range lo <= hi inside -200 .. 600 tenths of a dB, not %r" % (snr,))
+        if bank is None or bank.rir_bank is None:
+            reverb_permille = 0
+        if bank is None or bank.noise_bank is None:
+            noise_permille = 0
+        if reverb_permille == 0 and noise_permille == 0:
+            return None
+        if feature_cache_mb > 0:
+            raise ValueError("noise / reverberation augmentation with feature_cache_mb > 0: cached features would freeze the draw; "
+                             "set feature_cache_mb : 0")
+        return bank, reverb_permille, noise_permille, snr, int(seed)
+
+    def augment_draws(self, epoch_serial, start=0, count=None):
+        """(rir_index, noise_index, noise_offset, snr_decidb) of items start .. start + count of pass `epoch_serial`; None when the
+        option is off."""
+        if self._augment is None:
+            return None
+        bank, reverb_permille, noise_permille, snr, seed = self._augment
+        seed64 = ((seed + self._rank) << 32) & 0xFFFFFFFFFFFFFFFF
+        stop = len(self.items) if count is None else min(start + count, len(self.items))
+        return [ops.augment_draw(seed64, (int(epoch_serial) << 32) | pos, reverb_permille, len(bank.rir_taps), noise_permille,
+                                 bank.noise_len, snr) for pos in range(start, stop)]
+
     def with_items(self, input_set):
         """The same dataset over a re-ordered / re-shuffled item list, sharing the feature cache (the
         reference builds a fresh tf.data pipeline at every epoch, stt.py:198-207)."""
@@ -135,7 +173,7 @@ class AcousticDataset(object):
                                 sample_rate=self.audio.load_sr, frame_stack=self.audio.frame_stack,
                                 frame_skip=self.audio.frame_skip, feature_norm=self.audio.feature_norm,
                                 feature_norm_variance=self.audio.feature_norm_variance, feature_stats=self.audio.feature_stats,
-                                speed_perturb=self._speed)
+                                speed_perturb=self._speed, augment=self._augment)
         other._cache, other._room, other._epoch, other._rank = self._cache, self._room, self._epoch, self._rank
         return other
 
@@ -145,8 +183,9 @@ class AcousticDataset(object):
         for start in range(0, len(self.items), B):
             yield start, self.items[start:start + B]
 
-    def _prepare(self, chunk, speeds=None):
-        """Host half of one mini-batch: cached features or decoded waveforms per item.  speeds: the items' speed factors."""
+    def _prepare(self, chunk, speeds=None, draws=None):
+        """Host half of one mini-batch: cached features or decoded waveforms per item.  speeds: the items' speed factors; draws:
+        their augmentation draws (carried to the consumer)."""
         from .audioprocessor import decode_files
         cache = self._cache
         need = [a for a, _ in chunk if isinstance(a, str) and (cache is None or a not in cache)]
@@ -173,12 +212,13 @@ class AcousticDataset(object):
             staged = ("batch", self.audio.stage(sigs), parts[0][1][1])
         elif "cached" not in kinds:
             staged = ("files", self.audio.stage_files([p for _, p in parts], speeds))
-        return chunk, parts, dense, staged, speeds
+        return chunk, parts, dense, staged, speeds, draws
 
     def _prepared(self, epoch_serial=0):
         if self.prefetch <= 0:
             for start, chunk in self._chunks():
-                yield self._prepare(chunk, self.speed_draws(epoch_serial, start, len(chunk)))
+                yield self._prepare(chunk, self.speed_draws(epoch_serial, start, len(chunk)),
+                                    self.augment_draws(epoch_serial, start, len(chunk)))
             return
         import queue
         import threading
@@ -190,7 +230,8 @@ class AcousticDataset(object):
                 for start, chunk in self._chunks():
                     if stop.is_set():
                         return
-                    q.put(("ok", self._prepare(chunk, self.speed_draws(epoch_serial, start, len(chunk)))))
+                    q.put(("ok", self._prepare(chunk, self.speed_draws(epoch_serial, start, len(chunk)),
+                                               self.augment_draws(epoch_serial, start, len(chunk)))))
                 q.put(("end", None))
             except BaseException as exc:            # surfaced in the consumer
                 q.put(("error", exc))
@@ -227,17 +268,19 @@ class AcousticDataset(object):
     # ---- consumer side (device) -----------------------------------------------------
     def batches(self):
         B, T = self.batch_size, self.T
-        epoch_serial = self._epoch[0]              # this pass's draws of the speed perturbation; the next pass draws afresh
+        epoch_serial = self._epoch[0]              # this pass's draws (speed, noise, reverberation); the next pass draws afresh
         self._epoch[0] += 1
-        for chunk, parts, dense, staged, speeds in self._prepared(epoch_serial):
+        for chunk, parts, dense, staged, speeds, draws in self._prepared(epoch_serial):
+            extra = {} if draws is None else {"augment": draws}      # (off: the call is the one it was before the option existed)
             if staged is not None and staged[0] == "batch":
                 # in-memory signals at one rate: the process_signal convention (no resampling)
                 feat, lengths = self.audio.process_batch(None, staged[2], t_max=T, staged=staged[1],
-                                                         speed_permille=None if speeds is None else speeds + [1000] * (B - len(speeds)))
+                                                         speed_permille=None if speeds is None else speeds + [1000] * (B - len(speeds)),
+                                                         **extra)
             elif staged is not None:
                 # files: librosa.load semantics (22,050 Hz); a short final batch is padded with empty rows
                 feat, lengths = self.audio.process_files(None, t_max=T, rows=B, decoded=[p for _, p in parts], staged=staged[1],
-                                                         speed_permille=speeds)
+                                                         speed_permille=speeds, **extra)
             else:
                 feat, lengths = self._assemble(parts)
             if self._cache is not None:
@@ -751,15 +794,16 @@ class AcousticModel(object):
     def build_dataset(input_set, batch_size, max_input_seq_length, max_target_seq_length,
                       signal_processing, char_map, n_mfcc=20, prefetch=2, feature_cache_mb=0, sample_rate=22050,
                       frame_stack=1, frame_skip=1, feature_norm="none", feature_norm_variance=True, feature_stats=None,
-                      speed_perturb=None):
+                      speed_perturb=None, augment=None):
         """max_input_seq_length in SOURCE frames, whatever frame_stack / frame_skip (the dataset's T is in model frames).
-        speed_perturb: None, or (factors_permille, seed): speed perturbation of the waveforms (AcousticDataset)."""
+        speed_perturb: None, or (factors_permille, seed): speed perturbation of the waveforms (AcousticDataset).
+        augment: None, or (bank, reverb_permille, noise_permille, (snr_lo, snr_hi) decidb, seed): noise and reverberation."""
         return AcousticDataset(input_set, batch_size, max_input_seq_length, max_target_seq_length,
                                signal_processing, char_map, n_mfcc=n_mfcc, prefetch=prefetch,
                                feature_cache_mb=feature_cache_mb, sample_rate=sample_rate,
                                frame_stack=frame_stack, frame_skip=frame_skip, feature_norm=feature_norm,
                                feature_norm_variance=feature_norm_variance, feature_stats=feature_stats,
-                               speed_perturb=speed_perturb)
+                               speed_perturb=speed_perturb, augment=augment)
 
     def add_dataset_input(self, dataset):
         self._single_iter = DatasetIterator(dataset)

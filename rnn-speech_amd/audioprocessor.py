@@ -18,7 +18,8 @@ DEFAULT_LOAD_SR = 22050   # librosa.load default used by the reference's file pa
 
 class AudioProcessor(object):
     def __init__(self, max_input_seq_length, feature_type="mfcc", n_mfcc=20, device="cuda", load_sr=DEFAULT_LOAD_SR,
-                 frame_stack=1, frame_skip=1, feature_norm="none", feature_norm_variance=True, feature_stats=None):
+                 frame_stack=1, frame_skip=1, feature_norm="none", feature_norm_variance=True, feature_stats=None,
+                 augment_bank=None):
         """feature_type: 'mfcc' (n_mfcc-dim, reference default 20) or 'fbank' (120-dim).  load_sr: the rate audio
         FILES are resampled to before feature extraction (config.ini `sample_rate`; the reference's librosa.load
         default, 22,050 Hz) -- set it to the corpus rate (16,000 for LibriSpeech) to skip resampling.
@@ -30,8 +31,11 @@ class AudioProcessor(object):
         feature_norm ("none": the reference's behaviour | "utterance" | "global"): mean (and, with feature_norm_variance, variance)
         normalisation of the SOURCE frames on the GPU, between the front end and the frame stacking (ops.feature_norm) -- over the
         frames of the utterance that survive the truncation, or with the corpus statistics in feature_stats (a FeatureStats or the
-        path of the file `stt.py --feature_stats` wrote; a file taken from other features is refused)."""
+        path of the file `stt.py --feature_stats` wrote; a file taken from other features is refused).
+        augment_bank: the AugmentBank (impulse responses and noise clips at load_sr, on the device) that the `augment` draws of the
+        process_* calls index; None: those calls take no draws."""
         self.max_input_seq_length = max_input_seq_length
+        self.augment_bank = augment_bank
         self.load_sr = int(load_sr)
         self.feature_type = feature_type
         self.device = device
@@ -165,11 +169,39 @@ class AudioProcessor(object):
         out, n_out = ops.resample_rows(pcm, n, speeds, rate_in, rate_out)
         return out, n_out[:rows]
 
-    def process_batch(self, signals, sr, t_max=None, staged=None, speed_permille=None):
+    def _augmented(self, pcm, n, augment):
+        """Reverberation, then additive noise, on the rows of one call (ops.reverb_rows, ops.row_sumsq, ops.noise_mix_rows):
+        augment holds (rir_index, noise_index, noise_offset, snr_decidb) per row, an index of -1 = not applied; rows past the list
+        are padding.  None, or no row with an index: nothing is launched and pcm is returned as it came."""
+        if augment is None:
+            return pcm
+        bank, rows = self.augment_bank, pcm.shape[0]
+        if bank is None:
+            raise ValueError("augment draws without an augment_bank")
+        if len(augment) > rows:
+            raise ValueError("augment: %d draws for %d rows" % (len(augment), rows))
+        draws = [tuple(int(v) for v in d) for d in augment] + [(-1, -1, 0, 0)] * (rows - len(augment))
+        n = list(n) + [0] * (rows - len(n))
+        rir, noise = [d[0] for d in draws], [d[1] for d in draws]
+        if any(r >= 0 for r in rir):
+            if bank.rir_bank is None:
+                raise ValueError("augment: a draw names an impulse response, the bank holds none")
+            pcm = ops.reverb_rows(pcm, n, bank.rir_bank, bank.rir_taps, bank.rir_delay, rir)
+        if any(m >= 0 for m in noise):
+            if bank.noise_bank is None:
+                raise ValueError("augment: a draw names a noise clip, the bank holds none")
+            energy = ops.row_sumsq(pcm, n)
+            pcm = ops.noise_mix_rows(pcm, n, energy, bank.noise_bank, bank.noise_len, bank.noise_sumsq, noise, [d[2] for d in draws],
+                                     [d[3] for d in draws], out=pcm)
+        return pcm
+
+    def process_batch(self, signals, sr, t_max=None, staged=None, speed_permille=None, augment=None):
         """signals: list of 1-D float arrays, all at sample rate `sr`.  Returns (feat [t_max, B, feature_size] device
         float32, zero past each utterance; list of UNtruncated frame counts) -- model frames under low frame rate input,
         t_max defaulting to out_seq_length.  staged: (block, n) from stage().  speed_permille: a speed factor per signal (speed
-        perturbation, ops.resample_rows: a row played f times faster has 1 / f of its samples); None or all 1000: nothing is launched."""
+        perturbation, ops.resample_rows: a row played f times faster has 1 / f of its samples); None or all 1000: nothing is launched.
+        augment: (rir_index, noise_index, noise_offset, snr_decidb) per signal, indices into augment_bank (whose audio is taken to be at
+        `sr`): reverberation, then noise, behind the speed change; None or no index >= 0: nothing is launched."""
         t_out, t_max = t_max, self._source_t_max(t_max)
         if staged is not None:
             pcm, n = self._upload_staged(staged[0]), staged[1]
@@ -178,6 +210,7 @@ class AudioProcessor(object):
         speeds = self._speeds(speed_permille, len(n))
         if speeds is not None:
             pcm, n = self._resampled(pcm, n, speeds, int(sr), int(sr))
+        pcm = self._augmented(pcm, n, augment)
         return self._stacked(*ops.frontend(pcm, n, int(sr), self.feature_type, int(t_max), self.n_mfcc), t_out)
 
     def stage_files(self, decoded, speed_permille=None):
@@ -189,7 +222,7 @@ class AudioProcessor(object):
             by_rate.setdefault(int(sr), []).append(i)
         return [(sr, idx) + self.stage([decoded[i][0] for i in idx]) for sr, idx in by_rate.items()]
 
-    def process_files(self, file_names, t_max=None, rows=None, decoded=None, staged=None, speed_permille=None):
+    def process_files(self, file_names, t_max=None, rows=None, decoded=None, staged=None, speed_permille=None, augment=None):
         """What the reference's dataset map does per file (process_audio_file: librosa.load at 22,050 Hz,
         then the extractor, util/audioprocessor.py:41-61), for a whole mini-batch: files are decoded natively
         on host threads (or passed in as `decoded` [(signal, sr), ...]), uploaded once, resampled to
@@ -197,7 +230,9 @@ class AudioProcessor(object):
         `rows` > len(files) pads the batch with empty utterances (length 0).  Model frames as process_batch.
         speed_permille: a speed factor per file (speed perturbation, None: 1000 each); per source rate ONE ops.resample_rows call does
         the rate conversion and the speed change together, and a group whose rows all have ratio 1 makes no call.  A row made longer than
-        max_input_seq_length is truncated by the front end like any over-long file."""
+        max_input_seq_length is truncated by the front end like any over-long file.
+        augment: (rir_index, noise_index, noise_offset, snr_decidb) per file, indices into augment_bank: reverberation, then noise,
+        ONCE on the assembled [B, width] tensor at load_sr, behind the per-rate groups; None or no index >= 0: nothing is launched."""
         t_out, t_max = t_max, self._source_t_max(t_max)
         if decoded is None:
             decoded = decode_files(file_names)
@@ -221,8 +256,89 @@ class AudioProcessor(object):
                 pcm[ii, :part.shape[1]] = part
                 for j, i in enumerate(idx):
                     n[i] = lens[j]
+        pcm = self._augmented(pcm, n, augment)
         # (an empty row has no frames; the front end wants > n_fft/2 samples for real ones)
         return self._stacked(*ops.frontend(pcm, n, self.load_sr, self.feature_type, int(t_max), self.n_mfcc), t_out)
+
+
+AUDIO_SUFFIXES = (".wav", ".flac", ".sph")
+
+
+class AugmentBank(object):
+    """Room impulse responses and noise clips for the waveform augmentation (ops.reverb_rows / ops.noise_mix_rows), resident on the
+    device, built once per dataset.
+    rirs / noises: lists of 1-D float arrays at the processor's load_sr (from_dirs decodes and resamples files).  An impulse
+    response is cut to max_taps samples, scaled IN FLOAT64 to unit energy (one of zero energy is refused) and given delay =
+    argmax |h|, the direct path, so that reverberant speech stays aligned with its labels; the responses are stored as ONE
+    zero-padded tensor rir_bank [R, taps_max] with rir_taps / rir_delay (python ints).  A noise clip is cut to max_noise_samples;
+    the clips are ONE tensor noise_bank [M, m_max] with noise_len (python ints) and noise_sumsq (float64 [M] on the device,
+    ops.row_sumsq).  A part with no arrays is None.  The two tensors together may not exceed bank_mb MiB (`augment_bank_mb`)."""
+
+    def __init__(self, rirs=(), noises=(), device="cuda", max_taps=8192, max_noise_samples=None, bank_mb=256):
+        if not 1 <= int(max_taps) <= 8192:
+            raise ValueError("reverb_max_taps must be in 1 .. 8192, not %r" % (max_taps,))
+        rirs = [np.asarray(h, np.float64).ravel()[:int(max_taps)] for h in rirs]
+        noises = [np.asarray(v, np.float32).ravel()[:max_noise_samples] for v in noises]
+        for i, h in enumerate(rirs):
+            if h.size == 0 or not np.isfinite(h).all() or not np.sum(h * h) > 0.0:
+                raise ValueError("impulse response %d is empty, not finite or has no energy" % i)
+        for i, v in enumerate(noises):
+            if v.size == 0 or not np.isfinite(v).all():
+                raise ValueError("noise clip %d is empty or not finite" % i)
+        taps_max, m_max = max([h.size for h in rirs] + [0]), max([v.size for v in noises] + [0])
+        nbytes = 4 * (len(rirs) * taps_max + len(noises) * m_max)
+        if nbytes > int(bank_mb) << 20:
+            raise ValueError("the augmentation bank needs %.1f MiB, augment_bank_mb allows %d: raise augment_bank_mb, lower "
+                             "noise_max_seconds or use fewer files" % (nbytes / 2.0 ** 20, int(bank_mb)))
+        self.device, self.nbytes = device, nbytes
+        self.rir_bank, self.rir_taps, self.rir_delay = None, [], []
+        self.noise_bank, self.noise_len, self.noise_sumsq = None, [], None
+        if rirs:
+            host = np.zeros((len(rirs), taps_max), np.float32)
+            for i, h in enumerate(rirs):
+                host[i, :h.size] = h / np.sqrt(np.sum(h * h))
+                self.rir_taps.append(int(h.size))
+                self.rir_delay.append(int(np.argmax(np.abs(h))))
+            self.rir_bank = torch.from_numpy(host).to(device)
+        if noises:
+            host = np.zeros((len(noises), m_max), np.float32)
+            for i, v in enumerate(noises):
+                host[i, :v.size] = v
+                self.noise_len.append(int(v.size))
+            self.noise_bank = torch.from_numpy(host).to(device)
+            self.noise_sumsq = ops.row_sumsq(self.noise_bank, self.noise_len)
+
+    @staticmethod
+    def list_files(directory):
+        """The audio files under a directory (recursively), sorted: the order the draws index."""
+        import os
+        found = []
+        for root, _, names in os.walk(directory):
+            found += [os.path.join(root, f) for f in names if f.lower().endswith(AUDIO_SUFFIXES)]
+        return sorted(found)
+
+    @classmethod
+    def from_dirs(cls, load_sr, noise_dir="", reverb_dir="", device="cuda", max_taps=8192, noise_max_seconds=30.0, bank_mb=256):
+        """The bank of two directories of WAVE / FLAC / SPHERE files (either may be empty: that part is off), decoded by the
+        native decoders and brought to load_sr by ops.resample."""
+        def load(directory, what, limit):
+            if not directory:
+                return []
+            files = cls.list_files(directory)
+            if not files:
+                raise ValueError("%s %r holds no %s file" % (what, directory, " / ".join(AUDIO_SUFFIXES)))
+            out = []
+            for sig, sr in decode_files(files):
+                sig = sig[:max(1, int(np.ceil(limit * sr / float(load_sr))))]      # (what survives the cut below, at the source rate)
+                if sr != load_sr and sig.size:
+                    pcm = torch.from_numpy(np.ascontiguousarray(sig[None, :])).to(device)
+                    res, n = ops.resample(pcm, [len(sig)], sr, load_sr)
+                    sig = res[0, :n[0]].cpu().numpy()
+                out.append(sig)
+            return out
+        max_noise = max(1, int(float(noise_max_seconds) * load_sr))
+        return cls(load(reverb_dir, "reverb_dir", int(max_taps)), load(noise_dir, "noise_dir", max_noise), device=device,
+                   max_taps=max_taps, max_noise_samples=max_noise, bank_mb=bank_mb)
 
 
 class _Staged(object):

@@ -684,22 +684,7 @@ __global__ void fbank_pass_kernel(float* __restrict__ logmel, float* __restrict_
     }
 }
 
-// Host-side length vectors reach the device as KERNEL ARGUMENTS of a one-block kernel (no pageable
-// H2D copy, no stream synchronisation on the hot path), two values per row of row_args.h's block a launch; the front end's own
-// batches wider than ROW_ARGS_MAX fall back to a copy.
-struct MetaArg { int v[2 * ROW_ARGS_MAX]; };
-__global__ void write_meta_kernel(MetaArg m, int* dst, int n) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = m.v[i];
-}
-// dst[0 .. count) = src[0 .. count), stream-ordered: one launch per 2 * ROW_ARGS_MAX values
-static void write_ints(hipStream_t s, int* dst, const int* src, int count) {
-    for (int i0 = 0; i0 < count; i0 += 2 * ROW_ARGS_MAX) {
-        MetaArg m;
-        const int cnt = count - i0 < 2 * ROW_ARGS_MAX ? count - i0 : 2 * ROW_ARGS_MAX;
-        for (int i = 0; i < cnt; ++i) m.v[i] = src[i0 + i];
-        hipLaunchKernelGGL(write_meta_kernel, dim3(1), dim3(256), 0, s, m, dst + i0, cnt);
-    }
-}
+// (write_ints, the hand-off of host-side length vectors as kernel arguments of one-block launches, is row_args.h's.)
 
 // ---- the plan: which kernels a call takes and their launch geometry, as plain numbers (amdspeech.h: amdspeech_frontend_plan_info).
 // run_frontend plans first (nothing is dereferenced, nothing is launched, no device is needed) and LAUNCHES from the struct;

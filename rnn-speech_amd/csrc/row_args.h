@@ -42,4 +42,20 @@ static int with_row_args(hipStream_t s, const int* rows, int B, Launch&& launch)
     return AMDSPEECH_OK;
 }
 
+// Host-side int vectors that kernels read from a WORKSPACE (frontend.hip, augment.hip) reach the device as KERNEL ARGUMENTS of a
+// one-block kernel (no pageable H2D copy, no stream synchronisation on the hot path), two values per row of the block above a launch.
+struct MetaArg { int v[2 * ROW_ARGS_MAX]; };
+static __global__ void write_meta_kernel(MetaArg m, int* dst, int n) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = m.v[i];
+}
+// dst[0 .. count) = src[0 .. count), stream-ordered: one launch per 2 * ROW_ARGS_MAX values
+static inline void write_ints(hipStream_t s, int* dst, const int* src, int count) {
+    for (int i0 = 0; i0 < count; i0 += 2 * ROW_ARGS_MAX) {
+        MetaArg m;
+        const int cnt = count - i0 < 2 * ROW_ARGS_MAX ? count - i0 : 2 * ROW_ARGS_MAX;
+        for (int i = 0; i < cnt; ++i) m.v[i] = src[i0 + i];
+        hipLaunchKernelGGL(write_meta_kernel, dim3(1), dim3(256), 0, s, m, dst + i0, cnt);
+    }
+}
+
 }  // namespace amdspeech

@@ -1,7 +1,7 @@
 """config.ini reader + checkpoint-side pickle logic (reference:
 /root/reference/util/hyperparams.py:17-141).  Same section/key names and defaults; a few
 optional keys are added for the MI355X build (n_mfcc, sample_rate, frame_stack / frame_skip, feature_norm*, spec_augment_*,
-speed_perturb_* ...)."""
+speed_perturb_*, noise_* / reverb_* / augment_* ...)."""
 import configparser
 import logging
 import os
@@ -102,7 +102,47 @@ def read_config_file(config_file):
     d["speed_perturb_seed"] = cp.getint(_TRAINING, "speed_perturb_seed", fallback=0)
     if not 0 <= d["speed_perturb_seed"] <= 2 ** 32 - 1:
         raise ValueError("speed_perturb_seed must be in 0 .. %d, not %r" % (2 ** 32 - 1, d["speed_perturb_seed"]))
+    # noise and reverberation augmentation of the TRAINING waveforms (ops.reverb_rows / ops.noise_mix_rows), behind the speed
+    # perturbation: directories of noise clips and of room impulse responses, the probability of each per utterance and epoch, the
+    # SNR range in dB.  A part is off when its directory is empty or its probability 0 (the default).  NOT structural, like SpecAugment
+    d.update(read_augment_keys(lambda key, dflt: cp.get(_TRAINING, key, fallback=dflt)))
     return d
+
+
+def read_augment_keys(get):
+    """The noise_* / reverb_* / augment_* keys from get(key, default) -> text, checked; a bad value raises ValueError naming its key."""
+    def number(key, dflt, kind, lo, hi):
+        text = get(key, dflt)
+        try:
+            v = kind(str(text).strip())
+        except (ValueError, OverflowError):
+            raise ValueError("%s must be %s, not %r" % (key, "an integer" if kind is int else "a decimal", text))
+        if not lo <= v <= hi:          # (a NaN fails both comparisons)
+            raise ValueError("%s must be in %s .. %s, not %r" % (key, lo, hi, text))
+        return v
+
+    d = {"noise_dir": (get("noise_dir", "") or "").strip(), "reverb_dir": (get("reverb_dir", "") or "").strip()}
+    d["noise_prob"] = number("noise_prob", "0", float, 0.0, 1.0)
+    d["reverb_prob"] = number("reverb_prob", "0", float, 0.0, 1.0)
+    d["noise_snr_db"] = parse_snr_range(get("noise_snr_db", "5, 20"))
+    d["noise_max_seconds"] = number("noise_max_seconds", "30", float, 0.001, 3600.0)
+    d["reverb_max_taps"] = number("reverb_max_taps", "8192", int, 1, 8192)
+    d["augment_bank_mb"] = number("augment_bank_mb", "256", int, 1, 1 << 20)
+    d["augment_seed"] = number("augment_seed", "0", int, 0, 2 ** 32 - 1)
+    return d
+
+
+def parse_snr_range(text):
+    """"5, 20" -> (50, 200): lo and hi of the SNR draw in tenths of a dB, lo <= hi inside -20 .. 60 dB; one number is both."""
+    try:
+        vals = [int(round(10 * float(tok))) for tok in (text or "").split(",") if tok.strip()]
+    except (ValueError, OverflowError):
+        raise ValueError("noise_snr_db must be 'lo, hi' in dB, not %r" % text)
+    if len(vals) == 1:
+        vals = vals * 2
+    if len(vals) != 2 or not -200 <= vals[0] <= vals[1] <= 600:
+        raise ValueError("noise_snr_db must be 'lo, hi' with -20 <= lo <= hi <= 60 dB, not %r" % text)
+    return vals[0], vals[1]
 
 
 def parse_speed_factors(text):

@@ -77,6 +77,15 @@ class ResampleRowsPlanInfo(C.Structure):     # amdspeech_resample_rows_plan_info
     _fields_ = [(n, C.c_int) for n in ("tile", "tiles_per_row", "workgroups", "span_max", "table_chunk", "lds_bytes", "any_copy", "meta_launches")]
 
 
+class ReverbRowsPlanInfo(C.Structure):     # amdspeech_reverb_rows_plan_info (include/amdspeech.h): the launch geometry of a reverberation call, read-only
+    _fields_ = [(n, C.c_int) for n in ("tile", "tiles_per_row", "workgroups", "taps", "span_max", "k_chunk", "k_chunks", "lds_bytes", "copy_rows",
+                                       "meta_launches")]
+
+
+class NoiseMixRowsPlanInfo(C.Structure):     # amdspeech_noise_mix_rows_plan_info (include/amdspeech.h): the launch geometry of a noise-mixing call, read-only
+    _fields_ = [(n, C.c_int) for n in ("tile", "tiles_per_row", "workgroups", "lds_bytes", "copy_rows", "meta_launches")]
+
+
 GEMM_FAMILIES = ("skinny_n", "skinny_k", "skinny_tn", "tn_direct", "kc_direct", "lds", "bf3", "bf16p")      # AMDSPEECH_GEMM_* (include/amdspeech.h)
 GEMM_MAP_LINEAR, GEMM_MAP_XCD, GEMM_MAP_XCD_BLOCKS, GEMM_MAP_KC_BAND = range(4)      # AMDSPEECH_GEMM_MAP_*
 GEMM_GROUP_MAX = 10                                                                 # AMDSPEECH_GEMM_GROUP_MAX
@@ -168,6 +177,18 @@ PROTOTYPES = {
     "amdspeech_resample_rows_plan": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                C.POINTER(ResampleRowsPlanInfo)]),
     "amdspeech_speed_perturb_draw": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.c_int]),
+    "amdspeech_reverb_rows_workspace_bytes": (_SZ, [_I]),
+    "amdspeech_reverb_rows": (_I, [_P, _P, C.POINTER(_I), _I, _I, _P, C.POINTER(_I), C.POINTER(_I), _I, _I, C.POINTER(_I), _P, _P]),
+    "amdspeech_reverb_rows_plan": (_I, [C.POINTER(_I), _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _I, C.POINTER(_I),
+                                        C.POINTER(ReverbRowsPlanInfo)]),
+    "amdspeech_row_sumsq_workspace_bytes": (_SZ, [_I]),
+    "amdspeech_row_sumsq": (_I, [_P, _P, C.POINTER(_I), _I, _I, _P, _P]),
+    "amdspeech_noise_mix_rows_workspace_bytes": (_SZ, [_I]),
+    "amdspeech_noise_mix_rows": (_I, [_P, _P, C.POINTER(_I), _I, _I, _P, C.POINTER(_I), _P, _I, _I, _P, C.POINTER(_I), C.POINTER(_I),
+                                      C.POINTER(_I), _P, _P]),
+    "amdspeech_noise_mix_rows_plan": (_I, [C.POINTER(_I), _I, _I, C.POINTER(_I), _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I),
+                                           C.POINTER(NoiseMixRowsPlanInfo)]),
+    "amdspeech_augment_draw": (_I, [C.c_uint64, C.c_uint64, _I, _I, _I, _I, C.POINTER(_I), _I, _I, C.POINTER(_I)]),
     "amdspeech_audio_probe": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]),
     "amdspeech_audio_decode": (C.c_int, [C.c_char_p, _P, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_int), C.c_int]),
     "amdspeech_optim_workspace_bytes": (_SZ, [_L]),

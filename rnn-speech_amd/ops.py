@@ -975,6 +975,119 @@ def speed_perturb_draw(seed, index, factors_permille):
     return got
 
 
+# ------------------------------------------------ noise and reverberation augmentation
+_augment_ws = {}
+
+
+def _chk_rows(what, pcm, out=None):
+    """pcm (and out) are contiguous float32 device tensors [B, n_max]; returns (B, n_max)."""
+    _chk_f32(pcm, out)
+    if pcm.dim() != 2:
+        raise ValueError("%s: expected [B, n_max], got %s" % (what, tuple(pcm.shape)))
+    if out is not None and (out.shape != pcm.shape or out.device != pcm.device):
+        raise ValueError("%s: out is %s on %s, expected %s beside pcm" % (what, tuple(out.shape), out.device, tuple(pcm.shape)))
+    return pcm.shape
+
+
+def _chk_f64_vec(what, t, count, device):
+    if not (torch.is_tensor(t) and t.dtype == torch.float64 and t.dim() == 1 and t.shape[0] == count and t.is_contiguous()
+            and t.device == device):
+        raise ValueError("%s: expected %d contiguous float64 values on %s" % (what, count, device))
+
+
+def reverb_rows_plan(n_samples, n_max, rir_taps, rir_delay, taps_max, rir_index):
+    """The launch geometry of `reverb_rows` for these rows (amdspeech.h: amdspeech_reverb_rows_plan), as a dict of ints.  Read-only:
+    nothing is launched, no device is needed.  What the call refuses raises here too."""
+    B, R = len(n_samples), len(rir_taps)
+    info = _l.ReverbRowsPlanInfo()
+    _l.check(_l.load().amdspeech_reverb_rows_plan(_c_ints(n_samples, B, "reverb_rows_plan"), B, int(n_max),
+                                                  _c_ints(rir_taps, R, "reverb_rows_plan"), _c_ints(rir_delay, R, "reverb_rows_plan"), R,
+                                                  int(taps_max), _c_ints(rir_index, B, "reverb_rows_plan"), C.byref(info)),
+             "reverb_rows_plan")
+    return _plan_dict(info)
+
+
+def reverb_rows(pcm, n_samples, rir_bank, rir_taps, rir_delay, rir_index, out=None):
+    """pcm float32 [B, n_max] (device), n_samples and rir_index python ints per row; rir_bank float32 [R, taps_max] (device) with
+    rir_taps / rir_delay python ints per impulse response -> out [B, n_max]: row b convolved with impulse response rir_index[b],
+    shifted by its delay and cut to the row's length, in ONE launch (amdspeech.h: amdspeech_reverb_rows).  A row with index -1 is
+    copied bit for bit.  Every word of out is written; input words at or past a row's length are not read."""
+    B, n_max = _chk_rows("reverb_rows", pcm, out)
+    _chk_f32(rir_bank)
+    if rir_bank.dim() != 2 or rir_bank.device != pcm.device:
+        raise ValueError("reverb_rows: rir_bank is %s on %s, expected [R, taps_max] beside pcm" % (tuple(rir_bank.shape), rir_bank.device))
+    lib = _l.load()
+    R, taps_max = rir_bank.shape
+    if out is None:
+        out = torch.empty_like(pcm)
+    ws = _cached_ws(_augment_ws, ("reverb", B, pcm.device), lambda: lib.amdspeech_reverb_rows_workspace_bytes(B))
+    _l.check(lib.amdspeech_reverb_rows(_stream(), _p(pcm), _c_ints(n_samples, B, "reverb_rows"), B, n_max, _p(rir_bank),
+                                       _c_ints(rir_taps, R, "reverb_rows"), _c_ints(rir_delay, R, "reverb_rows"), R, taps_max,
+                                       _c_ints(rir_index, B, "reverb_rows"), _p(out), _p(ws)), "reverb_rows")
+    return out          # stream-ordered; the row values were kernel arguments, the cached workspace outlives the kernels
+
+
+def row_sumsq(pcm, n_samples, out=None):
+    """pcm float32 [B, n_max] (device), n_samples python ints -> float64 [B] (device): the sum of squares of each row's first n
+    samples, in a fixed order (amdspeech.h: amdspeech_row_sumsq): the same bits every call."""
+    B, n_max = _chk_rows("row_sumsq", pcm)
+    lib = _l.load()
+    if out is None:
+        out = torch.empty(B, device=pcm.device, dtype=torch.float64)
+    else:
+        _chk_f64_vec("row_sumsq: out", out, B, pcm.device)
+    ws = _cached_ws(_augment_ws, ("sumsq", B, pcm.device), lambda: lib.amdspeech_row_sumsq_workspace_bytes(B))
+    _l.check(lib.amdspeech_row_sumsq(_stream(), _p(pcm), _c_ints(n_samples, B, "row_sumsq"), B, n_max, _p(out), _p(ws)), "row_sumsq")
+    return out
+
+
+def noise_mix_rows_plan(n_samples, n_max, noise_len, m_max, noise_index, noise_offset, snr_decidb):
+    """The launch geometry of `noise_mix_rows` (amdspeech.h: amdspeech_noise_mix_rows_plan), as a dict of ints.  Read-only, no device."""
+    B, M = len(n_samples), len(noise_len)
+    info = _l.NoiseMixRowsPlanInfo()
+    what = "noise_mix_rows_plan"
+    _l.check(_l.load().amdspeech_noise_mix_rows_plan(_c_ints(n_samples, B, what), B, int(n_max), _c_ints(noise_len, M, what), M, int(m_max),
+                                                     _c_ints(noise_index, B, what), _c_ints(noise_offset, B, what),
+                                                     _c_ints(snr_decidb, B, what), C.byref(info)), what)
+    return _plan_dict(info)
+
+
+def noise_mix_rows(pcm, n_samples, row_sumsq, noise_bank, noise_len, noise_sumsq, noise_index, noise_offset, snr_decidb, out=None):
+    """pcm float32 [B, n_max] (device) with row_sumsq float64 [B] (device, ops.row_sumsq of pcm); noise_bank float32 [M, m_max]
+    (device) with noise_len python ints and noise_sumsq float64 [M] (device); noise_index / noise_offset / snr_decidb python ints per
+    row -> out: clip noise_index[b], from noise_offset[b] on and wrapping around, added to row b at snr_decidb[b] / 10 dB in ONE launch
+    (amdspeech.h: amdspeech_noise_mix_rows).  out None: a new tensor; out = pcm: in place.  A row with index -1, no samples or no
+    energy (its own or the clip's) keeps its bits."""
+    B, n_max = _chk_rows("noise_mix_rows", pcm, out)
+    _chk_f32(noise_bank)
+    if noise_bank.dim() != 2 or noise_bank.device != pcm.device:
+        raise ValueError("noise_mix_rows: noise_bank is %s on %s, expected [M, m_max] beside pcm" % (tuple(noise_bank.shape), noise_bank.device))
+    M, m_max = noise_bank.shape
+    _chk_f64_vec("noise_mix_rows: row_sumsq", row_sumsq, B, pcm.device)
+    _chk_f64_vec("noise_mix_rows: noise_sumsq", noise_sumsq, M, pcm.device)
+    lib = _l.load()
+    if out is None:
+        out = torch.empty_like(pcm)
+    what = "noise_mix_rows"
+    ws = _cached_ws(_augment_ws, ("mix", B, pcm.device), lambda: lib.amdspeech_noise_mix_rows_workspace_bytes(B))
+    _l.check(lib.amdspeech_noise_mix_rows(_stream(), _p(pcm), _c_ints(n_samples, B, what), B, n_max, _p(noise_bank), _c_ints(noise_len, M, what),
+                                          _p(noise_sumsq), M, m_max, _p(row_sumsq), _c_ints(noise_index, B, what),
+                                          _c_ints(noise_offset, B, what), _c_ints(snr_decidb, B, what), _p(out), _p(ws)), what)
+    return out
+
+
+def augment_draw(seed, index, reverb_permille, n_rirs, noise_permille, noise_len, snr_decidb):
+    """(rir_index, noise_index, noise_offset, snr_decidb) of utterance `index` under `seed`: SpecAugment's integer hash on the host
+    (amdspeech.h: amdspeech_augment_draw).  n_rirs impulse responses, clips of noise_len samples, snr_decidb = (lo, hi) inclusive;
+    an index of -1: that part is not applied."""
+    M = len(noise_len)
+    out = (C.c_int * 4)()
+    _l.check(_l.load().amdspeech_augment_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(index) & 0xFFFFFFFFFFFFFFFF, int(reverb_permille),
+                                              int(n_rirs), int(noise_permille), M, _c_ints(noise_len, M, "augment_draw"),
+                                              int(snr_decidb[0]), int(snr_decidb[1]), out), "augment_draw")
+    return tuple(out)
+
+
 def frontend_plan(mode, sample_rate, n_mfcc, B, n_max, t_max):
     """The kernels `frontend` takes for a call (amdspeech.h: amdspeech_frontend_plan), as a dict of ints.  mode "mfcc" / "fbank".
     Read-only: nothing is launched, no device is needed.  A call the front end refuses raises here too."""

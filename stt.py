@@ -142,6 +142,23 @@ def speed_perturb_option(hyper_params):
     return factors, int(hyper_params.get("speed_perturb_seed", 0))
 
 
+def augment_option(hyper_params, device="cuda"):
+    """AcousticDataset's augment from the noise_* / reverb_* / augment_* keys: None when both parts are off (the default: nothing is
+    read, launched or allocated), else (bank, reverb permille, noise permille, SNR range in tenths of a dB, seed) with the bank
+    built from the two directories at sample_rate."""
+    from rnn_speech_amd.audioprocessor import AugmentBank
+    get = hyper_params.get
+    reverb = int(round(1000 * get("reverb_prob", 0.0))) if get("reverb_dir") else 0
+    noise = int(round(1000 * get("noise_prob", 0.0))) if get("noise_dir") else 0
+    if reverb == 0 and noise == 0:
+        return None
+    bank = AugmentBank.from_dirs(get("sample_rate", 22050), noise_dir=get("noise_dir") if noise else "",
+                                 reverb_dir=get("reverb_dir") if reverb else "", device=device,
+                                 max_taps=get("reverb_max_taps", 8192), noise_max_seconds=get("noise_max_seconds", 30.0),
+                                 bank_mb=get("augment_bank_mb", 256))
+    return bank, reverb, noise, tuple(get("noise_snr_db", (50, 200))), int(get("augment_seed", 0))
+
+
 def _model_length(hyper_params):
     """Frames the model runs: max_input_seq_length in source frames, divided by frame_skip (rounded up)."""
     return hyper_params.get("out_seq_length", -(-hyper_params["max_input_seq_length"] // hyper_params.get("frame_skip", 1)))
@@ -177,8 +194,9 @@ def build_acoustic_training_rnn(sess, hyper_params, prog_params, train_set, test
                 sample_rate=hyper_params.get("sample_rate", 22050),
                 frame_stack=hyper_params.get("frame_stack", 1), frame_skip=hyper_params.get("frame_skip", 1),
                 **_feature_norm_options(hyper_params))
-    # speed perturbation: the TRAINING dataset only
-    train_dataset = model.build_dataset(train_set, *ds_args, speed_perturb=speed_perturb_option(hyper_params), **pipe)
+    # speed perturbation, noise and reverberation: the TRAINING dataset only
+    train_dataset = model.build_dataset(train_set, *ds_args, speed_perturb=speed_perturb_option(hyper_params),
+                                        augment=augment_option(hyper_params), **pipe)
     test_dataset = model.build_dataset(test_set, *ds_args, **pipe)
     t_iterator, v_iterator = model.add_datasets_input(train_dataset, test_dataset)
     sess.run(t_iterator.initializer)
