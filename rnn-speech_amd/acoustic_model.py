@@ -21,19 +21,8 @@ from . import dataparallel
 from . import labels as _labels
 from . import ops
 from .audioprocessor import AudioProcessor
+from .dataset import AcousticDataset, DatasetIterator, OutOfRangeError, bucketed_order  # noqa: F401 (the pipeline's names stay importable here)
 from .engine import Engine
-
-
-class OutOfRangeError(Exception):
-    """Stands in for tf.errors.OutOfRangeError (iterator exhausted)."""
-
-
-class _Op(object):
-    def __init__(self, fn):
-        self.fn = fn
-
-    def __call__(self):
-        return self.fn()
 
 
 class Session(object):
@@ -59,357 +48,14 @@ class _Variable(object):
         return self.value
 
 
-# --------------------------------------------------------------------- datasets
-class AcousticDataset(object):
-    """What build_dataset returns: items [audio, label, (length)] where `audio` is a file
-    path or an in-memory (signal, sample_rate) pair, batched to [T_max, B, D] device tensors
-    with the reference's padding rules (:825-827, :144-159).
-
-    The reference maps files through two py_func threads and prefetches 30 items (:820-822), and recomputes
-    every feature every epoch.  Here a producer thread decodes the NEXT `prefetch` mini-batches (native
-    decoders on a thread pool, GIL released) while the GPU trains on the current one, and -- optionally --
-    the features of file items are kept in host memory after their first use (`feature_cache_mb` > 0), so
-    later epochs skip decode, resampling and the front end altogether.
-
-    frame_stack / frame_skip: low frame rate input (AudioProcessor).  max_input_seq_length stays in SOURCE frames; the batches,
-    their lengths, T and the feature cache are in MODEL frames (T = audio.out_seq_length rows of audio.feature_size values).
-    feature_norm / feature_norm_variance / feature_stats: feature normalisation (AudioProcessor); the batches and the feature
-    cache hold normalised features.
-    speed_perturb: None (off: nothing is launched), or (factors_permille, seed) -- speed perturbation of the waveform on the GPU
-    (ops.resample_rows).  The factor of an item is ops.speed_perturb_draw(seed64, (epoch_serial << 32) | position in self.items,
-    factors) with seed64 = (seed + data-parallel rank) << 32; epoch_serial is a counter shared with the with_items siblings that
-    advances once per batches() pass, so a re-shuffled epoch draws afresh and a run is reproducible.  Durations used for bucketing
-    stay the unperturbed ones; a row made longer than max_input_seq_length is truncated like any over-long file.  Cached features
-    would freeze the draw: feature_cache_mb > 0 beside it is refused.
-    augment: None (off: nothing is launched, nothing is allocated), or (bank, reverb_permille, noise_permille, (snr_lo, snr_hi) in
-    tenths of a dB, seed) -- reverberation and additive noise on the waveform on the GPU, behind the speed change
-    (AudioProcessor._augmented); bank is an audioprocessor.AugmentBank at sample_rate, shared with the with_items siblings.  The draw
-    of an item is ops.augment_draw with the seed64 / epoch_serial / position scheme of the speed draw (and its rank handling), on
-    the producer thread.  feature_cache_mb > 0 beside it is refused for the same reason."""
-
-    def __init__(self, input_set, batch_size, max_input_seq_length, max_target_seq_length,
-                 signal_processing, char_map, n_mfcc=20, device="cuda", prefetch=2, feature_cache_mb=0,
-                 sample_rate=22050, frame_stack=1, frame_skip=1, feature_norm="none", feature_norm_variance=True,
-                 feature_stats=None, speed_perturb=None, augment=None):
-        self.items = [(it[0], it[1]) for it in input_set]
-        self.batch_size = batch_size
-        self.U = max_target_seq_length
-        self.char_map = char_map
-        self._augment = self._augment_option(augment, feature_cache_mb)
-        self.audio = AudioProcessor(max_input_seq_length, signal_processing, n_mfcc=n_mfcc, device=device,
-                                    load_sr=sample_rate, frame_stack=frame_stack, frame_skip=frame_skip,
-                                    feature_norm=feature_norm, feature_norm_variance=feature_norm_variance,
-                                    feature_stats=feature_stats, augment_bank=None if self._augment is None else self._augment[0])
-        self.T = self.audio.out_seq_length
-        self.prefetch = int(prefetch)
-        self._signal_processing, self._n_mfcc = signal_processing, n_mfcc
-        self._cache = {} if feature_cache_mb > 0 else None
-        self._room = [int(feature_cache_mb) << 20]          # shared (by reference) with reordered siblings
-        self._speed = self._speed_option(speed_perturb, feature_cache_mb)
-        self._epoch = [0]                                   # speed perturbation's epoch_serial, shared in the same way
-        # the data-parallel rank, resolved HERE on the caller's thread: the draws run on the decode-ahead thread
-        self._rank = dataparallel.current().rank if (self._speed is not None or self._augment is not None) else 0
-
-    @staticmethod
-    def _speed_option(speed_perturb, feature_cache_mb):
-        if speed_perturb is None:
-            return None
-        factors, seed = speed_perturb
-        factors = tuple(int(f) for f in factors)
-        if not 1 <= len(factors) <= 8 or any(not 500 <= f <= 2000 for f in factors):
-            raise ValueError("speed_perturb: 1 .. 8 factors of 500 .. 2000 permille, not %r" % (factors,))
-        if factors == (1000,):
-            return None
-        if feature_cache_mb > 0:
-            raise ValueError("speed_perturb with feature_cache_mb > 0: cached features would freeze the draw; set feature_cache_mb : 0")
-        return factors, int(seed)
-
-    def speed_draws(self, epoch_serial, start=0, count=None):
-        """The speed factors (permille) of items start .. start + count of pass `epoch_serial`; None when the option is off."""
-        if self._speed is None:
-            return None
-        factors, seed = self._speed
-        seed64 = ((seed + self._rank) << 32) & 0xFFFFFFFFFFFFFFFF
-        stop = len(self.items) if count is None else min(start + count, len(self.items))
-        return [ops.speed_perturb_draw(seed64, (int(epoch_serial) << 32) | pos, factors) for pos in range(start, stop)]
-
-    @staticmethod
-    def _augment_option(augment, feature_cache_mb):
-        if augment is None:
-            return None
-        bank, reverb_permille, noise_permille, snr, seed = augment
-        reverb_permille, noise_permille, snr = int(reverb_permille), int(noise_permille), (int(snr[0]), int(snr[1]))
-        if not (0 <= reverb_permille <= 1000 and 0 <= noise_permille <= 1000):
-            raise ValueError("augment: probabilities of 0 .. 1000 permille, not %r, %r" % (reverb_permille, noise_permille))
-        if not -200 <= snr[0] <= snr[1] <= 600:
-            raise ValueError("augment: an SNR range lo <= hi inside -200 .. 600 tenths of a dB, not %r" % (snr,))
-        if bank is None or bank.rir_bank is None:
-            reverb_permille = 0
-        if bank is None or bank.noise_bank is None:
-            noise_permille = 0
-        if reverb_permille == 0 and noise_permille == 0:
-            return None
-        if feature_cache_mb > 0:
-            raise ValueError("noise / reverberation augmentation with feature_cache_mb > 0: cached features would freeze the draw; "
-                             "set feature_cache_mb : 0")
-        return bank, reverb_permille, noise_permille, snr, int(seed)
-
-    def augment_draws(self, epoch_serial, start=0, count=None):
-        """(rir_index, noise_index, noise_offset, snr_decidb) of items start .. start + count of pass `epoch_serial`; None when the
-        option is off."""
-        if self._augment is None:
-            return None
-        bank, reverb_permille, noise_permille, snr, seed = self._augment
-        seed64 = ((seed + self._rank) << 32) & 0xFFFFFFFFFFFFFFFF
-        stop = len(self.items) if count is None else min(start + count, len(self.items))
-        return [ops.augment_draw(seed64, (int(epoch_serial) << 32) | pos, reverb_permille, len(bank.rir_taps), noise_permille,
-                                 bank.noise_len, snr) for pos in range(start, stop)]
-
-    def with_items(self, input_set):
-        """The same dataset over a re-ordered / re-shuffled item list, sharing the feature cache (the
-        reference builds a fresh tf.data pipeline at every epoch, stt.py:198-207)."""
-        other = AcousticDataset(input_set, self.batch_size, self.audio.max_input_seq_length, self.U, self._signal_processing,
-                                self.char_map, n_mfcc=self._n_mfcc, device=self.audio.device, prefetch=self.prefetch,
-                                sample_rate=self.audio.load_sr, frame_stack=self.audio.frame_stack,
-                                frame_skip=self.audio.frame_skip, feature_norm=self.audio.feature_norm,
-                                feature_norm_variance=self.audio.feature_norm_variance, feature_stats=self.audio.feature_stats,
-                                speed_perturb=self._speed, augment=self._augment)
-        other._cache, other._room, other._epoch, other._rank = self._cache, self._room, self._epoch, self._rank
-        return other
-
-    # ---- producer side (host only) -------------------------------------------------
-    def _chunks(self):
-        B = self.batch_size
-        for start in range(0, len(self.items), B):
-            yield start, self.items[start:start + B]
-
-    def _prepare(self, chunk, speeds=None, draws=None):
-        """Host half of one mini-batch: cached features or decoded waveforms per item.  speeds: the items' speed factors; draws:
-        their augmentation draws (carried to the consumer)."""
-        from .audioprocessor import decode_files
-        cache = self._cache
-        need = [a for a, _ in chunk if isinstance(a, str) and (cache is None or a not in cache)]
-        from_disk = dict(zip(need, decode_files(need)))
-        parts = []
-        for a, _ in chunk:
-            if not isinstance(a, str):
-                parts.append(("signal", (np.asarray(a[0], np.float32), int(a[1]))))
-            elif a in from_disk:
-                parts.append(("decoded", from_disk[a]))
-            else:
-                parts.append(("cached", cache[a]))
-        # everything the consumer would otherwise do on the training thread between two kernel launches: the label codec
-        # (0.12 ms per utterance) and the packing of the waveforms into one pinned block for an asynchronous upload
-        B = self.batch_size
-        dense = np.zeros((B, self.U), np.int32)
-        for i, (_, text) in enumerate(chunk):
-            ids = _labels.get_str_labels(self.char_map, text)[:self.U]
-            dense[i, :len(ids)] = ids
-        kinds = {k for k, _ in parts}
-        staged = None
-        if kinds == {"signal"} and len({p[1] for _, p in parts}) == 1:
-            sigs = [p[0] for _, p in parts] + [np.zeros(0, np.float32)] * (B - len(parts))
-            staged = ("batch", self.audio.stage(sigs), parts[0][1][1])
-        elif "cached" not in kinds:
-            staged = ("files", self.audio.stage_files([p for _, p in parts], speeds))
-        return chunk, parts, dense, staged, speeds, draws
-
-    def _prepared(self, epoch_serial=0):
-        if self.prefetch <= 0:
-            for start, chunk in self._chunks():
-                yield self._prepare(chunk, self.speed_draws(epoch_serial, start, len(chunk)),
-                                    self.augment_draws(epoch_serial, start, len(chunk)))
-            return
-        import queue
-        import threading
-        q = queue.Queue(maxsize=self.prefetch)
-        stop = threading.Event()
-
-        def produce():
-            try:
-                for start, chunk in self._chunks():
-                    if stop.is_set():
-                        return
-                    q.put(("ok", self._prepare(chunk, self.speed_draws(epoch_serial, start, len(chunk)),
-                                               self.augment_draws(epoch_serial, start, len(chunk)))))
-                q.put(("end", None))
-            except BaseException as exc:            # surfaced in the consumer
-                q.put(("error", exc))
-
-        th = threading.Thread(target=produce, name="amdspeech-decode", daemon=True)
-        th.start()
-        try:
-            while True:
-                tag, payload = q.get()
-                if tag == "end":
-                    return
-                if tag == "error":
-                    raise payload
-                yield payload
-        finally:
-            stop.set()
-            while th.is_alive() or not q.empty():   # unblock a producer waiting on a full queue; hand its staging blocks back
-                try:
-                    tag, payload = q.get_nowait()
-                    if tag == "ok":
-                        self._release(payload[3])
-                except queue.Empty:
-                    th.join(0.01)
-
-    @staticmethod
-    def _release(staged):
-        """A prepared mini-batch that will never be uploaded (the iterator was reset): its pinned blocks return to the pool."""
-        if staged is None:
-            return
-        blocks = [staged[1][0]] if staged[0] == "batch" else [part[2] for part in staged[1]]
-        for blk in blocks:
-            blk.claimed = False
-
-    # ---- consumer side (device) -----------------------------------------------------
-    def batches(self):
-        B, T = self.batch_size, self.T
-        epoch_serial = self._epoch[0]              # this pass's draws (speed, noise, reverberation); the next pass draws afresh
-        self._epoch[0] += 1
-        for chunk, parts, dense, staged, speeds, draws in self._prepared(epoch_serial):
-            extra = {} if draws is None else {"augment": draws}      # (off: the call is the one it was before the option existed)
-            if staged is not None and staged[0] == "batch":
-                # in-memory signals at one rate: the process_signal convention (no resampling)
-                feat, lengths = self.audio.process_batch(None, staged[2], t_max=T, staged=staged[1],
-                                                         speed_permille=None if speeds is None else speeds + [1000] * (B - len(speeds)),
-                                                         **extra)
-            elif staged is not None:
-                # files: librosa.load semantics (22,050 Hz); a short final batch is padded with empty rows
-                feat, lengths = self.audio.process_files(None, t_max=T, rows=B, decoded=[p for _, p in parts], staged=staged[1],
-                                                         speed_permille=speeds, **extra)
-            else:
-                feat, lengths = self._assemble(parts)
-            if self._cache is not None:
-                self._remember(chunk, parts, feat, lengths)
-            yield feat, np.asarray(lengths, np.int32), dense
-
-    def _assemble(self, parts):
-        """A mini-batch with cached rows: fresh rows go through the device path, cached rows are copied in."""
-        B, T, D = self.batch_size, self.T, self.audio.feature_size
-        fresh = [i for i, (k, _) in enumerate(parts) if k != "cached"]
-        lengths = [0] * B
-        host = np.zeros((T, B, D), np.float32)
-        for i, (k, p) in enumerate(parts):
-            if k == "cached":
-                f, n = p
-                host[:f.shape[0], i] = f
-                lengths[i] = n
-        feat = torch.from_numpy(host).to(self.audio.device)
-        if fresh:
-            sub, sub_len = self.audio.process_files(None, t_max=T, decoded=[parts[i][1] for i in fresh])
-            feat[:, torch.as_tensor(fresh, device=feat.device)] = sub
-            for j, i in enumerate(fresh):
-                lengths[i] = sub_len[j]
-        return feat, lengths
-
-    def _remember(self, chunk, parts, feat, lengths):
-        rows = [i for i, (k, _) in enumerate(parts) if k == "decoded"]
-        if not rows or self._room[0] <= 0:
-            return
-        host = feat[:, torch.as_tensor(rows, device=feat.device)].cpu().numpy()
-        for j, i in enumerate(rows):
-            n = min(int(lengths[i]), self.T)
-            f = host[:n, j].copy()
-            if f.nbytes > self._room[0]:
-                self._room[0] = 0
-                return
-            self._room[0] -= f.nbytes
-            self._cache[chunk[i][0]] = (f, int(lengths[i]))
-
-
-def bucketed_order(items, batch_size, rng=None):
-    """Length-bucketed batching: items [audio, label, duration] sorted by duration, cut into
-    mini-batches, and the mini-batches -- not the items -- shuffled.  Every batch then holds utterances of
-    similar length, so the recurrence (which stops at the batch's longest utterance) wastes no frames."""
-    import random
-    ordered = sorted(items, key=lambda it: (it[2] if len(it) > 2 and it[2] is not None else 0.0))
-    groups = [ordered[i:i + batch_size] for i in range(0, len(ordered), batch_size)]
-    tail = [groups.pop()] if groups and len(groups[-1]) < batch_size else []     # a short group stays last,
-    (rng or random).shuffle(groups)                                              # or every later batch straddles
-    return [it for g in groups + tail for it in g]
-
-
-class DatasetIterator(object):
-    """Iterator over a dataset's mini-batches.  `prefetch()` prepares the NEXT mini-batch ahead of its use: the
-    host part comes from the dataset's decode-ahead thread, the device part (upload, resampling, front-end
-    kernels) is enqueued on a side stream, so it runs under the tail of the training step in flight (the
-    reference's tf.data pipeline overlaps feature extraction with training the same way, :820-822)."""
-
-    _UNSET = object()
-
-    def __init__(self, dataset):
-        self._dataset = dataset
-        self._gen = None
-        self._ahead = self._UNSET
-        self._side = None
-        self.initializer = _Op(self._reset)
-
-    def _reset(self):
-        self._gen = self._dataset.batches()
-        self._ahead = self._UNSET
-
-    @property
-    def dataset(self):
-        return self._dataset
-
-    def make_initializer(self, dataset):
-        def _swap():
-            self._dataset = dataset
-            self._reset()
-        return _Op(_swap)
-
-    def prefetch(self, after=None):
-        """Prepare the next mini-batch ahead of its use.  after: an event the device half must wait for.
-        Returns the event that marks the device half done (None when there is nothing new in flight)."""
-        if self._gen is None or self._ahead is not self._UNSET:
-            return None
-        if not torch.cuda.is_available():        # host-only runs (multi-process CPU tests): nothing to overlap
-            try:
-                self._ahead = (next(self._gen), None)
-            except StopIteration:
-                self._ahead = None
-            return None
-        if self._side is None:
-            self._side = torch.cuda.Stream()
-        if after is not None:
-            self._side.wait_event(after)
-        try:
-            with torch.cuda.stream(self._side):
-                batch = next(self._gen)
-                done = torch.cuda.Event()
-                done.record(self._side)
-            self._ahead = (batch, done)
-            return done
-        except StopIteration:
-            self._ahead = None
-            return None
-
-    def has_next(self):
-        """True when another mini-batch is available (prepares it ahead if that has not happened yet)."""
-        if self._gen is None:
-            return False
-        self.prefetch()
-        return self._ahead is not None
-
-    def get_next(self):
-        if self._gen is None:
-            raise RuntimeError("iterator used before its initializer was run")
-        self.prefetch()
-        ahead, self._ahead = self._ahead, self._UNSET
-        if ahead is None:
-            self._ahead = None
-            raise OutOfRangeError()
-        batch, done = ahead
-        if done is not None:
-            cur = torch.cuda.current_stream()
-            cur.wait_event(done)
-            if torch.is_tensor(batch[0]):
-                batch[0].record_stream(cur)
-        return batch
+def _truth_rows(dense, num_labels):
+    """The reference's truth per row of a dense label matrix (:155-159): the ids without 0 (the EOS token stays), an empty row
+    is [C-1]."""
+    rows = []
+    for row in np.asarray(dense):
+        kept = row[row != 0]
+        rows.append(kept if len(kept) else np.array([num_labels - 1], np.int32))
+    return rows
 
 
 def _edit_distance(a, b):
@@ -482,11 +128,7 @@ class _AsyncBeamDecoder(object):
             done.record(self._copy_stream)
         self._last_copy = done
         lens = np.minimum(np.asarray(lengths, np.int32), Tr).astype(np.int32)
-        truth_rows = []
-        for row in np.asarray(dense):
-            kept = row[row != 0]
-            truth_rows.append(kept if len(kept) else np.array([num_labels - 1], np.int32))      # (:155-159)
-        fut = self._pool.submit(self._decode, buf, done, Tr, lens, truth_rows, num_labels)
+        fut = self._pool.submit(self._decode, buf, done, Tr, lens, _truth_rows(dense, num_labels), num_labels)
         self._pending.append((fut, buf))
 
     def _decode(self, buf, done, Tr, lens, truth_rows, num_labels):
@@ -557,7 +199,7 @@ class AcousticModel(object):
         self.grad_clip = 1.0
         self.lr_decay_factor = 1.0
         self.learning_rate_var = _Variable(0.0)
-        self.learning_rate_decay_op = _Op(self._decay_lr)
+        self.learning_rate_decay_op = self._decay_lr
         self.global_step = _Variable(0)
         self.is_training = False
         self.tensorboard_dir = None
@@ -790,20 +432,9 @@ class AcousticModel(object):
         return _edit_distance_tokens(list(first_string.replace(" ", "")), list(second_string.replace(" ", "")))
 
     # ---- input plumbing ----------------------------------------------------------
-    @staticmethod
-    def build_dataset(input_set, batch_size, max_input_seq_length, max_target_seq_length,
-                      signal_processing, char_map, n_mfcc=20, prefetch=2, feature_cache_mb=0, sample_rate=22050,
-                      frame_stack=1, frame_skip=1, feature_norm="none", feature_norm_variance=True, feature_stats=None,
-                      speed_perturb=None, augment=None):
-        """max_input_seq_length in SOURCE frames, whatever frame_stack / frame_skip (the dataset's T is in model frames).
-        speed_perturb: None, or (factors_permille, seed): speed perturbation of the waveforms (AcousticDataset).
-        augment: None, or (bank, reverb_permille, noise_permille, (snr_lo, snr_hi) decidb, seed): noise and reverberation."""
-        return AcousticDataset(input_set, batch_size, max_input_seq_length, max_target_seq_length,
-                               signal_processing, char_map, n_mfcc=n_mfcc, prefetch=prefetch,
-                               feature_cache_mb=feature_cache_mb, sample_rate=sample_rate,
-                               frame_stack=frame_stack, frame_skip=frame_skip, feature_norm=feature_norm,
-                               feature_norm_variance=feature_norm_variance, feature_stats=feature_stats,
-                               speed_perturb=speed_perturb, augment=augment)
+    # the reference's build_dataset(input_set, batch_size, max_input_seq_length, max_target_seq_length, signal_processing, char_map)
+    # plus this build's keyword options IS the dataset's constructor: parameters and options are described there, once
+    build_dataset = staticmethod(AcousticDataset)
 
     def add_dataset_input(self, dataset):
         self._single_iter = DatasetIterator(dataset)
@@ -818,31 +449,30 @@ class AcousticModel(object):
         labels_ph does in the reference."""
         self._placeholder_batch = (inputs, np.asarray(input_seq_lengths, np.int32), np.asarray(labels, np.int32))
 
+    def _iterator(self):
+        """The iterator the next mini-batch comes from: the single one, else the training or the validation one; None without
+        a dataset."""
+        if self._single_iter is not None:
+            return self._single_iter
+        return self._train_iter if self.is_training else self._valid_iter
+
     def _prefetch_next(self, after=None):
-        if self._placeholder_batch is not None:
+        it = self._iterator()
+        if self._placeholder_batch is not None or it is None:
             return None
-        it = self._single_iter
-        if it is None:
-            it = self._train_iter if self.is_training else self._valid_iter
-        if it is not None:
-            return it.prefetch(after)
-        return None
+        return it.prefetch(after)
 
     def _has_next(self):
         if self._placeholder_batch is not None:
             return True
-        it = self._single_iter
-        if it is None:
-            it = self._train_iter if self.is_training else self._valid_iter
+        it = self._iterator()
         return it is not None and it.has_next()
 
     def _next_batch(self):
         if self._placeholder_batch is not None:
             b, self._placeholder_batch = self._placeholder_batch, None
             return b
-        it = self._single_iter
-        if it is None:
-            it = self._train_iter if self.is_training else self._valid_iter
+        it = self._iterator()
         if it is None:
             raise RuntimeError("no input: add a dataset or feed() a batch first")
         return it.get_next()
@@ -1010,10 +640,7 @@ class AcousticModel(object):
                 ops.merge_repeated(ids, out_len, self.num_labels)
         truth = np.zeros_like(dense)
         tlen = np.zeros(self.batch_size, np.int32)
-        for b in range(self.batch_size):
-            kept = dense[b][dense[b] != 0]
-            if len(kept) == 0:
-                kept = np.array([self.num_labels - 1], np.int32)
+        for b, kept in enumerate(_truth_rows(dense[:self.batch_size], self.num_labels)):
             truth[b, :len(kept)] = kept
             tlen[b] = len(kept)
         dev = self.engine.device

@@ -195,6 +195,13 @@ class AudioProcessor(object):
                                      [d[3] for d in draws], out=pcm)
         return pcm
 
+    def _features(self, pcm, n, sr, t_out, augment):
+        """The tail of both process_* calls: augmentation, the front end at rate sr, normalisation and stacking to t_out model frames."""
+        pcm = self._augmented(pcm, n, augment)
+        # (an empty row has no frames; the front end wants > n_fft/2 samples for real ones)
+        feat, lengths = ops.frontend(pcm, n, int(sr), self.feature_type, int(self._source_t_max(t_out)), self.n_mfcc)
+        return self._stacked(feat, lengths, t_out)
+
     def process_batch(self, signals, sr, t_max=None, staged=None, speed_permille=None, augment=None):
         """signals: list of 1-D float arrays, all at sample rate `sr`.  Returns (feat [t_max, B, feature_size] device
         float32, zero past each utterance; list of UNtruncated frame counts) -- model frames under low frame rate input,
@@ -202,7 +209,6 @@ class AudioProcessor(object):
         perturbation, ops.resample_rows: a row played f times faster has 1 / f of its samples); None or all 1000: nothing is launched.
         augment: (rir_index, noise_index, noise_offset, snr_decidb) per signal, indices into augment_bank (whose audio is taken to be at
         `sr`): reverberation, then noise, behind the speed change; None or no index >= 0: nothing is launched."""
-        t_out, t_max = t_max, self._source_t_max(t_max)
         if staged is not None:
             pcm, n = self._upload_staged(staged[0]), staged[1]
         else:
@@ -210,8 +216,7 @@ class AudioProcessor(object):
         speeds = self._speeds(speed_permille, len(n))
         if speeds is not None:
             pcm, n = self._resampled(pcm, n, speeds, int(sr), int(sr))
-        pcm = self._augmented(pcm, n, augment)
-        return self._stacked(*ops.frontend(pcm, n, int(sr), self.feature_type, int(t_max), self.n_mfcc), t_out)
+        return self._features(pcm, n, sr, t_max, augment)
 
     def stage_files(self, decoded, speed_permille=None):
         """stage() for decoded files, grouped by source rate as process_files uploads them: [(sr, idx, block, n)].  speed_permille
@@ -233,7 +238,6 @@ class AudioProcessor(object):
         max_input_seq_length is truncated by the front end like any over-long file.
         augment: (rir_index, noise_index, noise_offset, snr_decidb) per file, indices into augment_bank: reverberation, then noise,
         ONCE on the assembled [B, width] tensor at load_sr, behind the per-rate groups; None or no index >= 0: nothing is launched."""
-        t_out, t_max = t_max, self._source_t_max(t_max)
         if decoded is None:
             decoded = decode_files(file_names)
         B = rows or len(decoded)
@@ -256,9 +260,7 @@ class AudioProcessor(object):
                 pcm[ii, :part.shape[1]] = part
                 for j, i in enumerate(idx):
                     n[i] = lens[j]
-        pcm = self._augmented(pcm, n, augment)
-        # (an empty row has no frames; the front end wants > n_fft/2 samples for real ones)
-        return self._stacked(*ops.frontend(pcm, n, self.load_sr, self.feature_type, int(t_max), self.n_mfcc), t_out)
+        return self._features(pcm, n, self.load_sr, t_max, augment)
 
 
 AUDIO_SUFFIXES = (".wav", ".flac", ".sph")

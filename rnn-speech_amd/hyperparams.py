@@ -64,9 +64,7 @@ def read_config_file(config_file):
     # low frame rate input: frame_stack consecutive 10 ms frames concatenated into one model frame, every frame_skip-th kept
     # (1 / 1: off, the reference's behaviour).  max_input_seq_length stays in source frames
     for key in ("frame_stack", "frame_skip"):
-        d[key] = cp.getint(_ACOUSTIC, key, fallback=1)
-        if not 1 <= d[key] <= 16:
-            raise ValueError("%s must be in 1 .. 16, not %r" % (key, d[key]))
+        d[key] = check_range(key, cp.getint(_ACOUSTIC, key, fallback=1), 1, 16)
     # feature normalisation between the front end and the frame stacking (ops.feature_norm): none (the reference's behaviour) |
     # utterance (mean / variance of the utterance itself) | global (of the training corpus, from the file feature_norm_stats names,
     # which `stt.py --feature_stats` writes).  feature_norm_variance False: means only
@@ -89,19 +87,13 @@ def read_config_file(config_file):
     # keys change the training data, not the model, and a checkpoint stays usable when they change
     for key, top in (("spec_augment_freq_masks", 8), ("spec_augment_freq_width", 4096), ("spec_augment_time_masks", 16),
                      ("spec_augment_time_width", 2 ** 31 - 1), ("spec_augment_seed", 2 ** 32 - 1)):
-        d[key] = cp.getint(_TRAINING, key, fallback=0)
-        if not 0 <= d[key] <= top:
-            raise ValueError("%s must be in 0 .. %d, not %r" % (key, top, d[key]))
-    ratio = cp.getfloat(_TRAINING, "spec_augment_time_ratio", fallback=1.0)
-    if not 0.0 <= ratio <= 1.0:          # (a NaN fails both comparisons)
-        raise ValueError("spec_augment_time_ratio must be in 0 .. 1, not %r" % ratio)
+        d[key] = check_range(key, cp.getint(_TRAINING, key, fallback=0), 0, top)
+    ratio = check_range("spec_augment_time_ratio", cp.getfloat(_TRAINING, "spec_augment_time_ratio", fallback=1.0), 0.0, 1.0)
     d["spec_augment_time_permille"] = int(round(1000 * ratio))
     # speed perturbation of the TRAINING waveforms (ops.resample_rows): a comma-separated list of speed factors, each rounded to
     # permille, one of which is drawn per utterance and epoch.  Absent, empty or 1.0 alone: off.  NOT structural, like SpecAugment
     d["speed_perturb_factors"] = parse_speed_factors(cp.get(_TRAINING, "speed_perturb_factors", fallback=""))
-    d["speed_perturb_seed"] = cp.getint(_TRAINING, "speed_perturb_seed", fallback=0)
-    if not 0 <= d["speed_perturb_seed"] <= 2 ** 32 - 1:
-        raise ValueError("speed_perturb_seed must be in 0 .. %d, not %r" % (2 ** 32 - 1, d["speed_perturb_seed"]))
+    d["speed_perturb_seed"] = check_range("speed_perturb_seed", cp.getint(_TRAINING, "speed_perturb_seed", fallback=0), 0, 2 ** 32 - 1)
     # noise and reverberation augmentation of the TRAINING waveforms (ops.reverb_rows / ops.noise_mix_rows), behind the speed
     # perturbation: directories of noise clips and of room impulse responses, the probability of each per utterance and epoch, the
     # SNR range in dB.  A part is off when its directory is empty or its probability 0 (the default).  NOT structural, like SpecAugment
@@ -117,9 +109,7 @@ def read_augment_keys(get):
             v = kind(str(text).strip())
         except (ValueError, OverflowError):
             raise ValueError("%s must be %s, not %r" % (key, "an integer" if kind is int else "a decimal", text))
-        if not lo <= v <= hi:          # (a NaN fails both comparisons)
-            raise ValueError("%s must be in %s .. %s, not %r" % (key, lo, hi, text))
-        return v
+        return check_range(key, v, lo, hi)
 
     d = {"noise_dir": (get("noise_dir", "") or "").strip(), "reverb_dir": (get("reverb_dir", "") or "").strip()}
     d["noise_prob"] = number("noise_prob", "0", float, 0.0, 1.0)
@@ -138,11 +128,9 @@ def parse_snr_range(text):
         vals = [int(round(10 * float(tok))) for tok in (text or "").split(",") if tok.strip()]
     except (ValueError, OverflowError):
         raise ValueError("noise_snr_db must be 'lo, hi' in dB, not %r" % text)
-    if len(vals) == 1:
-        vals = vals * 2
-    if len(vals) != 2 or not -200 <= vals[0] <= vals[1] <= 600:
-        raise ValueError("noise_snr_db must be 'lo, hi' with -20 <= lo <= hi <= 60 dB, not %r" % text)
-    return vals[0], vals[1]
+    if not 1 <= len(vals) <= 2:
+        raise ValueError("noise_snr_db must be 'lo, hi' in dB, not %r" % text)
+    return check_snr_decidb("noise_snr_db", (vals[0], vals[-1]))
 
 
 def parse_speed_factors(text):
@@ -152,12 +140,27 @@ def parse_speed_factors(text):
         factors = [int(round(1000 * float(tok))) for tok in (text or "").split(",") if tok.strip()]
     except (ValueError, OverflowError):          # (int() of a NaN / of an infinity)
         raise ValueError("speed_perturb_factors must be a comma-separated list of decimals, not %r" % text)
-    if len(factors) > 8:
-        raise ValueError("speed_perturb_factors holds %d factors, at most 8" % len(factors))
-    for f in factors:
-        if not 500 <= f <= 2000:
-            raise ValueError("speed_perturb_factors: %g outside 0.5 .. 2.0" % (f / 1000.0))
-    return [] if factors == [1000] else factors
+    return [] if factors in ([], [1000]) else check_speed_factors("speed_perturb_factors", factors)
+
+
+# One checker per option, for the config keys above and for the arguments AcousticDataset takes (a probability is check_range's
+# 0 .. 1 as a config key, 0 .. 1000 in permille); each returns what it was given
+def check_speed_factors(name, factors):
+    if not 1 <= len(factors) <= 8 or any(not 500 <= f <= 2000 for f in factors):
+        raise ValueError("%s: 1 .. 8 factors of 500 .. 2000 permille (0.5 .. 2.0), not %r" % (name, factors))
+    return factors
+
+
+def check_snr_decidb(name, snr):
+    if not -200 <= snr[0] <= snr[1] <= 600:
+        raise ValueError("%s: lo <= hi inside -200 .. 600 tenths of a dB (-20 .. 60 dB), not %r" % (name, snr))
+    return snr
+
+
+def check_range(name, v, lo, hi):
+    if not lo <= v <= hi:          # (a NaN fails both comparisons)
+        raise ValueError("%s must be in %s .. %s, not %r" % (name, lo, hi, v))
+    return v
 
 
 class HyperParameterHandler(object):

@@ -91,13 +91,9 @@ def build_audio_processor(hyper_params):
     """The front end of every mode, from the config keys; fills in what the model is built from.  Low frame rate input (frame_stack /
     frame_skip): the model reads input_dim = frame_stack * D values per frame and runs out_seq_length = ceil(max_input_seq_length /
     frame_skip) frames; at 1 / 1 these are the feature width and max_input_seq_length themselves."""
-    audio_processor = audioprocessor.AudioProcessor(hyper_params["max_input_seq_length"],
-                                                    hyper_params["signal_processing"],
-                                                    n_mfcc=hyper_params.get("n_mfcc", 20),
-                                                    load_sr=hyper_params.get("sample_rate", 22050),
-                                                    frame_stack=hyper_params.get("frame_stack", 1),
-                                                    frame_skip=hyper_params.get("frame_skip", 1),
-                                                    **_feature_norm_options(hyper_params))
+    opts = pipeline_options(hyper_params)
+    audio_processor = audioprocessor.AudioProcessor(hyper_params["max_input_seq_length"], hyper_params["signal_processing"],
+                                                    load_sr=opts.pop("sample_rate"), **opts)
     hyper_params["input_dim"] = audio_processor.feature_size
     hyper_params["out_seq_length"] = audio_processor.out_seq_length
     hyper_params["spec_augment"] = spec_augment_policy(hyper_params, audio_processor)
@@ -105,15 +101,22 @@ def build_audio_processor(hyper_params):
         logging.warning("out_seq_length %d (max_input_seq_length %d at frame_skip %d) is below max_target_seq_length %d: "
                         "a transcript with more tokens than its utterance has frames is ignored by the loss",
                         hyper_params["out_seq_length"], hyper_params["max_input_seq_length"],
-                        hyper_params.get("frame_skip", 1), hyper_params["max_target_seq_length"])
+                        audio_processor.frame_skip, hyper_params["max_target_seq_length"])
     return audio_processor
 
 
-def _feature_norm_options(hyper_params):
-    """AudioProcessor's feature normalisation arguments from the config keys; the statistics file is read in global mode only."""
-    mode = hyper_params.get("feature_norm", "none")
-    return dict(feature_norm=mode, feature_norm_variance=hyper_params.get("feature_norm_variance", True),
-                feature_stats=hyper_params.get("feature_norm_stats") if mode == "global" else None)
+def pipeline_options(hyper_params, dataset=False):
+    """The input pipeline's keyword arguments from the config keys, THE place their defaults live: what AudioProcessor (which
+    calls sample_rate load_sr), AcousticModel.build_dataset (dataset=True: with the decode-ahead depth and the feature cache)
+    and the model's own attributes take.  The statistics file is read in global mode only."""
+    get = hyper_params.get
+    mode = get("feature_norm", "none")
+    opts = dict(n_mfcc=get("n_mfcc", 20), sample_rate=get("sample_rate", 22050), frame_stack=get("frame_stack", 1),
+                frame_skip=get("frame_skip", 1), feature_norm=mode, feature_norm_variance=get("feature_norm_variance", True),
+                feature_stats=get("feature_norm_stats") if mode == "global" else None)
+    if dataset:
+        opts.update(prefetch=get("prefetch_batches", 2), feature_cache_mb=get("feature_cache_mb", 0))
+    return opts
 
 
 def spec_augment_policy(hyper_params, audio_processor):
@@ -152,7 +155,7 @@ def augment_option(hyper_params, device="cuda"):
     noise = int(round(1000 * get("noise_prob", 0.0))) if get("noise_dir") else 0
     if reverb == 0 and noise == 0:
         return None
-    bank = AugmentBank.from_dirs(get("sample_rate", 22050), noise_dir=get("noise_dir") if noise else "",
+    bank = AugmentBank.from_dirs(pipeline_options(hyper_params)["sample_rate"], noise_dir=get("noise_dir") if noise else "",
                                  reverb_dir=get("reverb_dir") if reverb else "", device=device,
                                  max_taps=get("reverb_max_taps", 8192), noise_max_seconds=get("noise_max_seconds", 30.0),
                                  bank_mb=get("augment_bank_mb", 256))
@@ -161,7 +164,7 @@ def augment_option(hyper_params, device="cuda"):
 
 def _model_length(hyper_params):
     """Frames the model runs: max_input_seq_length in source frames, divided by frame_skip (rounded up)."""
-    return hyper_params.get("out_seq_length", -(-hyper_params["max_input_seq_length"] // hyper_params.get("frame_skip", 1)))
+    return hyper_params.get("out_seq_length", -(-hyper_params["max_input_seq_length"] // pipeline_options(hyper_params)["frame_skip"]))
 
 
 def _set_model_options(model, hyper_params):
@@ -169,12 +172,10 @@ def _set_model_options(model, hyper_params):
     model.bidirectional = hyper_params.get("bidirectional", False)
     model.bidirectional_mode = hyper_params.get("bidirectional_mode", "top")
     model.sync_batch_norm = hyper_params.get("sync_batch_norm", False)
-    model.frame_stack = hyper_params.get("frame_stack", 1)
-    model.frame_skip = hyper_params.get("frame_skip", 1)
     model.spec_augment = hyper_params.get("spec_augment")       # (build_audio_processor; only run_step with gradients masks)
-    norm = _feature_norm_options(hyper_params)
-    model.feature_norm, model.feature_norm_variance, model.feature_stats = (norm["feature_norm"], norm["feature_norm_variance"],
-                                                                            norm["feature_stats"])
+    opts = pipeline_options(hyper_params)                       # (evaluate_full builds its AudioProcessor from these five)
+    for name in ("frame_stack", "frame_skip", "feature_norm", "feature_norm_variance", "feature_stats"):
+        setattr(model, name, opts[name])
 
 
 def build_acoustic_training_rnn(sess, hyper_params, prog_params, train_set, test_set):
@@ -189,11 +190,7 @@ def build_acoustic_training_rnn(sess, hyper_params, prog_params, train_set, test
     model.train_decoder_lag = hyper_params.get("train_decoder_lag", 1)
     if hyper_params["dataset_size_ordering"] == "Bucketed":
         train_set[:] = bucketed_order(train_set, hyper_params["batch_size"])
-    pipe = dict(n_mfcc=hyper_params.get("n_mfcc", 20), prefetch=hyper_params.get("prefetch_batches", 2),
-                feature_cache_mb=hyper_params.get("feature_cache_mb", 0),
-                sample_rate=hyper_params.get("sample_rate", 22050),
-                frame_stack=hyper_params.get("frame_stack", 1), frame_skip=hyper_params.get("frame_skip", 1),
-                **_feature_norm_options(hyper_params))
+    pipe = pipeline_options(hyper_params, dataset=True)
     # speed perturbation, noise and reverberation: the TRAINING dataset only
     train_dataset = model.build_dataset(train_set, *ds_args, speed_perturb=speed_perturb_option(hyper_params),
                                         augment=augment_option(hyper_params), **pipe)
@@ -377,11 +374,11 @@ def evaluate(hyper_params):
         sys.exit(1)
     logging.info("Using %d size of test set", len(test_set))
     model = _forward_model(hyper_params, hyper_params["batch_size"])
+    opts = pipeline_options(hyper_params)
     try:
         wer, cer = model.evaluate_full(None, test_set, hyper_params["max_input_seq_length"],
                                        hyper_params["signal_processing"], hyper_params["char_map"],
-                                       n_mfcc=hyper_params.get("n_mfcc", 20),
-                                       sample_rate=hyper_params.get("sample_rate", 22050))
+                                       n_mfcc=opts["n_mfcc"], sample_rate=opts["sample_rate"])
     finally:
         model.close()
     print("Resulting WER : {0:.3g} %".format(wer))
@@ -399,11 +396,10 @@ def feature_stats(train_set, hyper_params):
     path = hyper_params.get("feature_norm_stats")
     if not path:
         sys.exit("--feature_stats needs feature_norm_stats (the file to write) in the configuration file")
+    off = dict(frame_stack=1, frame_skip=1, feature_norm="none", feature_stats=None, feature_cache_mb=0)
     dataset = AcousticModel.build_dataset(train_set, hyper_params["batch_size"], hyper_params["max_input_seq_length"],
                                           hyper_params["max_target_seq_length"], hyper_params["signal_processing"],
-                                          hyper_params["char_map"], n_mfcc=hyper_params.get("n_mfcc", 20),
-                                          prefetch=hyper_params.get("prefetch_batches", 2),
-                                          sample_rate=hyper_params.get("sample_rate", 22050))
+                                          hyper_params["char_map"], **dict(pipeline_options(hyper_params, dataset=True), **off))
     stats = FeatureStats(describe_processor(dataset.audio))
     for feat, lengths, _ in dataset.batches():
         stats.accumulate(feat, lengths)

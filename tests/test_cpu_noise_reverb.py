@@ -413,6 +413,33 @@ def test_dataset_draws_are_reproducible_and_differ_between_passes(handle):
     assert ranked._rank == 3 and ranked.augment_draws(0) == want(0, rank=3) != want(0) and ranked.with_items(items)._rank == 3
 
 
+def test_with_items_copies_and_shares_the_parents_objects(handle):
+    """A with_items sibling is a copy over a new item list: the processor, the cache, the counters, the rank and the normalised
+    options are the parent's own objects, nothing is rebuilt."""
+    from models.AcousticModel import AcousticModel
+    items = [((np.zeros(4000, np.float32), 16000), "ab")] * 4 + [((np.zeros(3000, np.float32), 16000), "b")]
+    bank = _Bank([64, 200], [700, 9])
+    ds = AcousticModel.build_dataset(items, 3, 90, 12, "mfcc", ["a", "b", "_"], speed_perturb=([900, 1000, 1100], 5),
+                                     augment=(bank, 600, 700, (50, 200), 5), prefetch=0)
+    seen = []
+
+    def process_batch(sig, sr, t_max=None, staged=None, speed_permille=None, augment=None):
+        staged[0].claimed = False                  # (the staging block goes back to its pool: nothing is uploaded here)
+        seen.append((speed_permille, augment))
+        return None, [0] * 3
+    ds.audio.process_batch = process_batch
+    sibling = ds.with_items(items[::-1])
+    assert type(sibling) is type(ds) and sibling is not ds and sibling.audio is ds.audio
+    for name in ("_cache", "_room", "_epoch", "_rank", "_speed", "_augment"):
+        assert getattr(sibling, name) is getattr(ds, name), name
+    assert [t for _, t in sibling.items] == ["b"] + ["ab"] * 4 and [t for _, t in ds.items] == ["ab"] * 4 + ["b"]      # the parent keeps its list
+    assert (sibling.batch_size, sibling.U, sibling.T, sibling.char_map, sibling.prefetch) == (3, 12, 90, ds.char_map, 0)
+    list(sibling.batches())                        # the sibling's pass goes through the parent's processor and counter
+    assert ds._epoch[0] == 1 and len(seen) == 2
+    assert [s for s, _ in seen] == [ds.speed_draws(0, 0, 3), ds.speed_draws(0, 3, 2) + [1000]]
+    assert [a for _, a in seen] == [ds.augment_draws(0, 0, 3), ds.augment_draws(0, 3, 2)]
+
+
 def test_off_leaves_the_calls_as_they_were(handle):
     """Without the option batches() makes the very call it made before the option existed (no `augment` keyword), and the
     processor's stage returns the tensor it was given."""

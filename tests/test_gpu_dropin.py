@@ -165,6 +165,47 @@ def test_dataset_pipeline_prefetch_cache_and_buckets(tmp_path):
         run(AcousticModel.build_dataset(items, *args, n_mfcc=40, prefetch=2))   # files are gone: decode error surfaces
 
 
+def test_with_items_sibling_equals_a_freshly_built_dataset_bit_for_bit():
+    """with_items copies the dataset, it does not rebuild it: two passes and a third over the reversed list through the copy are,
+    bit for bit, what freshly constructed datasets give with every option of the pipeline on (low frame rate input, utterance
+    normalisation, speed perturbation, reverberation and noise).  No tolerance: both runs launch the same kernels with the same
+    arguments and the same epoch serials."""
+    from rnn_speech_amd.acoustic_model import AcousticModel
+    from rnn_speech_amd.audioprocessor import AugmentBank
+    from rnn_speech_amd.labels import ENGLISH_CHAR_MAP
+    sr = 16000
+    items = [[(synth(i, 4800 + 797 * i, sr), sr), txt, None]                                        # 0.3 .. 0.5 s, all different
+             for i, txt in enumerate(["hello there", "it'll do", "good bye", "yes", "no way"])]
+    assert len({len(it[0][0]) for it in items}) == 5 and all(0.3 * sr <= len(it[0][0]) <= 0.5 * sr for it in items)
+
+    def build(input_set):
+        rng = np.random.RandomState(11)
+        bank = AugmentBank(rirs=[rng.randn(64) * np.exp(-np.arange(64) / 9.0), rng.randn(200) * np.exp(-np.arange(200) / 40.0)],
+                           noises=[rng.randn(700).astype(np.float32), rng.randn(9).astype(np.float32)])
+        return AcousticModel.build_dataset(input_set, 3, 90, 12, "mfcc", ENGLISH_CHAR_MAP, n_mfcc=20, sample_rate=sr, frame_stack=3,
+                                           frame_skip=3, feature_norm="utterance", speed_perturb=([900, 1000, 1100], 5),
+                                           augment=(bank, 1000, 1000, (50, 200), 7))
+
+    def run(ds):
+        out = [(f.cpu().numpy().view(np.uint32).copy(), np.array(l), np.array(d)) for f, l, d in ds.batches()]
+        assert len(out) == 2 and out[0][0].shape == (30, 3, 60) and out[1][1][2] == 0          # 5 items, batch 3: a padded tail
+        return out
+
+    ds = build(items)
+    copied = [run(ds), run(ds), run(ds.with_items(items[::-1]))]
+    fresh = build(items)
+    built = [run(fresh), run(fresh)]
+    rebuilt = build(items[::-1])                   # the third pass from the constructor itself, at the same epoch serial
+    assert ds._epoch[0] == 3 and fresh._epoch[0] == 2 and rebuilt._epoch[0] == 0
+    rebuilt._epoch[0] = 2
+    built.append(run(rebuilt))
+    for a, b in zip(copied, built):
+        for (f0, l0, d0), (f1, l1, d1) in zip(a, b):
+            assert np.array_equal(f0, f1) and np.array_equal(l0, l1) and np.array_equal(d0, d1)
+    # (the passes differ from each other: the draws advance with the epoch serial, the third pass holds other rows)
+    assert not np.array_equal(copied[0][0][0], copied[1][0][0]) and not np.array_equal(copied[0][0][2], copied[2][0][2])
+
+
 def test_process_input_values_and_default_beam_decoder():
     """process_input (the reference's forward-only path, :705-721): logits against the float64 oracle, predictions =
     width-100 prefix beam search + merge_repeated (the reference's decoder, :312-314) -- not just shapes."""
