@@ -532,6 +532,14 @@ int amdspeech_ctc_beam_search_host(const float* logits, const int* lengths, int 
 int amdspeech_ctc_beam_search_host_mt(const float* logits, const int* lengths, int T, int B, int C,
                                       int beam_width, int merge_repeated, int* ids, int* out_len,
                                       float* log_prob, int max_threads);
+/* The n-best list of the same search: the first n_best entries of the FINAL beam in the decoder's own total order (score
+ * descending, then the prefixes in lexicographic order), so entry 0 is what the two calls above return, bit for bit.  ids
+ * [B][n_best][T] padded with C, out_len [B][n_best], log_prob [B][n_best], n_found [B] (may be NULL) = min(n_best, beam entries);
+ * unused slots get out_len 0 and log_prob -inf.  merge_repeated collapses each path on its own: two entries may then spell the
+ * same ids (the caller that rescores them drops the duplicates).  All pointers HOST memory.                                  */
+int amdspeech_ctc_beam_search_host_nbest(const float* logits, const int* lengths, int T, int B, int C,
+                                         int beam_width, int merge_repeated, int n_best, int* ids, int* out_len,
+                                         float* log_prob, int* n_found, int max_threads);
 
 /* Levenshtein distance on the HOST (the same un-normalised tf.edit_distance as amdspeech_edit_distance, for predictions that
  * were decoded on the host: the asynchronous training-time beam decoder): all pointers HOST memory.                        */
@@ -984,6 +992,45 @@ int amdspeech_reverse_sequences(void* stream, const float* in, float* out, const
  * y[i] += x[i] (gradient accumulation helper), y[i] = 0.                      */
 int amdspeech_axpy(void* stream, float a, const float* x, float* y, long n);
 int amdspeech_fill(void* stream, float* y, float value, long n);
+
+/* -------------------------------------------------------- language model ----
+ * The two ends of a next-token language-model step over the acoustic model's label alphabet (lm.hip): the token
+ * lookup in front of the LSTM stack and the softmax cross-entropy behind the output Linear.  The reference's LanguageModel feeds
+ * one-hot rows through the input Linear (models/LanguageModel.py) -- the lookup below IS that product for a one-hot row -- and
+ * trains with CTC on shifted labels; the cross-entropy is this build's deviation.
+ *
+ * All pointers are DEVICE memory; the calls are stream-ordered, do not synchronise and do not allocate.  Token arrays are
+ * int32 [B][ld] row-major with ld >= T: position (t, b) reads element b * ld + t, so one buffer serves the inputs (tok) and the
+ * targets (tok + 1).  lengths int32 [B]; a position is inside its row when t < lengths[b].
+ *
+ * amdspeech_embed_fwd: out[t][b][:] = w[id][:] + bias where t < lengths[b] and 0 <= id < V, and bias elsewhere (the zero one-hot
+ *   row); w [V][H], bias [H] or NULL, out [T][B][H]; H a multiple of 4, w / bias / out 16-byte aligned.
+ * amdspeech_embed_bwd: ACCUMULATES like amdspeech_linear_bwd: dw[v][:] += the sum of dz[t][b][:] over the positions inside their
+ *   row that hold v; dbias[:] (may be NULL) += the sum over all positions inside their row.  No floating-point atomics: the order
+ *   of every sum is a fixed function of the arguments (two runs give the same bits), and a row of dw whose token does not occur
+ *   is not written.  ws: amdspeech_embed_bwd_workspace_bytes (0 for a bad shape), 16-byte aligned.
+ * amdspeech_xent_fwd_bwd: logits [T][B][C], 2 <= C <= 4096.  A position is live when t < lengths[b] and 0 <= target < C; there
+ *   nll = logsumexp(row) - row[target] (with the row maximum subtracted) and dlogits = scale * (softmax(row) - onehot(target));
+ *   every other position gets nll = 0 and a zero dlogits row.  loss[b] is the float32 rounding of the float64 sum, in increasing
+ *   t, of the float32 nll[t][b].  nll [T][B] may be NULL; dlogits may be NULL (the scoring call) or BE logits (a row is read
+ *   completely before it is written).  ws: amdspeech_xent_workspace_bytes (0 for a bad shape).
+ * amdspeech_xent_plan: the row kernel and launch geometry of a shape as plain numbers, a READ-ONLY view of the plan the launch
+ *   itself reads (one function decides for both); no device is needed and nothing is launched.  c_min .. c_max is the range of C
+ *   that takes the very same kernel instantiation: the tests walk the boundaries from it.                                    */
+#define AMDSPEECH_XENT_KERNEL_WAVE 0  /* one wavefront per row, values_per_lane logits in each lane's registers (C <= 1024) */
+#define AMDSPEECH_XENT_KERNEL_BLOCK 1 /* one 256-thread workgroup per row, the row maximum and sum across its four waves through LDS */
+typedef struct amdspeech_xent_plan_info {
+    int kernel, values_per_lane, threads, rows_per_workgroup, grid, c_min, c_max, loss_threads, loss_grid;
+} amdspeech_xent_plan_info;
+int amdspeech_embed_fwd(void* stream, const int* ids, int ld, const int* lengths, int T, int B, int V, int H,
+                        const float* w, const float* bias, float* out);
+size_t amdspeech_embed_bwd_workspace_bytes(int T, int B, int V, int H);
+int amdspeech_embed_bwd(void* stream, const int* ids, int ld, const int* lengths, int T, int B, int V, int H,
+                        const float* dz, float* dw, float* dbias, void* ws);
+size_t amdspeech_xent_workspace_bytes(int T, int B, int C);
+int amdspeech_xent_plan(int T, int B, int C, amdspeech_xent_plan_info* out);
+int amdspeech_xent_fwd_bwd(void* stream, const float* logits, const int* targets, int ld, const int* lengths, int T, int B,
+                           int C, float scale, float* nll, float* loss, float* dlogits, void* ws);
 
 #ifdef __cplusplus
 }

@@ -246,6 +246,9 @@ class AcousticModel(object):
         self.save_optimizer_state = True   # native .npz also carries Adam m/v/step and the RNN state
         self.beam_width = 100
         self.merge_repeated = True
+        # config key `lm_weight` > 0: a language_model.NbestRescorer that picks among the beam decoder's n-best paths in process_input /
+        # evaluate_full.  None (the default): the decoder's own best path, nothing of the language model is loaded
+        self.rescorer = None
         self._train_iter = self._valid_iter = self._single_iter = None
         self._acc_loss = self._acc_err = 0.0
         self._mini_batches = 0
@@ -817,7 +820,9 @@ class AcousticModel(object):
 
     def _decode(self, dlen):
         """Dense int32 prediction matrix [B, width] padded with num_labels."""
-        if self.decoder == "beam":
+        if self.decoder == "beam" and self.rescorer is not None:      # config key lm_weight > 0: n-best list, the language model's pick
+            ids, out_len = self.rescorer(self.engine.logits, dlen, self.beam_width, self.merge_repeated)
+        elif self.decoder == "beam":
             ids, out_len, _ = ops.ctc_beam_search(self.engine.logits, dlen, self.beam_width, self.merge_repeated)
         else:
             ids, out_len = ops.ctc_greedy_decode(self.engine.logits, dlen, ws=self.engine.ctc_ws)

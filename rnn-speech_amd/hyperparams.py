@@ -1,7 +1,7 @@
 """config.ini reader + checkpoint-side pickle logic (reference:
 /root/reference/util/hyperparams.py:17-141).  Same section/key names and defaults; a few
 optional keys are added for the MI355X build (n_mfcc, sample_rate, frame_stack / frame_skip, feature_norm*, spec_augment_*,
-speed_perturb_*, noise_* / reverb_* / augment_* ...)."""
+speed_perturb_*, noise_* / reverb_* / augment_* ...) and the reference's [lm_network_params] section with this build's lm_* keys."""
 import configparser
 import logging
 import os
@@ -98,6 +98,36 @@ def read_config_file(config_file):
     # perturbation: directories of noise clips and of room impulse responses, the probability of each per utterance and epoch, the
     # SNR range in dB.  A part is off when its directory is empty or its probability 0 (the default).  NOT structural, like SpecAugment
     d.update(read_augment_keys(lambda key, dflt: cp.get(_TRAINING, key, fallback=dflt)))
+    d.update(read_lm_keys(lambda key, dflt: cp.get(_LM, key, fallback=dflt)))
+    return d
+
+
+_LM = "lm_network_params"
+
+
+def read_lm_keys(get):
+    """The character language model (rnn_speech_amd.language_model): the reference's [lm_network_params] section -- num_layers,
+    hidden_size, dropout (the keep probability of both DropoutWrapper sides), batch_size, learning_rate, lr_decay_factor, grad_clip,
+    defaulting to the values of this build's config.ini -- under lm_* names, plus this build's keys: lm_text_files (comma-separated text files,
+    one sentence per line; empty: the transcripts of the training and test corpora), lm_weight (0, the default: no rescoring,
+    nothing of the language model is loaded), lm_nbest and lm_length_bonus.  None is structural for the acoustic checkpoint.
+    get(key, default) -> text; a bad value raises ValueError naming its key."""
+    def number(key, dflt, kind, lo, hi):
+        text = get(key, dflt)
+        try:
+            v = kind(str(text).strip())
+        except (ValueError, OverflowError):
+            raise ValueError("[%s] %s must be %s, not %r" % (_LM, key, "an integer" if kind is int else "a decimal", text))
+        return check_range(key, v, lo, hi)
+
+    d = {"lm_num_layers": number("num_layers", "2", int, 1, 16), "lm_hidden_size": number("hidden_size", "256", int, 1, 1 << 16),
+         "lm_dropout": number("dropout", "0.9", float, 0.001, 1.0), "lm_batch_size": number("batch_size", "64", int, 1, 1 << 16),
+         "lm_learning_rate": number("learning_rate", "0.001", float, 0.0, 1e3),
+         "lm_lr_decay_factor": number("lr_decay_factor", "0.5", float, 0.0, 1.0), "lm_grad_clip": number("grad_clip", "5", float, 0.0, 1e9)}
+    d["lm_text_files"] = [p.strip() for p in (get("lm_text_files", "") or "").split(",") if p.strip()]
+    d["lm_weight"] = number("lm_weight", "0", float, 0.0, 1e3)
+    d["lm_nbest"] = number("lm_nbest", "16", int, 1, 1000)
+    d["lm_length_bonus"] = number("lm_length_bonus", "0", float, -1e3, 1e3)
     return d
 
 

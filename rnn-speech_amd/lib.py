@@ -86,11 +86,17 @@ class NoiseMixRowsPlanInfo(C.Structure):     # amdspeech_noise_mix_rows_plan_inf
     _fields_ = [(n, C.c_int) for n in ("tile", "tiles_per_row", "workgroups", "lds_bytes", "copy_rows", "meta_launches")]
 
 
+class XentPlanInfo(C.Structure):     # amdspeech_xent_plan_info (include/amdspeech.h): the row kernel and launch geometry of a cross-entropy call, read-only
+    _fields_ = [(n, C.c_int) for n in ("kernel", "values_per_lane", "threads", "rows_per_workgroup", "grid", "c_min", "c_max", "loss_threads",
+                                       "loss_grid")]
+
+
 GEMM_FAMILIES = ("skinny_n", "skinny_k", "skinny_tn", "tn_direct", "kc_direct", "lds", "bf3", "bf16p")      # AMDSPEECH_GEMM_* (include/amdspeech.h)
 GEMM_MAP_LINEAR, GEMM_MAP_XCD, GEMM_MAP_XCD_BLOCKS, GEMM_MAP_KC_BAND = range(4)      # AMDSPEECH_GEMM_MAP_*
 GEMM_GROUP_MAX = 10                                                                 # AMDSPEECH_GEMM_GROUP_MAX
 CTC_KERNELS = ("wave", "shift", "pair", "edge")      # AMDSPEECH_CTC_KERNEL_* (include/amdspeech.h)
 LSTM_PATHS = ("flow", "big1", "big", "hoist", "diag", "diag_bf3")      # AMDSPEECH_LSTM_PATH_* (include/amdspeech.h)
+XENT_KERNELS = ("wave", "block")      # AMDSPEECH_XENT_KERNEL_* (include/amdspeech.h)
 FEATURE_NORM_MODES = ("none", "utterance", "global")      # AMDSPEECH_FEATURE_NORM_* (include/amdspeech.h)
 LSTM_ARMED, LSTM_ARM_NEXT, LSTM_SAME_WS, LSTM_PER_DIAGONAL, LSTM_INJECT_TIMEOUT = 1, 2, 4, 8, 16      # amdspeech_lstm_desc.flags (include/amdspeech.h)
 
@@ -166,6 +172,7 @@ PROTOTYPES = {
     "amdspeech_edit_distance": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _P]),
     "amdspeech_ctc_beam_search_host": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "amdspeech_ctc_beam_search_host_mt": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I]),
+    "amdspeech_ctc_beam_search_host_nbest": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I]),
     "amdspeech_edit_distance_host": (_I, [_P, _P, _I, _P, _P, _I, _I, _P]),
     "amdspeech_crc32c": (C.c_uint32, [_P, _SZ, C.c_uint32]),
     "amdspeech_resample_workspace_bytes": (_SZ, [C.c_int]),
@@ -220,6 +227,12 @@ PROTOTYPES = {
     "amdspeech_reverse_sequences": (_I, [_P, _P, _P, _P, _I, _I, _I, _I]),
     "amdspeech_axpy": (_I, [_P, _F, _P, _P, _L]),
     "amdspeech_fill": (_I, [_P, _P, _F, _L]),
+    "amdspeech_embed_fwd": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "amdspeech_embed_bwd_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "amdspeech_embed_bwd": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "amdspeech_xent_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "amdspeech_xent_plan": (_I, [_I, _I, _I, C.POINTER(XentPlanInfo)]),
+    "amdspeech_xent_fwd_bwd": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P]),
 }
 
 _lib = None

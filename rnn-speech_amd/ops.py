@@ -867,6 +867,27 @@ def ctc_beam_search(logits, lengths, beam_width=100, merge_repeated=True, max_th
     return ids, out_len, logp
 
 
+def ctc_beam_search_nbest(logits, lengths, n_best, beam_width=100, merge_repeated=True, max_threads=0):
+    """The n-best list of the same search (amdspeech.h: amdspeech_ctc_beam_search_host_nbest): the first n_best entries of the
+    final beam, best first; entry 0 is ctc_beam_search's answer.  Returns numpy (ids int32 [B,n_best,T] padded with C,
+    out_len [B,n_best], log_prob float32 [B,n_best] with -inf in unused slots, n_found [B])."""
+    import numpy as np
+    host = logits.detach().cpu().numpy() if torch.is_tensor(logits) else np.asarray(logits)
+    host = np.ascontiguousarray(host, np.float32)
+    T, B, C_ = host.shape
+    n_best = int(n_best)
+    lens = np.ascontiguousarray(lengths.cpu().numpy() if torch.is_tensor(lengths) else lengths, np.int32)
+    ids = np.empty((B, max(n_best, 0), T), np.int32)
+    out_len = np.empty((B, max(n_best, 0)), np.int32)
+    logp = np.empty((B, max(n_best, 0)), np.float32)
+    n_found = np.empty(B, np.int32)
+    _l.check(_l.load().amdspeech_ctc_beam_search_host_nbest(
+        host.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), T, B, C_, int(beam_width),
+        int(bool(merge_repeated)), n_best, ids.ctypes.data_as(C.c_void_p), out_len.ctypes.data_as(C.c_void_p),
+        logp.ctypes.data_as(C.c_void_p), n_found.ctypes.data_as(C.c_void_p), int(max_threads)), "ctc_beam_search_host_nbest")
+    return ids, out_len, logp, n_found
+
+
 # --------------------------------------------------------------------- optimiser
 _optim_ws = {}
 
@@ -1257,3 +1278,76 @@ def feature_norm(feat, n_frames, mode, norm_vars=True, var_floor=FEATURE_NORM_VA
     desc = _l.FeatureNormDesc(imode, int(bool(norm_vars)), float(var_floor))
     _l.check(_l.load().amdspeech_feature_norm(_stream(), _p(feat), nf, B, D, t_in, C.byref(desc), _p(table), _p(ws)), "feature_norm")
     return feat
+
+
+# ---------------------------------------------------------------- language model
+_embed_ws = {}
+_xent_ws = {}
+
+
+def _chk_tokens(what, tok, lengths, T, B):
+    """tok: int32 device matrix [B, >= T] with contiguous rows (a column-shifted view of a wider buffer is fine); returns its ld."""
+    if not (torch.is_tensor(tok) and tok.is_cuda and tok.dtype == torch.int32 and tok.dim() == 2 and tok.shape[0] == B
+            and tok.shape[1] >= T and (tok.shape[1] == 1 or tok.stride(1) == 1) and (B == 1 or tok.stride(0) >= tok.shape[1])):
+        raise ValueError("%s: expected an int32 device matrix [%d, >= %d] with contiguous rows" % (what, B, T))
+    _chk_i32(lengths)
+    if lengths.numel() != B:
+        raise ValueError("%s: %d lengths for %d rows" % (what, lengths.numel(), B))
+    return tok.stride(0) if B > 1 else max(tok.shape[1], tok.stride(0))
+
+
+def embed_fwd(tok, lengths, w, bias, out):
+    """out [T,B,H] = w[tok[b, t]] + bias inside each row's length, bias elsewhere (amdspeech.h: amdspeech_embed_fwd).  out is
+    written in place (the LSTM workspace's Z0 region) and returned."""
+    T, B, H = _chk_f32_3d("embed_fwd", out, "[T, B, H]")
+    _chk_f32(w, bias)
+    ld = _chk_tokens("embed_fwd", tok, lengths, T, B)
+    V = w.shape[0]
+    if w.dim() != 2 or w.shape[1] != H or (bias is not None and bias.numel() != H):
+        raise ValueError("embed_fwd: w %s / bias do not fit H = %d" % (tuple(w.shape), H))
+    _l.check(_l.load().amdspeech_embed_fwd(_stream(), _p(tok), ld, _p(lengths), T, B, V, H, _p(w), _p(bias), _p(out)), "embed_fwd")
+    return out
+
+
+def embed_bwd(tok, lengths, dz, dw, dbias):
+    """dw [V,H] += the rows of dz [T,B,H] summed per token, dbias [H] (or None) += their sum: no atomics, a fixed order
+    (amdspeech.h: amdspeech_embed_bwd)."""
+    T, B, H = _chk_f32_3d("embed_bwd", dz, "[T, B, H]")
+    _chk_f32(dw, dbias)
+    ld = _chk_tokens("embed_bwd", tok, lengths, T, B)
+    V = dw.shape[0]
+    if dw.dim() != 2 or dw.shape[1] != H or (dbias is not None and dbias.numel() != H):
+        raise ValueError("embed_bwd: dw %s / dbias do not fit H = %d" % (tuple(dw.shape), H))
+    lib = _l.load()
+    ws = _cached_ws(_embed_ws, (T, B, V, H, dz.device), lambda: max(int(lib.amdspeech_embed_bwd_workspace_bytes(T, B, V, H)), 16))
+    _l.check(lib.amdspeech_embed_bwd(_stream(), _p(tok), ld, _p(lengths), T, B, V, H, _p(dz), _p(dw), _p(dbias), _p(ws)), "embed_bwd")
+
+
+def xent_plan(T, B, C_):
+    """The row kernel xent_fwd_bwd takes for a shape (amdspeech.h: amdspeech_xent_plan), as a dict of ints with "kernel" as a name
+    ("wave", "block").  Read-only: nothing is launched.  A shape the call refuses raises here too."""
+    info = _l.XentPlanInfo()
+    _l.check(_l.load().amdspeech_xent_plan(int(T), int(B), int(C_), C.byref(info)), "xent_plan")
+    out = _plan_dict(info)
+    out["kernel"] = _l.XENT_KERNELS[out["kernel"]]
+    return out
+
+
+def xent_fwd_bwd(logits, targets, lengths, scale=1.0, nll=None, loss=None, dlogits=None, want_nll=False, want_grad=True):
+    """Softmax cross-entropy of logits [T,B,C] against targets int32 [B, >= T] (amdspeech.h: amdspeech_xent_fwd_bwd).  Returns
+    (loss [B], nll [T,B] or None, dlogits [T,B,C] or None); dlogits may be `logits` itself.  want_grad=False is the scoring call."""
+    T, B, C_ = _chk_f32_3d("xent_fwd_bwd", logits, "[T, B, C]")
+    _chk_f32(nll, loss, dlogits)
+    ld = _chk_tokens("xent_fwd_bwd", targets, lengths, T, B)
+    dev = logits.device
+    if loss is None:
+        loss = torch.empty(B, device=dev, dtype=torch.float32)
+    if nll is None and want_nll:
+        nll = torch.empty(T, B, device=dev, dtype=torch.float32)
+    if dlogits is None and want_grad:
+        dlogits = torch.empty_like(logits)
+    lib = _l.load()
+    ws = _cached_ws(_xent_ws, (T, B, C_, dev), lambda: max(int(lib.amdspeech_xent_workspace_bytes(T, B, C_)), 16))
+    _l.check(lib.amdspeech_xent_fwd_bwd(_stream(), _p(logits), _p(targets), ld, _p(lengths), T, B, C_, float(scale), _p(nll), _p(loss),
+                                        _p(dlogits), _p(ws)), "xent_fwd_bwd")
+    return loss, nll, dlogits

@@ -5,8 +5,13 @@ stt.py (argument parser :360-404, train loop + LR plateau rule :171-236, file / 
 --align AUDIO --transcript "text" prints when each word of a known transcript was spoken (forced CTC alignment), and
 --feature_stats writes the corpus statistics that `feature_norm : global` normalises with.
 
-Not kept (out of the hot-path scope): --train_language / --generate_text (the
-reference's language model is an unfinished stub), --record (pyaudio), --XLA (no tracing
+--train_language trains the character language model of the [lm_network_params] section (rnn_speech_amd.language_model: a
+next-token LSTM over the acoustic model's own label alphabet) on lm_text_files or, when that is empty, on the transcripts of the
+training and test corpora, with the loop shape of --train_acoustic; single process.  With lm_weight > 0, --evaluate and --file
+decode lm_nbest paths per utterance and return argmax(log p_ctc + lm_weight * log p_lm + lm_length_bonus * tokens); with
+lm_weight 0 (the default) nothing of the language model is loaded.
+
+Not kept (out of the hot-path scope): --generate_text, --record (pyaudio), --XLA (no tracing
 compiler here; accepted and ignored), TensorBoard.  `training_dataset_dirs` takes the reference's corpus
 trees (LibriSpeech / TED-LIUM / Shtooka / Vystadial, walked by rnn_speech_amd.corpus) or a `path<TAB>transcript`
 manifest.
@@ -70,6 +75,10 @@ def main():
         else:
             train_set = dataparallel.shard(train_set, grp.rank, grp.world)
         train_acoustic_rnn(train_set, test_set, hyper_params, prog_params)
+    elif prog_params["train_language"]:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            sys.exit("--train_language runs in one process: the language model is not trained data-parallel")
+        train_language_rnn(*load_language_dataset(speech_reco, hyper_params), hyper_params, prog_params)
     elif prog_params["file"] is not None:
         process_file(audio_processor, hyper_params, prog_params["file"])
     elif prog_params["evaluate"]:
@@ -306,6 +315,92 @@ def _forward_model(hyper_params, batch_size):
     model.create_forward_rnn()
     model.initialize(None)
     model.restore(None, hyper_params["checkpoint_dir"] + "/acoustic/")
+    model.rescorer = build_rescorer(hyper_params)
+    return model
+
+
+def _language_model(hyper_params, training):
+    from models.LanguageModel import LanguageModel
+    hp = hyper_params
+    model = LanguageModel(hp["lm_num_layers"], hp["lm_hidden_size"], hp["lm_batch_size"], hp["max_target_seq_length"],
+                          hp["max_target_seq_length"], hp["char_map_length"], precision=hp.get("precision", "f32"))
+    if training:
+        model.create_training_rnn(hp["lm_dropout"], hp["lm_dropout"], hp["lm_grad_clip"], hp["lm_learning_rate"], hp["lm_lr_decay_factor"])
+    else:
+        model.create_forward_rnn()
+    return model
+
+
+def build_rescorer(hyper_params):
+    """AcousticModel.rescorer from the lm_* keys: None at lm_weight 0 (the default: nothing is loaded, launched or allocated), else
+    the restored language model behind an n-best rescorer.  A missing checkpoint is an error that names the directory."""
+    if not hyper_params.get("lm_weight", 0) > 0:
+        return None
+    from rnn_speech_amd.language_model import NbestRescorer
+    model = _language_model(hyper_params, training=False)
+    model.restore(None, hyper_params["checkpoint_dir"], must_exist=True)
+    return NbestRescorer(model.score, hyper_params["lm_weight"], hyper_params.get("lm_nbest", 16), hyper_params.get("lm_length_bonus", 0.0))
+
+
+def load_language_dataset(speech_reco, hyper_params):
+    """(train sentences, test sentences): the lines of lm_text_files (the last tenth held out), or the transcripts of the training
+    and test corpora."""
+    clean = dataprocessor.DataProcessor.clean_label
+    files = hyper_params.get("lm_text_files") or []
+    if files:
+        lines = []
+        for path in files:
+            with open(path) as fh:
+                lines += [clean(l) for l in fh if l.strip()]
+        cut = max(1, len(lines) - len(lines) // 10)
+        return lines[:cut], lines[cut:]
+    train_set, test_set = speech_reco.load_acoustic_dataset(
+        hyper_params["training_dataset_dirs"], hyper_params["test_dataset_dirs"], hyper_params["training_filelist_cache"],
+        False, hyper_params["train_frac"])
+    return [item[1] for item in train_set], [item[1] for item in test_set]
+
+
+def train_language_rnn(train_set, test_set, hyper_params, prog_params):
+    """--train_language: the loop shape of train_acoustic_rnn -- windows of steps_per_checkpoint optimiser steps, checkpoint,
+    evaluation on the test sentences, plateau rule on the window's token error rate."""
+    from models.LanguageModel import LanguageModel
+    hp = hyper_params
+    if not train_set:
+        sys.exit("--train_language: no training sentence (lm_text_files / training_dataset_dirs)")
+    model = _language_model(hp, training=True)
+    model.restore(None, hp["checkpoint_dir"])
+    if prog_params["learn_rate"] is not None:
+        model.set_learning_rate(None, prog_params["learn_rate"])
+    ds_args = (hp["lm_batch_size"], hp["max_target_seq_length"], hp["char_map"])
+    test_dataset = LanguageModel.build_dataset(test_set, *ds_args) if test_set else []
+    model.add_dataset_input(LanguageModel.build_dataset(train_set, *ds_args))
+    schedule = PlateauSchedule()
+    epoch, epoch_limit, window = 0, prog_params["max_epoch"], hp["steps_per_checkpoint"]
+    while epoch_limit is None or epoch <= epoch_limit:
+        window_error = 0.0
+        for _ in range(window):
+            _loss, err, step, exhausted = model.run_train_step(None, 1)
+            window_error += err / window
+            if exhausted:
+                epoch += 1
+                logging.info("End of epoch number : %d", epoch)
+                if epoch_limit is not None and epoch > epoch_limit:
+                    break
+                shuffle(train_set)
+                model.add_dataset_input(LanguageModel.build_dataset(train_set, *ds_args))
+        model.save(None, hp["checkpoint_dir"])
+        if test_dataset:
+            loss, err = model.evaluate_dataset(test_dataset)
+            logging.info("Language model evaluation : loss %.5f nats per token (perplexity %.3f) - token error rate %.5f",
+                         loss, float(np.exp(min(loss, 50.0))), err)
+        if schedule.should_decay(window_error):
+            model.set_learning_rate(None, model.get_learning_rate() * hp["lm_lr_decay_factor"])
+            logging.info("Language model is not improving, decaying the learning rate")
+            if model.get_learning_rate() < 1e-7:
+                logging.info("Learning rate is too low, exiting")
+                return model
+            model.save(None, hp["checkpoint_dir"])
+    logging.info("Max number of epochs reached, exiting training session")
     return model
 
 
@@ -412,7 +507,7 @@ def feature_stats(train_set, hyper_params):
 
 
 _MODES = (("train_acoustic", "store_true", "train the acoustic model"),
-          ("train_language", "store_true", "reference stub -- not supported here"),
+          ("train_language", "store_true", "train the character language model ([lm_network_params]) that rescores n-best lists"),
           ("file", str, "transcribe one wav file"),
           ("record", "store_true", "live microphone mode -- not supported here"),
           ("evaluate", "store_true", "WER / CER of the restored model on the test manifest"),
