@@ -1032,6 +1032,62 @@ int amdspeech_xent_plan(int T, int B, int C, amdspeech_xent_plan_info* out);
 int amdspeech_xent_fwd_bwd(void* stream, const float* logits, const int* targets, int ld, const int* lengths, int T, int B,
                            int C, float scale, float* nll, float* loss, float* dlogits, void* ws);
 
+/* amdspeech_lm_step (lm_step.hip): ONE step of the language model for N hypotheses, each from its own parent state,
+ * gathered from a state pool -- what a beam search with the model inside it needs (amdspeech_ctc_beam_search_host_fused below).
+ * The pool is two f32 device arrays pool_h, pool_c of shape [n_slots][L][H] (amdspeech_lm_step_pool_bytes: the bytes of ONE of
+ * them, 0 for a bad shape).  parent / token / dest: device int32 [N].  Per row r, exactly f32 whatever precision trained the model:
+ *     x_0 = input_w[token[r]] + input_b                      (the bias alone for a token outside 0 .. V-1, as amdspeech_embed_fwd)
+ *     g = [x_l ; h_parent,l] . kernel_l + bias_l             (BasicLSTMCell: gates i, j, f, o; forget bias 1.0; no dropout)
+ *     c' = c_parent s(f + 1) + s(i) tanh(j),  h' = s(o) tanh(c'),  x_{l+1} = h'     -> slot dest[r], layer l
+ *     logq[r][:] = log_softmax(h'_top . output_w + output_b)  natural log, the row maximum subtracted; logq device [N][V]
+ * parent[r] == -1 is the zero state (the start of a sentence).  kernel_l = kernel_0 + l * kernel_stride ([2H][4H]), bias_l =
+ * bias_0 + l * bias_stride (floats), as the LSTM calls take them.
+ *   - dest entries must be distinct and no dest slot may also be a parent slot of the same call; the C call does NOT check this
+ *     (the indices are on the device).  An index outside its range touches nothing outside the buffers: a parent outside
+ *     -1 .. n_slots-1 reads the zero state, a row whose dest is outside 0 .. n_slots-1 is not written (its logq row neither).
+ *   - Slots not named in dest keep their bits.
+ *   - A row's h', c', logq depend on that row's parent state, token and the weights ONLY -- not on N, the row's position or the
+ *     other rows, bit for bit: every instantiation contracts k in the same fixed order and there are no atomics.
+ *   - L + 1 plain launches (one per layer, one for the output layer and log-softmax); no workgroup waits for another one.  The gate
+ *     pre-activations stay on the chip, the parent rows are gathered through the index while the operands are loaded.
+ *   - H a multiple of 16 in 16 .. 4096, 2 <= V <= 256, 1 <= L <= 8, 1 <= N < 2^24, n_slots >= 1 with n_slots * L * H < 2^31;
+ *     pointers 16-byte aligned, kernel_stride / bias_stride multiples of 4 floats: otherwise AMDSPEECH_EINVAL (a bad argument) or
+ *     AMDSPEECH_EUNSUPPORTED (a size limit of the kernels) with a message that names the limit, and nothing is launched.
+ * amdspeech_lm_step_plan: the instantiation and launch geometry of a shape, a READ-ONLY view of the plan the launch itself reads;
+ *   no device is needed.  n_min .. n_max is the range of N that takes the very same instantiation (row_tile = 16 or 32 rows per
+ *   workgroup).                                                                                                                   */
+#define AMDSPEECH_LM_STEP_KERNEL_MFMA16 0 /* v_mfma_f32_16x16x4_f32, the rows on the A port, k split over the four waves of a workgroup */
+typedef struct amdspeech_lm_step_plan_info {
+    int kernel, row_tile, threads, launches, n_min, n_max, col_tiles, row_tiles, lds_bytes, out_row_tile, out_row_tiles, v_max;
+} amdspeech_lm_step_plan_info;
+int amdspeech_lm_step(void* stream, int N, const int* parent, const int* token, const int* dest,
+                      float* pool_h, float* pool_c, int n_slots, int L, int H, int V,
+                      const float* input_w, const float* input_b, const float* kernel_0, long kernel_stride,
+                      const float* bias_0, long bias_stride, const float* output_w, const float* output_b,
+                      float* logq);
+int amdspeech_lm_step_plan(int N, int L, int H, int V, amdspeech_lm_step_plan_info* out);
+size_t amdspeech_lm_step_pool_bytes(int n_slots, int L, int H);
+
+/* The prefix beam search of amdspeech_ctc_beam_search_host_nbest with the language model INSIDE the beam (first-pass fusion).
+ * HOST pointers.  `step` advances the model: for n new hypotheses it gets parent[k] (a state slot, -1 = the start of a sentence),
+ * token[k] and dest[k] (the slot that receives the new state) and fills logq [n][C], the model's natural-log next-token
+ * distribution after that token; a non-zero return ends the search with that status and no further callback.  `step` is only
+ * ever called on the calling thread, once per frame for ALL utterances of the mini-batch (at most T + 1 calls), the first one
+ * being the root alone (parent -1, token C-1 -> dest root).  Within a call the dest slots are distinct and none is a parent.
+ * Slots: utterance b owns 2 * beam_width of them and the last one is the shared root: amdspeech_ctc_beam_search_fused_slots.
+ * Scoring: the extension of a beam entry by the non-blank label c adds lm_weight * q[c] + lm_length_bonus to the acoustic
+ * from + lp[c], q being the model's row for the entry's prefix AS THE TRIE HOLDS IT -- before merge_repeated: "b b" is scored as
+ * the model sees "b b" --, also where that extension merges into a beam child; blank and repeat transitions add nothing; after
+ * the last frame an entry's score is tot + lm_weight * q[C-1] (the closing EOS).  Candidates are selected exhaustively.  The
+ * outputs are those of the n-best call in (final score descending, lexicographic) order, log_prob the final score; n_best == 0
+ * means one path: ids [B][T], out_len [B], log_prob [B] (may be NULL), n_found unused.                                        */
+typedef int (*amdspeech_lm_step_fn)(void* user, int n, const int* parent, const int* token, const int* dest, float* logq);
+int amdspeech_ctc_beam_search_fused_slots(int B, int beam_width);
+int amdspeech_ctc_beam_search_host_fused(const float* logits, const int* lengths, int T, int B, int C, int beam_width,
+                                         int merge_repeated, int n_best, float lm_weight, float lm_length_bonus,
+                                         amdspeech_lm_step_fn step, void* user, int* ids, int* out_len, float* log_prob,
+                                         int* n_found, int max_threads);
+
 #ifdef __cplusplus
 }
 #endif

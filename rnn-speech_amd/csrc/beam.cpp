@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <condition_variable>
 #include <cstdlib>
 #if defined(__x86_64__)
 #include <immintrin.h>      // (the AVX2 rank sort below; other hosts keep std::sort)
@@ -20,6 +21,7 @@
 #include <exception>
 #include <thread>
 #include <limits>
+#include <mutex>
 #include <vector>
 
 #include "common.h"
@@ -104,6 +106,17 @@ struct Decoder {
     std::vector<uint64_t> keys;
     std::vector<uint64_t> keys2;
     std::vector<int64_t> keys_tmp;
+    // Language model inside the beam (amdspeech_ctc_beam_search_host_fused; all empty / unused in the acoustic-only calls):
+    // q[i] is the model's log-probability row [C] for the prefix of beam slot i AS THE TRIE HOLDS IT (before merge_repeated), and
+    // the extension of i by c adds lm_w * q[i][c] + lm_bonus.  A prefix's state lives in one of the utterance's 2 * width slots
+    // while the prefix is in the beam (lm_slot: node -> slot, LM_NONE without a state, LM_ROOT the shared root slot).
+    enum { LM_NONE = -1, LM_ROOT = -2 };
+    bool fused = false;
+    float lm_w = 0.0f, lm_bonus = 0.0f;
+    std::vector<const float*> q;                      // beam slot -> its row (empty: no language model)
+    std::vector<int> lm_slot;                         // node -> state slot of the utterance
+    std::vector<int> free_slots;
+    std::vector<float> qbuf;                          // [2 * width][C]: the row of every state slot
     void sort_keys() {                                // keys ascending (unique: the index is in the low half)
         const int n = (int)keys.size();
 #if defined(__x86_64__)
@@ -164,6 +177,23 @@ struct Decoder {
     void reserve_for(int frames) {                    // at most `width` new prefixes per frame
         const size_t n = (size_t)frames * width + 1;
         arena.reserve(n); depth.reserve(n); slot_of.reserve(n);
+        if (fused) lm_slot.reserve(n);
+    }
+    void reset_fused(int C_, int width_, float w, float bonus, const float* root_q) {
+        reset(C_, width_, true);                      // (the bounded frontier rests on rank-one scores: not valid with the model's term)
+        fused = true; lm_w = w; lm_bonus = bonus;
+        lm_slot.assign(1, LM_ROOT);
+        q.assign(1, root_q);
+        free_slots.resize(2 * (size_t)width_);
+        for (int k = 0; k < 2 * width_; ++k) free_slots[k] = 2 * width_ - 1 - k;
+        qbuf.resize((size_t)2 * width_ * C_);
+    }
+    // from + lp[c], plus the model's term for the extension of slot i by c where there is a model
+    float ext_score(float from, int i, int c) const {
+#pragma clang fp contract(off)
+        float s2 = from + lp[c];
+        if (!q.empty()) s2 += lm_w * q[i][c] + lm_bonus;
+        return s2;
     }
 
     float from_of(int i, int c) const { return c == arena[node[i]].label ? sc[i].pb : tot[i]; }
@@ -175,7 +205,7 @@ struct Decoder {
             for (int c = 0; c < C; ++c) {
                 if (c == blank) continue;
                 const float from = from_of(i, c);                                   // a repeat starts a NEW character only after a blank
-                if (from != NEG) e[c] = from + lp[c];
+                if (from != NEG) e[c] = ext_score(from, i, c);
             }
             for (int j = kid_head[i]; j >= 0; j = kid_next[j]) e[arena[node[j]].label] = NEG;      // the same prefix as a beam entry: merged there
         }
@@ -366,7 +396,7 @@ struct Decoder {
             for (int j = kid_head[i]; j >= 0; j = kid_next[j]) {                    // the same prefix as a beam entry: merge there
                 const int c = arena[node[j]].label;
                 const float from = from_of(i, c);
-                if (from != NEG) stay[j].pnb = lse2(stay[j].pnb, from + lp[c]);
+                if (from != NEG) stay[j].pnb = lse2(stay[j].pnb, ext_score(from, i, c));
             }
         }
         if (exhaustive) select_exhaustive(nb); else select_frontier(nb);
@@ -393,6 +423,7 @@ struct Decoder {
                     arena[par].first_child = id;
                     depth.push_back(depth[par] + 1);
                     slot_of.push_back(-1);
+                    if (fused) lm_slot.push_back(LM_NONE);
                 }
                 new_node[k] = id;
                 new_sc[k].pnb = cd.score;
@@ -540,6 +571,227 @@ static int beam_search_host(const float* logits, const int* lengths, int T, int 
         }
     } catch (const std::exception& e) {       // (no C++ exception crosses the C ABI)
         set_error("ctc_beam_search_host: %s", e.what());
+        return AMDSPEECH_EINVAL;
+    }
+    return AMDSPEECH_OK;
+}
+
+// ---- the language model inside the beam (first-pass fusion; amdspeech.h: amdspeech_ctc_beam_search_host_fused) ----
+// Lockstep over the mini-batch: frame t of every utterance runs on the worker threads, then THIS thread gathers the entries that
+// entered a beam without a model state -- over all utterances --, makes one `step` call for them and hands the rows out.  The
+// callback therefore runs on the calling thread only (a ctypes callback is safe) and at most T + 1 times.
+//
+// Slots.  Utterance b owns the slots b * 2 * width .. + 2 * width - 1, the last slot of all is the root's (parent -1, token C-1:
+// evaluated once per call, shared).  An entry takes a free slot of its utterance when it enters the beam and gives it back when it
+// leaves -- AFTER that frame's step call, because the frame's new entries were selected against it and read its state.  At most
+// `width` entries hold a state when a frame starts and at most `width` enter: 2 * width slots are enough, whatever T.  A prefix that
+// left the beam and comes back is stepped again from its parent, which is in the beam (the trie argument above: a candidate is
+// the extension of a beam entry); the step is bit-for-bit row independent, so it gets the same row again.
+extern "C" int amdspeech_ctc_beam_search_fused_slots(int B, int beam_width) {
+    if (B <= 0 || beam_width <= 0 || (long)B * 2 * beam_width + 1 > 0x7fffffffL) {
+        amdspeech::set_error("ctc_beam_search_fused_slots: B = %d and beam_width = %d must be positive with 2 * B * beam_width + 1 below 2^31",
+                             B, beam_width);
+        return 0;
+    }
+    return B * 2 * beam_width + 1;
+}
+
+namespace {
+
+// `job(b)` for b = 0 .. B-1 on a fixed set of threads, again and again (one round per frame), the caller waiting for each round.
+struct RoundPool {
+    std::mutex mu;
+    std::condition_variable go, done;
+    std::vector<std::thread> threads;
+    std::atomic<int> next{0};
+    std::atomic<bool> failed{false};
+    int round = 0, pending = 0, B = 0;
+    bool quit = false;
+    void (*job)(void*, int) = nullptr;
+    void* ctx = nullptr;
+
+    void start(int n, int B_, void (*job_)(void*, int), void* ctx_) {
+        B = B_; job = job_; ctx = ctx_;
+        for (int w = 0; w < n; ++w) threads.emplace_back([this] { work(); });
+    }
+    void work() {
+        int seen = 0;
+        for (;;) {
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                go.wait(lk, [&] { return quit || round != seen; });
+                if (quit) return;
+                seen = round;
+            }
+            try {
+                for (int b = next++; b < B; b = next++) job(ctx, b);
+            } catch (...) { failed = true; }
+            std::lock_guard<std::mutex> lk(mu);
+            if (--pending == 0) done.notify_one();
+        }
+    }
+    void run_round() {
+        if (threads.empty()) {
+            for (int b = 0; b < B; ++b) job(ctx, b);
+            return;
+        }
+        std::unique_lock<std::mutex> lk(mu);
+        next = 0;
+        pending = (int)threads.size();
+        ++round;
+        go.notify_all();
+        done.wait(lk, [&] { return pending == 0; });
+    }
+    ~RoundPool() {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            quit = true;
+        }
+        go.notify_all();
+        for (auto& th : threads) th.join();
+    }
+};
+
+struct FusedCtx {
+    const float* logits;
+    const int* lengths;
+    int T, B, C, t;
+    std::vector<Decoder>* dec;
+};
+
+void fused_frame_job(void* p, int b) {
+    FusedCtx& c = *static_cast<FusedCtx*>(p);
+    const int Tb = std::min(std::max(c.lengths[b], 0), c.T);
+    if (c.t < Tb) (*c.dec)[b].frame(c.logits + ((size_t)c.t * c.B + b) * c.C);
+}
+
+}  // namespace
+
+extern "C" int amdspeech_ctc_beam_search_host_fused(const float* logits, const int* lengths, int T, int B, int C, int beam_width,
+                                                    int merge_repeated, int n_best, float lm_weight, float lm_length_bonus,
+                                                    amdspeech_lm_step_fn step, void* user, int* ids, int* out_len, float* log_prob,
+                                                    int* n_found, int max_threads) {
+    using amdspeech::set_error;
+    if (!logits || !lengths || !ids || !out_len || !step || T <= 0 || B <= 0 || C <= 1 || beam_width <= 0 || n_best < 0 ||
+        (n_best > 0 && !log_prob)) {
+        set_error("ctc_beam_search_host_fused: bad arguments");
+        return AMDSPEECH_EINVAL;
+    }
+    if (amdspeech_ctc_beam_search_fused_slots(B, beam_width) == 0) return AMDSPEECH_EINVAL;
+    const int per_utt = 2 * beam_width, root_slot = B * per_utt;
+    try {
+        // the root: the model's row after the start symbol, once for the whole call
+        std::vector<float> root_q((size_t)C);
+        std::vector<int> s_parent(1, -1), s_token(1, C - 1), s_dest(1, root_slot), s_owner;
+        std::vector<float> s_logq;
+        if (int rc = step(user, 1, s_parent.data(), s_token.data(), s_dest.data(), root_q.data())) {
+            set_error("ctc_beam_search_host_fused: the step callback returned %d", rc);
+            return rc;
+        }
+        int Tmax = 0;
+        for (int b = 0; b < B; ++b) Tmax = std::max(Tmax, std::min(std::max(lengths[b], 0), T));
+        std::vector<Decoder> dec((size_t)B);
+        for (int b = 0; b < B; ++b) {
+            dec[b].reset_fused(C, beam_width, lm_weight, lm_length_bonus, root_q.data());
+            dec[b].reserve_for(std::min(std::max(lengths[b], 0), T));
+        }
+        FusedCtx ctx{logits, lengths, T, B, C, 0, &dec};
+        const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+        int nthreads = (int)std::min<unsigned>((unsigned)B, std::min(hw, 64u));
+        if (max_threads > 0) nthreads = std::min(nthreads, max_threads);
+        RoundPool pool;
+        pool.start(nthreads <= 1 ? 0 : nthreads, B, fused_frame_job, &ctx);
+        for (int t = 0; t < Tmax; ++t) {
+            ctx.t = t;
+            pool.run_round();
+            if (pool.failed) { set_error("ctc_beam_search_host_fused: out of memory in a decode thread"); return AMDSPEECH_EINVAL; }
+            // the entries that entered a beam without a state, over all utterances: one call
+            s_parent.clear(); s_token.clear(); s_dest.clear(); s_owner.clear();
+            for (int b = 0; b < B; ++b) {
+                if (t >= std::min(std::max(lengths[b], 0), T)) continue;
+                Decoder& d = dec[b];
+                for (size_t k = 0; k < d.node.size(); ++k) {
+                    const int n = d.node[k];
+                    if (d.lm_slot[n] != Decoder::LM_NONE) continue;
+                    const int ps = d.lm_slot[d.arena[n].parent];              // (in the beam this frame was selected from: it has a state)
+                    const int local = d.free_slots.back();
+                    d.free_slots.pop_back();
+                    d.lm_slot[n] = local;
+                    s_parent.push_back(ps == Decoder::LM_ROOT ? root_slot : b * per_utt + ps);
+                    s_token.push_back(d.arena[n].label);
+                    s_dest.push_back(b * per_utt + local);
+                    s_owner.push_back(b);
+                }
+            }
+            const int n_new = (int)s_dest.size();
+            if (n_new > 0) {
+                s_logq.resize((size_t)n_new * C);
+                if (int rc = step(user, n_new, s_parent.data(), s_token.data(), s_dest.data(), s_logq.data())) {
+                    set_error("ctc_beam_search_host_fused: the step callback returned %d", rc);
+                    return rc;
+                }
+                for (int r = 0; r < n_new; ++r) {
+                    Decoder& d = dec[s_owner[r]];
+                    memcpy(d.qbuf.data() + (size_t)(s_dest[r] - s_owner[r] * per_utt) * C, s_logq.data() + (size_t)r * C, (size_t)C * sizeof(float));
+                }
+            }
+            for (int b = 0; b < B; ++b) {
+                if (t >= std::min(std::max(lengths[b], 0), T)) continue;
+                Decoder& d = dec[b];
+                for (int n : d.new_node)                                       // (after frame(): the beam the frame started from)
+                    if (d.slot_of[n] < 0 && d.lm_slot[n] >= 0) { d.free_slots.push_back(d.lm_slot[n]); d.lm_slot[n] = Decoder::LM_NONE; }
+                d.q.resize(d.node.size());
+                for (size_t k = 0; k < d.node.size(); ++k) {
+                    const int sl = d.lm_slot[d.node[k]];
+                    d.q[k] = sl == Decoder::LM_ROOT ? root_q.data() : d.qbuf.data() + (size_t)sl * C;
+                }
+            }
+        }
+        // final scores: the closing EOS; (score descending, lexicographic)
+        std::vector<float> fin;
+        std::vector<int> slots, path;
+        for (int b = 0; b < B; ++b) {
+            Decoder& d = dec[b];
+            const int nb = (int)d.node.size();
+            fin.resize(nb);
+            for (int k = 0; k < nb; ++k) fin[k] = d.tot[k] + lm_weight * d.q[k][C - 1];
+            slots.resize(nb);
+            for (int k = 0; k < nb; ++k) slots[k] = k;
+            std::sort(slots.begin(), slots.end(), [&](int u, int v) {
+                if (fin[u] != fin[v]) return fin[u] > fin[v];
+                return d.lex_less(d.node[u], -1, d.node[v], -1);
+            });
+            auto write_path = [&](int k, int* row, int* len_out) {
+                d.prefix_of(d.node[slots[k]], -1, path);
+                int n = 0;
+                for (size_t i = 0; i < path.size(); ++i) {
+                    if (merge_repeated && i > 0 && path[i] == path[i - 1]) continue;
+                    row[n++] = path[i];
+                }
+                for (int i = n; i < T; ++i) row[i] = C;
+                *len_out = n;
+            };
+            if (n_best == 0) {
+                write_path(0, ids + (size_t)b * T, out_len + b);
+                if (log_prob) log_prob[b] = fin[slots[0]];
+                continue;
+            }
+            const int found = std::min(nb, n_best);
+            for (int k = 0; k < n_best; ++k) {
+                const size_t e = (size_t)b * n_best + k;
+                if (k < found) {
+                    write_path(k, ids + e * T, out_len + e);
+                    log_prob[e] = fin[slots[k]];
+                } else {
+                    for (int i = 0; i < T; ++i) ids[e * T + i] = C;
+                    out_len[e] = 0;
+                    log_prob[e] = NEG;
+                }
+            }
+            if (n_found) n_found[b] = found;
+        }
+    } catch (const std::exception& e) {       // (no C++ exception crosses the C ABI)
+        set_error("ctc_beam_search_host_fused: %s", e.what());
         return AMDSPEECH_EINVAL;
     }
     return AMDSPEECH_OK;

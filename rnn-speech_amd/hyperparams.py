@@ -103,6 +103,7 @@ def read_config_file(config_file):
 
 
 _LM = "lm_network_params"
+LM_FUSION_MODES = ("rescore", "beam")
 
 
 def read_lm_keys(get):
@@ -110,7 +111,9 @@ def read_lm_keys(get):
     hidden_size, dropout (the keep probability of both DropoutWrapper sides), batch_size, learning_rate, lr_decay_factor, grad_clip,
     defaulting to the values of this build's config.ini -- under lm_* names, plus this build's keys: lm_text_files (comma-separated text files,
     one sentence per line; empty: the transcripts of the training and test corpora), lm_weight (0, the default: no rescoring,
-    nothing of the language model is loaded), lm_nbest and lm_length_bonus.  None is structural for the acoustic checkpoint.
+    nothing of the language model is loaded), lm_nbest, lm_length_bonus and lm_fusion (rescore, the default: the model picks among
+    the lm_nbest paths of the acoustic beam; beam: the model scores every extension inside the beam).  None is structural for the
+    acoustic checkpoint.
     get(key, default) -> text; a bad value raises ValueError naming its key."""
     def number(key, dflt, kind, lo, hi):
         text = get(key, dflt)
@@ -128,6 +131,9 @@ def read_lm_keys(get):
     d["lm_weight"] = number("lm_weight", "0", float, 0.0, 1e3)
     d["lm_nbest"] = number("lm_nbest", "16", int, 1, 1000)
     d["lm_length_bonus"] = number("lm_length_bonus", "0", float, -1e3, 1e3)
+    d["lm_fusion"] = (get("lm_fusion", "rescore") or "rescore").strip().lower()
+    if d["lm_fusion"] not in LM_FUSION_MODES:
+        raise ValueError("lm_fusion : %r is not one of %s" % (d["lm_fusion"], " | ".join(LM_FUSION_MODES)))
     return d
 
 

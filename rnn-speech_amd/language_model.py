@@ -1,4 +1,4 @@
-"""Character language model over the acoustic model's label alphabet: GPU training and n-best rescoring.
+"""Character language model over the acoustic model's label alphabet: GPU training, n-best rescoring and first-pass fusion.
 
 Stands where the reference's models/LanguageModel.py stands ("acoustic RNN -> character level RNN-LM") and keeps its class
 surface where that means something here.  Next-token model, V = C = len(char_map): a sentence with tokens y_0 .. y_{n-1} is one
@@ -471,4 +471,110 @@ class NbestRescorer(object):
     def __call__(self, logits, lengths, beam_width=100, merge_repeated=True):
         nbest = ops.ctc_beam_search_nbest(logits, lengths, self.lm_nbest, beam_width, merge_repeated)
         ids, out_len, _ = rescore_nbest(*nbest, scorer=self.scorer, lm_weight=self.lm_weight, lm_length_bonus=self.lm_length_bonus)
+        return ids, out_len
+
+
+# ---- the language model inside the beam (first-pass fusion) -----------------------------------------
+class LmStepper(object):
+    """The `step` of ops.ctc_beam_search_fused on the GPU: a pool of n_slots model states (two float32 device arrays [n_slots, L,
+    H]) and one ops.lm_step per call.  engine_or_params: an LmEngine (its float32 master parameters are used in place, whatever
+    precision it trains in) or a dict of numpy arrays under the ParamLayout(L, H, V, V) names.
+    __call__(parent, token, dest) -> logq float32 [n, V] on the host: the indices go up through one pinned buffer, then one
+    amdspeech_lm_step, one device-to-host copy and one stream synchronisation.  The slot contract of amdspeech_lm_step is checked
+    here, on the host copies: dest distinct and inside the pool, no dest among the parents, parents -1 or inside the pool."""
+
+    def __init__(self, engine_or_params, n_slots, max_rows=None, device="cuda"):
+        if isinstance(engine_or_params, dict):
+            arrays = engine_or_params
+            V, H = np.shape(arrays["input_w"])
+            L = sum(1 for k in arrays if k.startswith("kernel_"))
+            self.layout = ParamLayout(L, H, V, V)
+            self.device = torch.device(device)
+            self.params = torch.zeros(self.layout.total, device=self.device)
+            for name, a in arrays.items():
+                self.layout.view(self.params, name).copy_(torch.as_tensor(np.asarray(a), dtype=torch.float32))
+        else:
+            eng = engine_or_params
+            self.layout, self.params, self.device = eng.layout, eng.params, eng.device
+            L, H, V = eng.L, eng.H, eng.V
+        self.L, self.H, self.V, self.n_slots = int(L), int(H), int(V), int(n_slots)
+        ops.lm_step_plan(1, self.L, self.H, self.V)                      # a shape the kernels refuse raises here, not in the beam
+        self.pool_h = torch.zeros(self.n_slots, self.L, self.H, device=self.device)
+        self.pool_c = torch.zeros_like(self.pool_h)
+        self._cap = 0
+        self._reserve(int(max_rows or min(self.n_slots, 4096)))
+        self.calls, self.rows, self.seconds = 0, 0, 0.0                  # what tools/lm_fusion_bench.py reports
+
+    def _reserve(self, rows):
+        if rows <= self._cap:
+            return
+        self._cap = rows
+        self._idx_host = torch.empty(3 * rows, dtype=torch.int32).pin_memory()
+        self._idx_dev = torch.empty(3 * rows, dtype=torch.int32, device=self.device)
+        self._logq_dev = torch.empty(rows, self.V, device=self.device)
+        self._logq_host = torch.empty(rows, self.V).pin_memory()
+
+    def _p(self, name):
+        return self.layout.view(self.params, name)
+
+    def check_slots(self, parent, dest):
+        n_slots = self.n_slots
+        if dest.size and (dest.min() < 0 or dest.max() >= n_slots):
+            raise ValueError("lm step: a dest slot is outside 0 .. %d" % (n_slots - 1))
+        if parent.size and (parent.min() < -1 or parent.max() >= n_slots):
+            raise ValueError("lm step: a parent slot is outside -1 .. %d" % (n_slots - 1))
+        if np.unique(dest).size != dest.size:
+            raise ValueError("lm step: two rows write the same dest slot")
+        if np.intersect1d(dest, parent).size:
+            raise ValueError("lm step: a dest slot is also a parent slot of the same call")
+
+    def __call__(self, parent, token, dest):
+        import time
+        t0 = time.perf_counter()
+        parent, token, dest = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (parent, token, dest))
+        n = parent.size
+        if n == 0 or token.size != n or dest.size != n:
+            raise ValueError("lm step: parent, token and dest must hold the same positive number of rows")
+        self.check_slots(parent, dest)
+        self._reserve(n)
+        host = self._idx_host.numpy()
+        host[:n], host[n:2 * n], host[2 * n:3 * n] = parent, token, dest
+        idx = self._idx_dev[:3 * n]
+        idx.copy_(self._idx_host[:3 * n], non_blocking=True)
+        lay = self.layout
+        ops.lm_step(idx[:n], idx[n:2 * n], idx[2 * n:], self.pool_h, self.pool_c, self._p("input_w"), self._p("input_b"),
+                    self._p("kernel_0"), lay.kernel_stride, self._p("bias_0"), lay.bias_stride, self._p("output_w"), self._p("output_b"),
+                    logq=self._logq_dev)
+        self._logq_host[:n].copy_(self._logq_dev[:n], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        out = self._logq_host[:n].numpy().copy()
+        self.calls += 1
+        self.rows += n
+        self.seconds += time.perf_counter() - t0
+        return out
+
+
+class FusedDecoder(object):
+    """What AcousticModel.rescorer holds at lm_fusion : beam: NbestRescorer's call signature, the language model INSIDE the beam
+    (ops.ctc_beam_search_fused over an LmStepper).  The model scores the prefix as decoded, before merge_repeated.  model: a
+    LanguageModel, an LmEngine or a parameter dict.  The stepper (state pool and staging) is made at the first call and kept while
+    the mini-batch size and the beam width stay the same."""
+
+    def __init__(self, model, lm_weight, beam_width=100, lm_length_bonus=0.0, max_threads=0):
+        self.source = getattr(model, "engine", model)
+        self.lm_weight, self.beam_width, self.lm_length_bonus = float(lm_weight), int(beam_width), float(lm_length_bonus)
+        self.max_threads = int(max_threads)
+        self.stepper = None
+
+    def _stepper(self, B, beam_width):
+        n_slots = ops.ctc_beam_search_fused_slots(B, beam_width)
+        if self.stepper is None or self.stepper.n_slots != n_slots:
+            self.stepper = LmStepper(self.source, n_slots, max_rows=B * beam_width + 1)
+        return self.stepper
+
+    def __call__(self, logits, lengths, beam_width=None, merge_repeated=True):
+        width = self.beam_width if beam_width is None else int(beam_width)
+        B = logits.shape[1]
+        ids, out_len, _ = ops.ctc_beam_search_fused(logits, lengths, self._stepper(B, width), 0, width, merge_repeated, self.lm_weight,
+                                                    self.lm_length_bonus, max_threads=self.max_threads)
         return ids, out_len

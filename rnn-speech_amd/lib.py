@@ -20,6 +20,7 @@ class DataflowTimeout(AmdSpeechError):
 
 
 ETIMEOUT = -4                     # include/amdspeech.h
+ECALLBACK = -100                  # ops.ctc_beam_search_fused: the status its trampoline returns when `step` raised
 
 
 class LstmDesc(C.Structure):
@@ -91,12 +92,21 @@ class XentPlanInfo(C.Structure):     # amdspeech_xent_plan_info (include/amdspee
                                        "loss_grid")]
 
 
+class LmStepPlanInfo(C.Structure):     # amdspeech_lm_step_plan_info (include/amdspeech.h): the instantiation and launch geometry of a language-model step, read-only
+    _fields_ = [(n, C.c_int) for n in ("kernel", "row_tile", "threads", "launches", "n_min", "n_max", "col_tiles", "row_tiles", "lds_bytes",
+                                       "out_row_tile", "out_row_tiles", "v_max")]
+
+
+# amdspeech_lm_step_fn (include/amdspeech.h): (user, n, parent, token, dest, logq) -> status, called on the thread that called the decoder
+LM_STEP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float))
+
 GEMM_FAMILIES = ("skinny_n", "skinny_k", "skinny_tn", "tn_direct", "kc_direct", "lds", "bf3", "bf16p")      # AMDSPEECH_GEMM_* (include/amdspeech.h)
 GEMM_MAP_LINEAR, GEMM_MAP_XCD, GEMM_MAP_XCD_BLOCKS, GEMM_MAP_KC_BAND = range(4)      # AMDSPEECH_GEMM_MAP_*
 GEMM_GROUP_MAX = 10                                                                 # AMDSPEECH_GEMM_GROUP_MAX
 CTC_KERNELS = ("wave", "shift", "pair", "edge")      # AMDSPEECH_CTC_KERNEL_* (include/amdspeech.h)
 LSTM_PATHS = ("flow", "big1", "big", "hoist", "diag", "diag_bf3")      # AMDSPEECH_LSTM_PATH_* (include/amdspeech.h)
 XENT_KERNELS = ("wave", "block")      # AMDSPEECH_XENT_KERNEL_* (include/amdspeech.h)
+LM_STEP_KERNELS = ("mfma16",)      # AMDSPEECH_LM_STEP_KERNEL_* (include/amdspeech.h)
 FEATURE_NORM_MODES = ("none", "utterance", "global")      # AMDSPEECH_FEATURE_NORM_* (include/amdspeech.h)
 LSTM_ARMED, LSTM_ARM_NEXT, LSTM_SAME_WS, LSTM_PER_DIAGONAL, LSTM_INJECT_TIMEOUT = 1, 2, 4, 8, 16      # amdspeech_lstm_desc.flags (include/amdspeech.h)
 
@@ -233,6 +243,11 @@ PROTOTYPES = {
     "amdspeech_xent_workspace_bytes": (_SZ, [_I, _I, _I]),
     "amdspeech_xent_plan": (_I, [_I, _I, _I, C.POINTER(XentPlanInfo)]),
     "amdspeech_xent_fwd_bwd": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P]),
+    "amdspeech_lm_step": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _L, _P, _P, _P]),
+    "amdspeech_lm_step_plan": (_I, [_I, _I, _I, _I, C.POINTER(LmStepPlanInfo)]),
+    "amdspeech_lm_step_pool_bytes": (_SZ, [_I, _I, _I]),
+    "amdspeech_ctc_beam_search_fused_slots": (_I, [_I, _I]),
+    "amdspeech_ctc_beam_search_host_fused": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, LM_STEP_FN, _P, _P, _P, _P, _P, _I]),
 }
 
 _lib = None

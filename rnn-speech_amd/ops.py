@@ -1351,3 +1351,96 @@ def xent_fwd_bwd(logits, targets, lengths, scale=1.0, nll=None, loss=None, dlogi
     _l.check(lib.amdspeech_xent_fwd_bwd(_stream(), _p(logits), _p(targets), ld, _p(lengths), T, B, C_, float(scale), _p(nll), _p(loss),
                                         _p(dlogits), _p(ws)), "xent_fwd_bwd")
     return loss, nll, dlogits
+
+
+def lm_step_plan(N, L, H, V):
+    """The instantiation lm_step takes for a shape (amdspeech.h: amdspeech_lm_step_plan), as a dict of ints with "kernel" as a
+    name; n_min .. n_max is the range of N on the same instantiation.  Read-only, no device needed; a refused shape raises."""
+    info = _l.LmStepPlanInfo()
+    _l.check(_l.load().amdspeech_lm_step_plan(int(N), int(L), int(H), int(V), C.byref(info)), "lm_step_plan")
+    out = _plan_dict(info)
+    out["kernel"] = _l.LM_STEP_KERNELS[out["kernel"]]
+    return out
+
+
+def lm_step(parent, token, dest, pool_h, pool_c, input_w, input_b, kernel_0, kernel_stride, bias_0, bias_stride, output_w, output_b,
+            logq=None):
+    """One language-model step for N hypotheses (amdspeech.h: amdspeech_lm_step): parent / token / dest int32 device [N], the state
+    pool pool_h / pool_c float32 device [n_slots, L, H] (written in place at the dest slots), the parameters as ParamLayout(L, H, V,
+    V) views.  Returns logq [N, V], the natural-log next-token distribution of every row.  The slot contract (dest distinct, no dest
+    among the parents) is the caller's: language_model.LmStepper checks it on its host copies."""
+    _chk_i32(parent, token, dest)
+    _chk_f32(pool_h, pool_c, input_w, input_b, kernel_0, bias_0, output_w, output_b, logq)
+    N = parent.numel()
+    if token.numel() != N or dest.numel() != N:
+        raise ValueError("lm_step: parent, token and dest must have one entry per row")
+    if pool_h.dim() != 3 or pool_h.shape != pool_c.shape:
+        raise ValueError("lm_step: pool_h / pool_c must be [n_slots, L, H], got %s / %s" % (tuple(pool_h.shape), tuple(pool_c.shape)))
+    n_slots, L, H = pool_h.shape
+    V = output_b.numel()
+    if tuple(input_w.shape) != (V, H) or input_b.numel() != H or tuple(output_w.shape) != (H, V) or tuple(kernel_0.shape) != (2 * H, 4 * H) \
+            or bias_0.numel() != 4 * H:
+        raise ValueError("lm_step: the parameters do not fit L = %d, H = %d, V = %d" % (L, H, V))
+    if logq is None:
+        logq = torch.empty(N, V, device=pool_h.device, dtype=torch.float32)
+    elif logq.numel() < N * V:
+        raise ValueError("lm_step: logq holds %d values, %d rows of %d need %d" % (logq.numel(), N, V, N * V))
+    _l.check(_l.load().amdspeech_lm_step(_stream(), N, _p(parent), _p(token), _p(dest), _p(pool_h), _p(pool_c), n_slots, L, H, V,
+                                         _p(input_w), _p(input_b), _p(kernel_0), int(kernel_stride or 0), _p(bias_0), int(bias_stride or 0),
+                                         _p(output_w), _p(output_b), _p(logq)), "lm_step")
+    return logq
+
+
+def ctc_beam_search_fused_slots(B, beam_width):
+    """State slots ctc_beam_search_fused hands to its `step`: 2 * beam_width per utterance and the root's (the last one)."""
+    n = int(_l.load().amdspeech_ctc_beam_search_fused_slots(int(B), int(beam_width)))
+    if n <= 0:
+        _l.check(-1, "ctc_beam_search_fused_slots")
+    return n
+
+
+def ctc_beam_search_fused(logits, lengths, step, n_best=0, beam_width=100, merge_repeated=True, lm_weight=1.0, lm_length_bonus=0.0,
+                          max_threads=0):
+    """Host prefix beam search with a language model INSIDE the beam (amdspeech.h: amdspeech_ctc_beam_search_host_fused).
+    step(parent, token, dest) -> logq [n, C]: numpy int32 arrays of the n hypotheses to advance (parent slot or -1, the token, the
+    slot that receives the new state) in, the model's natural-log next-token rows out; it is called on this thread, once per frame
+    for the whole mini-batch.  The model scores the prefix BEFORE merge_repeated.  n_best == 0: (ids [B,T], out_len [B], log_prob
+    [B]); otherwise (ids [B,n_best,T], out_len [B,n_best], log_prob [B,n_best], n_found [B]) -- log_prob is the fused score.
+    An exception in `step` ends the search and is raised here."""
+    import numpy as np
+    host = logits.detach().cpu().numpy() if torch.is_tensor(logits) else np.asarray(logits)
+    host = np.ascontiguousarray(host, np.float32)
+    T, B, C_ = host.shape
+    n_best = int(n_best)
+    lens = np.ascontiguousarray(lengths.cpu().numpy() if torch.is_tensor(lengths) else lengths, np.int32)
+    shape = (B,) if n_best == 0 else (B, n_best)
+    ids = np.empty(shape + (T,), np.int32)
+    out_len = np.empty(shape, np.int32)
+    logp = np.empty(shape, np.float32)
+    n_found = np.empty(B, np.int32)
+    raised = []
+
+    def trampoline(_user, n, parent, token, dest, logq):
+        try:
+            q = step(np.ctypeslib.as_array(parent, (n,)).copy(), np.ctypeslib.as_array(token, (n,)).copy(),
+                     np.ctypeslib.as_array(dest, (n,)).copy())
+            if isinstance(q, int):                      # a status instead of rows: passed through as the call's status
+                return q
+            q = np.asarray(q, np.float32)
+            if q.shape != (n, C_):
+                raise ValueError("ctc_beam_search_fused: step returned %s, expected (%d, %d)" % (q.shape, n, C_))
+            np.ctypeslib.as_array(logq, (n, C_))[...] = q
+            return 0
+        except BaseException as e:                      # noqa: B902  (nothing may unwind through the C frames)
+            raised.append(e)
+            return _l.ECALLBACK
+
+    cb = _l.LM_STEP_FN(trampoline)
+    rc = _l.load().amdspeech_ctc_beam_search_host_fused(
+        host.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), T, B, C_, int(beam_width), int(bool(merge_repeated)), n_best,
+        float(lm_weight), float(lm_length_bonus), cb, None, ids.ctypes.data_as(C.c_void_p), out_len.ctypes.data_as(C.c_void_p),
+        logp.ctypes.data_as(C.c_void_p), n_found.ctypes.data_as(C.c_void_p), int(max_threads))
+    if raised:
+        raise raised[0]
+    _l.check(rc, "ctc_beam_search_host_fused")
+    return (ids, out_len, logp) if n_best == 0 else (ids, out_len, logp, n_found)

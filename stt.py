@@ -332,13 +332,16 @@ def _language_model(hyper_params, training):
 
 
 def build_rescorer(hyper_params):
-    """AcousticModel.rescorer from the lm_* keys: None at lm_weight 0 (the default: nothing is loaded, launched or allocated), else
-    the restored language model behind an n-best rescorer.  A missing checkpoint is an error that names the directory."""
+    """AcousticModel.rescorer from the lm_* keys: None at lm_weight 0 (the default: nothing is loaded, launched or allocated,
+    whatever lm_fusion says), else the restored language model behind an n-best rescorer (lm_fusion : rescore) or inside the beam
+    (lm_fusion : beam).  A missing checkpoint is an error that names the directory."""
     if not hyper_params.get("lm_weight", 0) > 0:
         return None
-    from rnn_speech_amd.language_model import NbestRescorer
+    from rnn_speech_amd.language_model import FusedDecoder, NbestRescorer
     model = _language_model(hyper_params, training=False)
     model.restore(None, hyper_params["checkpoint_dir"], must_exist=True)
+    if hyper_params.get("lm_fusion", "rescore") == "beam":
+        return FusedDecoder(model, hyper_params["lm_weight"], lm_length_bonus=hyper_params.get("lm_length_bonus", 0.0))
     return NbestRescorer(model.score, hyper_params["lm_weight"], hyper_params.get("lm_nbest", 16), hyper_params.get("lm_length_bonus", 0.0))
 
 
