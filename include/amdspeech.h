@@ -337,7 +337,7 @@ int amdspeech_lstm_bwd(void* stream, const amdspeech_lstm_desc* d, void* ws,
  * Same semantics as amdspeech_ctc_loss_fwd_bwd on the same logits: the loss is bit-identical (same device code), dlogits
  * equal to ~1e-7 (the order LDS atomics meet in).  A head on lstm_fwd_ctc obliges the caller to run lstm_bwd_ctc (not lstm_bwd)
  * for that mini-batch, or no backward pass at all.  amdspeech_lstm_ctc_fusable says whether a descriptor takes the head: the
- * whole-sequence kernels (H % 128 == 0, H <= 512, at least one XCD without a recurrence group), C a multiple of 16 up to 80,
+ * whole-sequence kernels (H % 128 == 0, H <= 512, at least one XCD without a recurrence group), C one of 16, 32, 48, 64 and 80,
  * 2 U + 1 <= 384 extended states, B within two utterances per follower team; AMDSPEECH_FLOW_CTC=0 switches it off.  `ctc_ws`:
  * amdspeech_ctc_workspace_bytes(T, B, C, U) bytes, 256-byte aligned, the same T as the descriptor's.                          */
 typedef struct amdspeech_ctc_head {

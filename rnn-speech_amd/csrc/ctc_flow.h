@@ -108,7 +108,7 @@ __device__ __forceinline__ void ctc_follower(const CtcFlow& c, float* lds, const
 #pragma unroll
         for (int u = 0; u < UPT; ++u) {
             CtcChain& U = us[u];
-            // ---- 16 frames x K slice [128 w, 128 w + 128) of the top layer's output, row b of its batch tile: lane (j, kq) takes the
+            // ---- 16 frames x K slice [H/4 w, H/4 w + H/4) of the top layer's output, row b of its batch tile: lane (j, kq) takes the
             // float4 (4 k) of frame t0 + j from that frame's panel (packed_off: block (b/16, k/16), float4 kq*16 + b%16)
             const int fj = min(t0 + (lane & 15), T - 1);
             const unsigned vo = (unsigned)((size_t)fj * bph * 4) +
