@@ -391,8 +391,14 @@ int amdspeech_lstm_plan(const amdspeech_lstm_desc* d, int C, int U, amdspeech_ls
  * (`mv` counts whole blocks): 0 none, 2 one block (full roles on the spare XCDs), 3 a block and a half (half roles on waves 4-7 of
  * the worker workgroups too: gates f and o of a second K block -- exact f32, H = 512, one full role per SIMD fits); -1: bad
  * descriptor.  Read-only like amdspeech_lstm_plan.  The environment switch AMDSPEECH_FLOW_FWD_WORKERS (read once per process)
- * picks among the kernels a shape can take: 0 = no workers, 1 = full roles only, unset or 2 = half roles where they fit.     */
+ * picks among the kernels a shape can take: 0 = no workers, 1 = full roles only, 2 or unset = half roles where they fit
+ * (2: exactly round 6's; unset: the half roles extended by k-steps, below).                                                  */
 int amdspeech_lstm_plan_xw_halves(const amdspeech_lstm_desc* d, int C, int U);
+/* ... and how many of the four k-steps of the K block BELOW the half roles' block those roles take as well, for their two N tiles
+ * (gates f, o) and into the same tile -- more K, not more N: the frame of the workers' tile history and the workspace size do not
+ * change; the recurrence waves multiply those two tiles of that block for the other k-steps only.  0: none (no half roles, or
+ * AMDSPEECH_FLOW_FWD_WORKERS=2); -1: bad descriptor.  amdspeech_lstm_plan_xw_halves keeps counting whole half blocks (3).        */
+int amdspeech_lstm_plan_xw_ksteps(const amdspeech_lstm_desc* d, int C, int U);
 
 /* ------------------------------------------------ layer-wise bidirectional stacks ----
  * tf.contrib.rnn.stack_bidirectional_dynamic_rnn (torch.nn.LSTM(bidirectional=True, num_layers=L)): L layers, each a forward and

@@ -431,13 +431,14 @@ static bool use_flow(const amdspeech_lstm_desc* d) {
 // The instantiations of the two dataflow kernels, by K blocks per wave and half (H / 128) and precision; CF: with the fused CTC
 // head's role (flow_shape_ok: reduced precision only at H = 256, 512; x-product workers only in exact f32 at H = 512)
 template <bool CF>
-static void (*flow_fwd_kernel(int kb, int pr, int mv, int mh))(FlowArgs) {
+static void (*flow_fwd_kernel(int kb, int pr, int mv, int mh, int me))(FlowArgs) {
     switch (kb) {
         case 1: return lstm_fwd_flow2<1, 0, 0, CF>;
         case 2: return pr == 2 ? lstm_fwd_flow2<2, 2, 0, CF> : (pr == 1 ? lstm_fwd_flow2<2, 1, 0, CF> : lstm_fwd_flow2<2, 0, 0, CF>);
         case 3: return lstm_fwd_flow2<3, 0, 0, CF>;
         default:
-            if (pr == 0 && mv == 1) return mh == 1 ? lstm_fwd_flow2<4, 0, 1, CF, 1> : lstm_fwd_flow2<4, 0, 1, CF>;
+            if (pr == 0 && mv == 1 && mh == 1) return me > 0 ? lstm_fwd_flow2<4, 0, 1, CF, 1, FWD2_HALF_KSTEPS> : lstm_fwd_flow2<4, 0, 1, CF, 1>;
+            if (pr == 0 && mv == 1) return lstm_fwd_flow2<4, 0, 1, CF>;
             return pr == 2 ? lstm_fwd_flow2<4, 2, 0, CF> : (pr == 1 ? lstm_fwd_flow2<4, 1, 0, CF> : lstm_fwd_flow2<4, 0, 0, CF>);
     }
 }
@@ -635,7 +636,8 @@ struct LstmPlan {
     size_t fwd_lds, bwd_lds;              // their dynamic LDS
     int mv, wpx, wpw;                     // x-product workers: K blocks per recurrence wave (0: none), workgroups per spare XCD, waves per role
     int mh;                               // ... half roles on waves 4-7 of those workgroups (0 or 1; wpw = 4 then)
-    int nfw;                              // the fused CTC head's followers per spare XCD (0: no head, or the shape does not take it)
+    int me;                               // ... the k-steps of the block below that the half roles take as well (0, or FWD2_HALF_KSTEPS)
+    int nfw;                             // the fused CTC head's followers per spare XCD (0: no head, or the shape does not take it)
     int dz0_inkernel;                     // lstm_bwd_flow2: dZ_0 formed by the layer-0 groups
     int w_pieces, w_t0, w_dz0;            // ... its in-kernel weight gradients: chunks (0: none), first frame, dZ_0 too
     bool w_deal;                          // ... dealt from counters
@@ -712,8 +714,9 @@ static LstmPlan lstm_plan(const amdspeech_lstm_desc* d, const amdspeech_ctc_head
 
     // ---- the dataflow kernels.  x-product workers (lstm_fwd_flow2<., ., 1>): one role per SIMD where that fits, else two; where one
     // fits, waves 4-7 of the worker workgroups take half roles (lstm_fwd_flow2<., ., 1, ., 1>: a block and a half per recurrence wave)
-    // (AMDSPEECH_FLOW_FWD_WORKERS=0: the kernel of rounds 2 - 4, every recurrence wave multiplies its whole x half; 1: full roles only)
-    static const int workers_env = runtime_switch("AMDSPEECH_FLOW_FWD_WORKERS", 2);
+    // (AMDSPEECH_FLOW_FWD_WORKERS=0: the kernel of rounds 2 - 4, every recurrence wave multiplies its whole x half; 1: full roles only;
+    //  2: full and half roles, the half roles without the k-steps of the block below -- the kernel of round 6; unset / 3: with them)
+    static const int workers_env = runtime_switch("AMDSPEECH_FLOW_FWD_WORKERS", 3);
     const int groups = L * p.nmt, spare = 8 - groups;
     p.wpw = 8;
     if (workers_env != 0 && p.xw_parts > 0)
@@ -722,9 +725,10 @@ static LstmPlan lstm_plan(const amdspeech_lstm_desc* d, const amdspeech_ctc_head
             if (per <= 32 - FWD2_WORKER_RESERVE) { p.mv = 1; p.wpx = per; p.wpw = waves; }
         }
     p.mh = (workers_env != 1 && p.mv == 1 && p.wpw == 4 && p.xw_half > 0) ? 1 : 0;
+    p.me = (p.mh == 1 && workers_env != 2) ? FWD2_HALF_KSTEPS : 0;
     if (head != nullptr) p.nfw = ctc_head_nfw(d, head->C, head->U, p.wpx);
     const int kb = H / 128;
-    p.fwd_flow = head != nullptr ? flow_fwd_kernel<true>(kb, pr, p.mv, p.mh) : flow_fwd_kernel<false>(kb, pr, p.mv, p.mh);
+    p.fwd_flow = head != nullptr ? flow_fwd_kernel<true>(kb, pr, p.mv, p.mh, p.me) : flow_fwd_kernel<false>(kb, pr, p.mv, p.mh, p.me);
     p.bwd_flow = head != nullptr ? flow_bwd_kernel<true>(kb, pr) : flow_bwd_kernel<false>(kb, pr);
     p.fwd_lds = head != nullptr ? (size_t)2 * CF_FOLLOW_TEAM_FLOATS * sizeof(float) : 0;      // (ctc_follower's two teams)
     // two dG tiles, the dh reduction buffer, the stash, the down product's per-wave tiles (double-buffered), the partners' dG tiles
@@ -1603,6 +1607,14 @@ extern "C" int amdspeech_lstm_plan_xw_halves(const amdspeech_lstm_desc* d, int C
     h.C = C; h.U = U;
     const LstmPlan p = lstm_plan(d, C > 0 ? &h : nullptr);
     return 2 * p.mv + p.mh;
+}
+// ... and the k-steps (of four) of the K block below the half roles' that those roles take as well (ME of lstm_fwd_flow2; 0: none)
+extern "C" int amdspeech_lstm_plan_xw_ksteps(const amdspeech_lstm_desc* d, int C, int U) {
+    if (check_desc(d) != AMDSPEECH_OK) return -1;
+    amdspeech_ctc_head h{};
+    h.C = C; h.U = U;
+    const LstmPlan p = lstm_plan(d, C > 0 ? &h : nullptr);
+    return p.me;
 }
 extern "C" int amdspeech_lstm_ctc_fusable(const amdspeech_lstm_desc* d, int C, int U) {
     if (check_desc(d) != AMDSPEECH_OK) return 0;

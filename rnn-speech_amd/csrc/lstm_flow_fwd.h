@@ -14,8 +14,14 @@
 #ifndef FWD2_GATHER_AT
 #define FWD2_GATHER_AT 1          // the loads of h_t are issued after this many of the K blocks of the x half (clamped to the last one)
 #endif
+#ifndef FWD2_GATHER_AT_EXT
+#define FWD2_GATHER_AT_EXT 0      // ... in the instantiation with extended half roles (ME > 0): its x half behind the gather point is 4 ME MFMAs
+#endif                            // per SIMD shorter, and the loads of h_t in front of the whole x half measured 0.07 ms per launch better than behind block 0
 #ifndef FWD2_WORKER_LAG
 #define FWD2_WORKER_LAG 4         // x-product workers above the bottom layer: frames they stay behind the layer below (see fwd_x_worker)
+#endif
+#ifndef FWD2_HALF_KSTEPS
+#define FWD2_HALF_KSTEPS 2        // ME: the k-steps of the K block below theirs that the half roles take as well (2 or 3; see fwd_x_worker)
 #endif
 
 // ---- x-product workers of lstm_fwd_flow2 (round 5) ---------------------------------------------------------------------------
@@ -35,13 +41,23 @@
 // 64 VGPRs of weights, 64 MFMAs per frame, a [16 rows x 32 gate columns] tile as two 1 KiB stores (element lane*4 + i: its two
 // gates as 8 bytes) behind the full tiles of the frame.  Two full roles on one SIMD cost more than a recurrence step (round 5,
 // MV = 2); a role and a half, 192 MFMAs per frame, stays under it.
+// EXTENDED HALF ROLES (ME > 0): the half role takes more K, not more N -- for its two N tiles also the last ME of the four k-steps
+// of the block below, {w*KB + KB-2-MV}, into the SAME accumulators: 16 ME more VGPRs of weights, 16 ME more MFMAs and 8 more panel
+// loads per frame (only the ME dwords of the 16 bytes it uses), the same tile, the same two stores, the same frame of xwp.  The
+// recurrence wave multiplies N tiles 2 and 3 of that block for k-steps 0 .. 3-ME only: 192 + 16 ME against 208 - 4 ME per SIMD.
 // NTW: the N tiles of this role (4: a full role, 2: a half role); MH: whether the launch has half roles (the frame of xwp holds them)
-template <int KB, int MV, int MH, int NTW>
+// ME: the extra k-steps of a half role (0 for a full role)
+template <int KB, int MV, int MH, int NTW, int ME = 0>
 __device__ __forceinline__ void fwd_x_worker(const FlowArgs& a, const int role, const int lane, const unsigned long long t_begin) {
     constexpr int H = 128 * KB, NKBX = H / 16, NU = H / 16, NT = 4;
     constexpr bool HALF = NTW != NT;
     constexpr int J0 = NT - NTW;             // the first N tile of the role
     static_assert(NTW == 4 || (NTW == 2 && MH == 1), "x-product workers: full roles, or half roles of a launch that carries them");
+    static_assert(ME == 0 || (NTW == 2 && (ME == 2 || ME == 3) && KB - 2 - MV >= 0), "extended half roles: 2 or 3 k-steps of the block below the half role's");
+    constexpr bool EXT = ME > 0;
+    constexpr int MEA = EXT ? ME : 2;        // (the register arrays of a role without the extension: never touched)
+    constexpr int NLD = 8 + (EXT ? 8 : 0);   // loads per frame: the panel's eight blocks (+ the eight partial blocks below them)
+    typedef unsigned xe_t __attribute__((ext_vector_type(MEA)));
     const int T = a.T, nmt = (a.B + 15) / 16;
     int r = __builtin_amdgcn_readfirstlane(role);
     const int part = HALF ? MV : r % MV;     // (the K block KB-1-part: a half role takes the one below the full roles')
@@ -59,6 +75,16 @@ __device__ __forceinline__ void fwd_x_worker(const FlowArgs& a, const int role, 
 #pragma unroll
             for (int j = 0; j < NTW; ++j) w[wv][j] = *reinterpret_cast<const float4*>(wp + (size_t)((wv * KB + KB - 1 - part) * NT + J0 + j) * 256);
     }
+    float we[8][2][MEA];                     // k-steps 4-ME .. 3 of the block below, N tiles 2 and 3
+    if constexpr (EXT) {
+        const float* wp = a.wp + ((size_t)(l * NU + ub) * (2 * NKBX)) * (NT * 256) + lane * 4 + (4 - ME);
+#pragma unroll
+        for (int wv = 0; wv < 8; ++wv)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int m = 0; m < ME; ++m) we[wv][j][m] = wp[(size_t)((wv * KB + KB - 2 - MV) * NT + J0 + j) * 256 + m];
+    }
     const float* xsrc = l == 0 ? a.xp0 : a.xph + (size_t)l * T * bph;
     const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xsrc), 0, (unsigned)((size_t)T * bph * 4), 0x00020000);
     const size_t fs = (size_t)a.L * nmt * NU * (MV * 1024 + MH * 512);                 // floats per frame of xwp: the full tiles, then the half tiles
@@ -69,20 +95,44 @@ __device__ __forceinline__ void fwd_x_worker(const FlowArgs& a, const int role, 
     const unsigned par = a.xw_par & 1u;
     bool dead = false;
     u32x4_f xa[8] = {}, xb[8] = {};
+    xe_t ea[8] = {}, eb[8] = {};             // (ME > 0) the last ME dwords of the lane's 16 bytes of the blocks below
+    // (an extended half role addresses BOTH blocks from one register per recurrence wave, the lane's 16 bytes of the LOWER block:
+    //  its own dwords at the immediate offset (4-ME)*4, the block above at 1024 -- a second set of eight offsets did not fit 256 VGPRs)
+    constexpr int MOFF = EXT ? 1024 : 0, EOFF = (4 - MEA) * 4;
+    const unsigned lane_base = lane_off - (unsigned)MOFF;
     // EVERY load of the frame loop is inline assembly and every wait an explicit s_waitcnt (the pattern of gemm_tile_tn_direct):
     // left to hipcc, the retry paths below turn the waits in front of the MFMAs into vmcnt(0) -- a wait for
     // the probe issued a moment earlier, i.e. a round trip to memory in series with every frame's MFMAs (first version: 5.6 us per
-    // step).  The frame loop issues, per frame and in this order: 1 probe, NTW tile stores (a half role: 2), 8 panel loads -- always,
-    // with clamped frame indices at the end of the sequence -- so "this frame's panel and probe have landed" is vmcnt(8 + NTW) everywhere.
+    // step).  The frame loop issues, per frame and in this order: 1 probe, NTW tile stores (a half role: 2), NLD panel loads (8; an
+    // extended half role: 8 + 8) -- always, with clamped frame indices at the end of the sequence -- so "this frame's panel and probe
+    // have landed" is vmcnt(NLD + NTW) everywhere.
     // (plain lambdas: clang does not capture a variable that a GENERIC lambda names only in an asm operand)
-    auto load_l2 = [&](u32x4_f& dst, unsigned vo, unsigned so) { asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "+v"(dst) : "v"(vo), "s"(rx), "s"(so)); };
-    auto load_mem = [&](u32x4_f& dst, unsigned vo, unsigned so) { asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen sc1" : "+v"(dst) : "v"(vo), "s"(rx), "s"(so)); };
-    auto issue = [&](auto bottom, u32x4_f (&buf)[8], int t) {
+    auto load_l2 = [&](u32x4_f& dst, unsigned vo, unsigned so) { asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:%4" : "+v"(dst) : "v"(vo), "s"(rx), "s"(so), "n"(MOFF)); };
+    auto load_mem = [&](u32x4_f& dst, unsigned vo, unsigned so) { asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:%4 sc1" : "+v"(dst) : "v"(vo), "s"(rx), "s"(so), "n"(MOFF)); };
+    // (the ME dwords of a lane's 16 bytes that an extended half role multiplies)
+    auto ext_l2 = [&](xe_t& dst, unsigned vo, unsigned so) {
+        if constexpr (ME == 3) asm volatile("buffer_load_dwordx3 %0, %1, %2, %3 offen offset:%4" : "+v"(dst) : "v"(vo), "s"(rx), "s"(so), "n"(EOFF));
+        else asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen offset:%4" : "+v"(dst) : "v"(vo), "s"(rx), "s"(so), "n"(EOFF));
+    };
+    auto ext_mem = [&](xe_t& dst, unsigned vo, unsigned so) {
+        if constexpr (ME == 3) asm volatile("buffer_load_dwordx3 %0, %1, %2, %3 offen offset:%4 sc1" : "+v"(dst) : "v"(vo), "s"(rx), "s"(so), "n"(EOFF));
+        else asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen offset:%4 sc1" : "+v"(dst) : "v"(vo), "s"(rx), "s"(so), "n"(EOFF));
+    };
+    auto issue = [&](auto bottom, u32x4_f (&buf)[8], xe_t (&ebuf)[8], int t) {
         const unsigned base = (unsigned)((size_t)(t < T ? t : T - 1) * bph * 4);
 #pragma unroll
         for (int wv = 0; wv < 8; ++wv) {       // (bottom layer: xp0 is complete and read through this XCD's L2; above it: sc1, served by memory)
-            const unsigned vo = lane_off + (unsigned)(wv * KB * 1024);
-            if (decltype(bottom)::value) load_l2(buf[wv], vo, base); else load_mem(buf[wv], vo, base);
+            // (an extended half role: the recurrence wave's stride in the SCALAR offset -- eight vector offsets fewer)
+            const unsigned vo = EXT ? lane_base : lane_base + (unsigned)(wv * KB * 1024);
+            const unsigned so = EXT ? base + (unsigned)(wv * KB * 1024) : base;
+            if (decltype(bottom)::value) load_l2(buf[wv], vo, so); else load_mem(buf[wv], vo, so);
+        }
+        if constexpr (EXT) {
+#pragma unroll
+            for (int wv = 0; wv < 8; ++wv) {
+                const unsigned so = base + (unsigned)(wv * KB * 1024);
+                if (decltype(bottom)::value) ext_l2(ebuf[wv], lane_base, so); else ext_mem(ebuf[wv], lane_base, so);
+            }
         }
     };
     FLOW_WEIGHTS_RESIDENT();
@@ -95,19 +145,35 @@ __device__ __forceinline__ void fwd_x_worker(const FlowArgs& a, const int role, 
     u32x4_f pr = (u32x4_f){0u, 0u, 0u, 0u};
     auto probe = [&](int t) {
         const int tp = t + FWD2_WORKER_LAG < T ? t + FWD2_WORKER_LAG : T - 1;
-        load_mem(pr, lane_off, (unsigned)((size_t)tp * bph * 4));
+        load_mem(pr, lane_base, (unsigned)((size_t)tp * bph * 4));
     };
-    // at most 8 + NTW / 0 younger operations may still be in flight: the probe and the panel have landed
-    auto landed12 = [&](u32x4_f (&buf)[8]) {
-        asm volatile("s_waitcnt vmcnt(%9)" : "+v"(pr), "+v"(buf[0]), "+v"(buf[1]), "+v"(buf[2]), "+v"(buf[3]), "+v"(buf[4]), "+v"(buf[5]), "+v"(buf[6]), "+v"(buf[7]) : "n"(8 + NTW));
+    // at most NLD + NTW / 0 younger operations may still be in flight: the probe and the panel have landed
+    // (the ONE counted wait of the frame loop: what a frame issues behind its probe -- NTW stores, NLD loads)
+    constexpr int FRAME_INFLIGHT = NLD + NTW;
+    auto landed12 = [&](u32x4_f (&buf)[8], xe_t (&ebuf)[8]) {
+        if constexpr (EXT)
+            asm volatile("s_waitcnt vmcnt(%17)" : "+v"(pr), "+v"(buf[0]), "+v"(buf[1]), "+v"(buf[2]), "+v"(buf[3]), "+v"(buf[4]), "+v"(buf[5]), "+v"(buf[6]), "+v"(buf[7]),
+                         "+v"(ebuf[0]), "+v"(ebuf[1]), "+v"(ebuf[2]), "+v"(ebuf[3]), "+v"(ebuf[4]), "+v"(ebuf[5]), "+v"(ebuf[6]), "+v"(ebuf[7]) : "n"(FRAME_INFLIGHT));
+        else
+            asm volatile("s_waitcnt vmcnt(%9)" : "+v"(pr), "+v"(buf[0]), "+v"(buf[1]), "+v"(buf[2]), "+v"(buf[3]), "+v"(buf[4]), "+v"(buf[5]), "+v"(buf[6]), "+v"(buf[7]) : "n"(FRAME_INFLIGHT));
     };
-    auto landed0 = [&](u32x4_f (&buf)[8]) {
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(pr), "+v"(buf[0]), "+v"(buf[1]), "+v"(buf[2]), "+v"(buf[3]), "+v"(buf[4]), "+v"(buf[5]), "+v"(buf[6]), "+v"(buf[7]));
+    auto landed0 = [&](u32x4_f (&buf)[8], xe_t (&ebuf)[8]) {
+        if constexpr (EXT)
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(pr), "+v"(buf[0]), "+v"(buf[1]), "+v"(buf[2]), "+v"(buf[3]), "+v"(buf[4]), "+v"(buf[5]), "+v"(buf[6]), "+v"(buf[7]),
+                         "+v"(ebuf[0]), "+v"(ebuf[1]), "+v"(ebuf[2]), "+v"(ebuf[3]), "+v"(ebuf[4]), "+v"(ebuf[5]), "+v"(ebuf[6]), "+v"(ebuf[7]));
+        else
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(pr), "+v"(buf[0]), "+v"(buf[1]), "+v"(buf[2]), "+v"(buf[3]), "+v"(buf[4]), "+v"(buf[5]), "+v"(buf[6]), "+v"(buf[7]));
     };
-    auto pending_any = [&](const u32x4_f (&buf)[8]) -> bool {      // branch-free (a chain of || became eight saveexec branches)
+    auto pending_any = [&](const u32x4_f (&buf)[8], const xe_t (&ebuf)[8]) -> bool {      // branch-free (a chain of || became eight saveexec branches)
         unsigned bad = 0u;
 #pragma unroll
         for (int wv = 0; wv < 8; ++wv) bad |= (unsigned)flow_pending(buf[wv]);
+        if constexpr (EXT) {
+#pragma unroll
+            for (int wv = 0; wv < 8; ++wv)
+#pragma unroll
+                for (int m = 0; m < ME; ++m) bad |= (unsigned)(ebuf[wv][m] == FLOW_SENTINEL);
+        }
         return bad != 0u;
     };
 #if defined(AMDSPEECH_DEVTRACE) && AMDSPEECH_DEVTRACE == 5      // tools/trace_fwd2.py: the worker of layer 1 (if any), batch tile 0, unit block 3, part 0
@@ -116,19 +182,19 @@ __device__ __forceinline__ void fwd_x_worker(const FlowArgs& a, const int role, 
 #else
 #define FXWSTAMP(i) do { } while (0)
 #endif
-    auto work = [&](auto bottom, int t, u32x4_f (&buf)[8]) __attribute__((always_inline)) {
+    auto work = [&](auto bottom, int t, u32x4_f (&buf)[8], xe_t (&ebuf)[8]) __attribute__((always_inline)) {
         FXWSTAMP(0);
-        landed12(buf);
+        landed12(buf, ebuf);
         FXWSTAMP(1);
         if (!decltype(bottom)::value) {
-            if (__any(flow_pending(pr) || pending_any(buf)) && !dead) {      // the gate is shut, or (never seen) a panel behind it is missing
+            if (__any(flow_pending(pr) || pending_any(buf, ebuf)) && !dead) {      // the gate is shut, or (never seen) a panel behind it is missing
                 while (true) {
                     if (wall_clock64() - t_begin > a.limit) { dead = true; if (lane == 0) atomicOr(a.err, 8u); break; }
                     __builtin_amdgcn_s_sleep(4);
                     probe(t);
-                    issue(bottom, buf, t);
-                    landed0(buf);
-                    if (!__any(flow_pending(pr) || pending_any(buf))) break;
+                    issue(bottom, buf, ebuf, t);      // (both blocks again)
+                    landed0(buf, ebuf);
+                    if (!__any(flow_pending(pr) || pending_any(buf, ebuf))) break;
                 }
             }
         }
@@ -146,6 +212,15 @@ __device__ __forceinline__ void fwd_x_worker(const FlowArgs& a, const int role, 
                 acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(buf[wv][2]), w[wv][j].z, acc[j], 0, 0, 0);
                 acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(buf[wv][3]), w[wv][j].w, acc[j], 0, 0, 0);
             }
+        if constexpr (EXT) {      // k-steps 4-ME .. 3 of the blocks below, into the same two accumulators
+#pragma unroll
+            for (int wv = 0; wv < 8; ++wv)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int m = 0; m < ME; ++m)
+                        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(ebuf[wv][m]), we[wv][j][m], acc[j], 0, 0, 0);
+        }
         // element lane*4 + i of the 16x16 tile: its four gates as one 16-byte word at slot i*64 + lane (a 1 KiB run per store)
         // (the frame offset in voffset, not in an SGPR soffset: the gfx950 store hazard noted at lstm_bwd_flow2's store_tiles)
         const unsigned fo = out_off + (unsigned)((size_t)t * fs * 4);
@@ -159,34 +234,34 @@ __device__ __forceinline__ void fwd_x_worker(const FlowArgs& a, const int role, 
         }
         __builtin_amdgcn_sched_barrier(0);
         FXWSTAMP(3);
-        issue(bottom, buf, t + 2);      // (two register sets: the operand panels are requested two frames ahead; past the end: the last frame again)
+        issue(bottom, buf, ebuf, t + 2);      // (two register sets: the operand panels are requested two frames ahead; past the end: the last frame again)
         FXWSTAMP(4);
     };
 #undef FXWSTAMP
     auto run = [&](auto bottom) __attribute__((always_inline)) {
         probe(0);
         if (!decltype(bottom)::value) {                // the first panels are requested once the gate of frame 0 is open
-            landed0(xa);
+            landed0(xa, ea);
             if (__any(flow_pending(pr)) && !dead) {
                 while (true) {
                     if (wall_clock64() - t_begin > a.limit) { dead = true; if (lane == 0) atomicOr(a.err, 8u); break; }
                     __builtin_amdgcn_s_sleep(4);
                     probe(0);
-                    landed0(xa);
+                    landed0(xa, ea);
                     if (!__any(flow_pending(pr))) break;
                 }
             }
         }
-        issue(bottom, xa, 0);
-        landed0(xa);
+        issue(bottom, xa, ea, 0);
+        landed0(xa, ea);
         // (frame 0: its probe and panel have landed, only the second panel is in flight; from frame 1 on the order above holds)
-        issue(bottom, xb, 1);
+        issue(bottom, xb, eb, 1);
         for (int t = 0; t < T; t += 2) {
-            work(bottom, t, xa);
-            if (t + 1 < T) work(bottom, t + 1, xb);
+            work(bottom, t, xa, ea);
+            if (t + 1 < T) work(bottom, t + 1, xb, eb);
         }
-        landed0(xa);
-        landed0(xb);
+        landed0(xa, ea);
+        landed0(xb, eb);
     };
     if (l == 0) run(std::true_type{}); else run(std::false_type{});
 }
@@ -214,10 +289,12 @@ __device__ __forceinline__ void ctc_follower_call(const CtcFlow& c, int wg, int 
     else ctc_follower<H, 2>(c, cf_lds, wg, nwg);
 }
 
-template <int KB, int PR, int MV, bool CF = false, int MH = 0>   // KB: 16-row K blocks per wave and half (H / 128); PR: 0 exact f32, 1 bf16x3, 2 bf16 products (KB even);
+template <int KB, int PR, int MV, bool CF = false, int MH = 0, int ME = 0>   // KB: 16-row K blocks per wave and half (H / 128); PR: 0 exact f32, 1 bf16x3, 2 bf16 products (KB even);
                                     // MV: K blocks per wave of the x half that the x-product workers of the spare XCDs form (0: none)
                                     // MH: 1 = half roles too (fwd_x_worker): of the wave's K block KB-1-MV the workers form N tiles 2 and 3
                                     // (gates f, o) and the wave multiplies N tiles 0 and 1 only -- "a block and a half" with MV = 1
+                                    // ME: the half roles also form, for those two N tiles, the last ME k-steps of the block below
+                                    // (KB-2-MV); the wave multiplies N tiles 2 and 3 of that block for k-steps 0 .. 3-ME only
                                     // CF: the instantiation that carries the fused CTC head's follower (ctc_flow.h).  A separate one: the
                                     // role's scalar-register pressure costs the recurrence loops of the SAME function lane moves per
                                     // step (register allocation is per function), which launches without a head must not pay
@@ -225,6 +302,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
     constexpr bool BF3 = PR != 0;
     static_assert(MV >= 0 && MV < KB && (MV == 0 || PR == 0), "x-product workers: exact f32 only, and one K block of the x half stays");
     static_assert(MH == 0 || (MH == 1 && MV > 0 && KB - MV >= 2), "half roles: beside full roles, and one whole K block of the x half stays");
+    static_assert(ME == 0 || (MH == 1 && (ME == 2 || ME == 3)), "extended half roles: 2 or 3 k-steps, in a launch with half roles");
     constexpr int KX = KB - MV;       // K blocks of the x half this wave multiplies itself (MH: the last of them for N tiles 0 and 1 only)
     constexpr int NTL = MH ? 2 : 4;   // ... the N tiles of that last block
     constexpr int MVA = MV > 0 ? MV : 1;
@@ -242,9 +320,9 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
     if (grp >= a_in.L * ((a_in.B + 15) / 16)) {             // an XCD without a recurrence group
         const int first = a_in.L * ((a_in.B + 15) / 16);
         if (MV > 0 && ub < a_in.w_wpx && wave < a_in.w_wpw)
-            fwd_x_worker<KB, MVA, MH, 4>(a_in, (((grp - first) * a_in.w_wpx + ub) * a_in.w_wpw + wave), lane, wall_clock64());
+            fwd_x_worker<KB, MVA, MH, 4, 0>(a_in, (((grp - first) * a_in.w_wpx + ub) * a_in.w_wpw + wave), lane, wall_clock64());
         else if (MH > 0 && ub < a_in.w_wpx) {      // (w_wpw = 4: wave 4 + w takes the half role of the units of wave w's full role)
-            if constexpr (MH > 0) fwd_x_worker<KB, MVA, MH, 2>(a_in, (((grp - first) * a_in.w_wpx + ub) * 4 + wave - 4), lane, wall_clock64());
+            if constexpr (MH > 0) fwd_x_worker<KB, MVA, MH, 2, ME>(a_in, (((grp - first) * a_in.w_wpx + ub) * 4 + wave - 4), lane, wall_clock64());
         }
         else if (CF && a_in.cf_on && ub >= a_in.w_wpx && ub < a_in.w_wpx + a_in.cf_nfw) {
             // the CTC head's forward half (ctc_flow.h): output Linear + log-softmax + alpha, 16 frames behind the top layer
@@ -271,7 +349,11 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
         for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                if (kb < KX && (kb < KX - 1 || j < NTL)) { const f32x4 v = *(const f32x4 __attribute__((address_space(1)))*)(wp + (size_t)((wave * KB + kb) * NT + j) * 256); wx[kb][j] = make_float4(v[0], v[1], v[2], v[3]); }
+                if (ME > 0 && kb == KX - 2 && j >= 2) {      // (the half roles hold k-steps 4-ME .. 3 of these two tiles: those words are not loaded)
+                    const float __attribute__((address_space(1)))* q = wp + (size_t)((wave * KB + kb) * NT + j) * 256;
+                    wx[kb][j] = make_float4(q[0], ME < 3 ? q[1] : 0.0f, 0.0f, 0.0f);
+                }
+                else if (kb < KX && (kb < KX - 1 || j < NTL)) { const f32x4 v = *(const f32x4 __attribute__((address_space(1)))*)(wp + (size_t)((wave * KB + kb) * NT + j) * 256); wx[kb][j] = make_float4(v[0], v[1], v[2], v[3]); }
                 { const f32x4 v = *(const f32x4 __attribute__((address_space(1)))*)(wp + (size_t)((NKBX + wave * KB + kb) * NT + j) * 256); wh[kb][j] = make_float4(v[0], v[1], v[2], v[3]); }
             }
     }
@@ -471,8 +553,19 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
         }
 #endif
     };
+    // the block of the x half whose N tiles 2 and 3 the extended half roles share: those two tiles for k-steps 0 .. 3-ME only
+    auto mma_block_cut = [&](const u32x4_f& v, const float4 (&w)[NT]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[0]), w[j].x, acc[j], 0, 0, 0);
+            if (j < 2 || ME < 3) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[1]), w[j].y, acc[j], 0, 0, 0);
+            if (j < 2) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[2]), w[j].z, acc[j], 0, 0, 0);
+            if (j < 2) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(v[3]), w[j].w, acc[j], 0, 0, 0);
+        }
+    };
     // one half of the product: the wave's KB blocks of operand `v` against the matching weight fragments
-    // (last_tiles: the N tiles of the LAST block -- NTL for the x half, whose other tiles the half roles form)
+    // (last_tiles: the N tiles of the LAST block -- NTL for the x half, whose other tiles the half roles form; with fewer than NT
+    //  of them and ME > 0, i.e. in the x half of a launch with extended half roles, the block before the last is cut as well)
     auto half_product = [&](const auto& v, const auto& w, const u32x4_f (&wh_)[KP][NT], const u32x4_f (&wl_)[KP][NT],
                             auto between, auto last_tiles) __attribute__((always_inline)) {
         constexpr int NB = (int)(sizeof(v) / sizeof(v[0]));       // KB for the h half, KX for the x half
@@ -494,6 +587,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
             for (int kb = 0; kb < NB; ++kb) {
                 between(kb);
                 if (kb == NB - 1) mma_block(v[kb], w[kb], last_tiles);
+                else if (ME > 0 && decltype(last_tiles)::value < NT && kb == NB - 2) mma_block_cut(v[kb], w[kb]);
                 else mma_block(v[kb], w[kb], std::integral_constant<int, NT>{});
             }
         }
@@ -565,7 +659,8 @@ __global__ __launch_bounds__(512) void lstm_fwd_flow2(FlowArgs a_in) {
         if (t + 1 < T) {
             if (decltype(xpol)::value != 2 && !(ASM && FWD2_EARLY_XCHECK)) settle(Remote{}, xnext, rx, (unsigned)((size_t)(t + 1) * bph * 4));
             half_product(xnext, wx, wxh, wxl, [&](int kb) {
-                if (gather_h && kb == (FWD2_GATHER_AT < KX ? FWD2_GATHER_AT : KX - 1)) {
+                constexpr int GAT = ME > 0 ? FWD2_GATHER_AT_EXT : FWD2_GATHER_AT;
+                if (gather_h && kb == (GAT < KX ? GAT : KX - 1)) {
                     __builtin_amdgcn_sched_barrier(0);
                     issue(Local{}, hv, rh, (unsigned)((size_t)(t + 1) * bph * 4));
                     __builtin_amdgcn_sched_barrier(0);

@@ -162,6 +162,7 @@ PROTOTYPES = {
     "amdspeech_lstm_dropout_multipliers": (_I, [_P, C.POINTER(LstmDesc), _I, _I, _P]),
     "amdspeech_lstm_plan": (_I, [C.POINTER(LstmDesc), _I, _I, C.POINTER(LstmPlanInfo)]),
     "amdspeech_lstm_plan_xw_halves": (_I, [C.POINTER(LstmDesc), _I, _I]),
+    "amdspeech_lstm_plan_xw_ksteps": (_I, [C.POINTER(LstmDesc), _I, _I]),
     "amdspeech_lstm_bidir_workspace_bytes": (_SZ, [C.POINTER(LstmDesc)]),
     "amdspeech_lstm_bidir_ws_ptr": (_P, [C.POINTER(LstmDesc), _P, _I]),
     "amdspeech_lstm_bidir_layer_stride": (_L, [C.POINTER(LstmDesc)]),

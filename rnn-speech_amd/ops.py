@@ -449,6 +449,18 @@ def lstm_plan_xw_halves(ws, head=None, per_diagonal=False):
     return n
 
 
+def lstm_plan_xw_ksteps(ws, head=None, per_diagonal=False):
+    """How many of the four k-steps of the K block below theirs the half roles of the forward dataflow launch take as well
+    (amdspeech.h: amdspeech_lstm_plan_xw_ksteps); 0: none.  Read-only, like lstm_plan."""
+    c_u = (0, 0) if head is None else ((head.c.C, head.c.U) if isinstance(head, CtcHead) else (int(head[0]), int(head[1])))
+    d = _l.LstmDesc(ws.desc.T, ws.desc.B, ws.desc.H, ws.desc.L, ws.desc.keep_in, ws.desc.keep_out, ws.desc.seed, ws.desc.precision,
+                    _l.LSTM_PER_DIAGONAL if per_diagonal else 0)
+    n = int(ws.lib.amdspeech_lstm_plan_xw_ksteps(C.byref(d), c_u[0], c_u[1]))
+    if n < 0:
+        raise ValueError("lstm_plan_xw_ksteps: bad descriptor")
+    return n
+
+
 def lstm_fwd(ws, kernels, kernel_stride, biases, bias_stride, lengths, h0=None, c0=None, training=False, per_diagonal=False, head=None):
     """kernels/biases: tensors whose data_ptr is layer 0's K / bias; strides in elements.
     training: lstm_bwd on the same workspace follows; the call then prepares that call's hand-off panels and the next forward
