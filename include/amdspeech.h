@@ -436,7 +436,22 @@ enum {
 size_t amdspeech_lstm_bidir_workspace_bytes(const amdspeech_lstm_desc* d);
 void* amdspeech_lstm_bidir_ws_ptr(const amdspeech_lstm_desc* d, void* ws, int which);
 long amdspeech_lstm_bidir_layer_stride(const amdspeech_lstm_desc* d);
-int amdspeech_lstm_bidir_path(const amdspeech_lstm_desc* d);
+int amdspeech_lstm_bidir_path(const amdspeech_lstm_desc* d);      /* = the plan's `path`, below */
+/* What amdspeech_lstm_bidir_fwd / _bwd on this descriptor launch for the recurrence -- each call plans once and launches from this;
+ * read-only: nothing is launched, no pointer is dereferenced, d->flags & AMDSPEECH_LSTM_PER_DIAGONAL is honoured.  Errors: those
+ * of the other entry points for the descriptor (AMDSPEECH_EUNSUPPORTED: precision 2, a hidden size the kernels do not take),
+ * AMDSPEECH_EINVAL for a null `out`.
+ *   path                2 / 1 / 0 as above;  cus: the device's compute units the path was planned for (0: no device, path 0)
+ *   fwd_* / bwd_*       the recurrence kernel of the forward / backward call:
+ *     kpw               bf16x3: K blocks of 32 per wave, the instantiation lstm_layer_{fwd,bwd}_bf3<KPW> (0 at precision 0)
+ *     waves             waves of 64 threads per workgroup (precision 0: 8)
+ *     groups            bf16x3: groups of 4 (forward) / 2 (backward) 16-row batch tiles per block of hidden units (precision 0: 1)
+ *     wgs               workgroups PER DIRECTION: a path-2 and a per-frame launch have 2 * wgs, a path-1 launch wgs
+ *     lds               dynamic LDS bytes per workgroup                                                                         */
+typedef struct amdspeech_lstm_bidir_plan_info {
+    int path, cus, fwd_kpw, fwd_waves, fwd_groups, fwd_wgs, fwd_lds, bwd_kpw, bwd_waves, bwd_groups, bwd_wgs, bwd_lds;
+} amdspeech_lstm_bidir_plan_info;
+int amdspeech_lstm_bidir_plan(const amdspeech_lstm_desc* d, amdspeech_lstm_bidir_plan_info* out);
 int amdspeech_lstm_bidir_fwd(void* stream, const amdspeech_lstm_desc* d, void* ws, const float* const* kernels,
                              const float* const* biases, const int* lengths, const float* h0, const float* c0);
 int amdspeech_lstm_bidir_bwd(void* stream, const amdspeech_lstm_desc* d, void* ws, const float* const* kernels,

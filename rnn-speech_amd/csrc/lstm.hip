@@ -1642,383 +1642,9 @@ extern "C" int amdspeech_lstm_bwd_ctc(void* stream, const amdspeech_lstm_desc* d
     return lstm_bwd(static_cast<hipStream_t>(stream), BwdCall{d, static_cast<float*>(ws), kernels, kernel_stride, dkernels, dbiases, bias_stride, lengths, head});
 }
 
-// ------------------------------------------------------------------- layer-wise bidirectional stacks (lstm_layer.h)
+// ------------------------------------------- layer-wise bidirectional stacks: their kernels, then their host driver (lstm_bidir.h)
 namespace amdspeech {
 #include "lstm_layer.h"
 #include "lstm_layer_bf3.h"
-
-struct BidirLayout {
-    size_t sync, z0, dz0, g[2], dx[2], dy[2], dc[2], total;
-    size_t xin[2], hh[2], hc[2], gates[2], y[2];      // of layer 0; layer l at + l * per_layer[dir]
-    size_t per_layer;
-    size_t ring[2];       // precision 1 only (behind everything else): the split h / dG ring of each direction
-};
-static size_t bidir_sync_words(int T) { return 64 + 2 * ((size_t)T + 1); }      // error word, then the two directions' counters
-static BidirLayout bidir_layout(const amdspeech_lstm_desc* d) {
-    const size_t T = d->T, B = d->B, H = d->H, L = d->L, tbh = T * B * H;
-    BidirLayout o;
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t r = off; off += (n + 63) / 64 * 64; return r; };
-    o.sync = take(bidir_sync_words(d->T));      // (first: the block the per-launch memset zeroes)
-    o.z0 = take(tbh);
-    o.dz0 = take(tbh);
-    for (int k = 0; k < 2; ++k) {
-        o.g[k] = take(4 * tbh);
-        o.dx[k] = take(2 * tbh);
-        o.dy[k] = take(tbh);
-        o.dc[k] = take(B * H);
-    }
-    // per layer and direction: the cell input (2H wide: layer 0 uses the first H columns' worth), h / c history, gates, output
-    const size_t start = off;
-    for (int k = 0; k < 2; ++k) {
-        o.xin[k] = take(2 * tbh);
-        o.hh[k] = take((T + 1) * B * H);
-        o.hc[k] = take((T + 1) * B * H);
-        o.gates[k] = take(4 * tbh);
-        o.y[k] = take(tbh);
-    }
-    o.per_layer = off - start;
-    off = start + L * o.per_layer;
-    o.ring[0] = o.ring[1] = 0;
-    if (d->precision == 1)      // two slots of [16 * ceil(B / 16)][4H] (bf16 hi + lo = one float per value); forward uses the first H
-        for (int k = 0; k < 2; ++k) o.ring[k] = take(2 * ((B + 15) / 16 * 16) * 4 * H);
-    o.total = off;
-    return o;
-}
-static size_t bidir_at(const BidirLayout& o, size_t base, int l) { return base + (size_t)l * o.per_layer; }
-
-// bf16x3 kernels: K-blocks (32 wide) per wave, from the instantiated set, such that the waves of a workgroup take the whole K
-// (forward K = H, at most 8 waves; backward K = 4H, at most 16); 0 = no instance takes this hidden size
-static int bf3_kpw(int nkb, int max_waves, int max_kpw) {
-    for (int kpw = 1; kpw <= max_kpw; kpw *= 2)
-        if (nkb % kpw == 0 && nkb / kpw <= max_waves) return kpw;
-    return 0;
-}
-static int bf3_fwd_kpw(const amdspeech_lstm_desc* d) { return bf3_kpw(d->H / 32, LBF3_FWD_MAXW, 4); }
-static int bf3_bwd_kpw(const amdspeech_lstm_desc* d) { return bf3_kpw(4 * d->H / 32, LBF3_BWD_MAXW, 16); }
-
-static int bidir_check(const amdspeech_lstm_desc* d) {
-    if (int rc = check_desc(d)) return rc;
-    if (d->precision == 2) {
-        set_error("lstm_bidir: the layer-wise bidirectional mode runs in exact f32 (precision 0) or bf16x3 (1), not plain bf16 (2)");
-        return AMDSPEECH_EUNSUPPORTED;
-    }
-    if (d->precision == 1 && (d->H > 1024 || bf3_fwd_kpw(d) == 0 || bf3_bwd_kpw(d) == 0)) {
-        set_error("lstm_bidir: bf16x3 does not take hidden size %d: its kernels split the H (forward) and 4H (backward) rows of "
-                  "W_hh over at most 8 waves, 32 x 1, 2, 4, 8 or 16 rows each (H = 64, 128, 256, 512, 768, 1024 qualify)", d->H);
-        return AMDSPEECH_EUNSUPPORTED;
-    }
-    if (d->H > 1024) {
-        set_error("lstm_bidir: hidden size %d above 1024 (the recurrence keeps H x %d floats of W_hh per workgroup in LDS)", d->H, 4 * LAYER_U);
-        return AMDSPEECH_EUNSUPPORTED;
-    }
-    AS_CHECK_ARG((size_t)d->T * d->B * 2 * d->H < (1ull << 32), "lstm_bidir: T*B*2H too large for the dropout counter");
-    return AMDSPEECH_OK;
-}
-// The bf16x3 recurrence launch of one direction: kernel, workgroups, threads, dynamic LDS (the partial tiles of every wave)
-struct Bf3Launch {
-    void (*kern)(LayerBf3Args);
-    int nwg, threads, ngrp;
-    size_t lds;
-};
-static Bf3Launch bf3_launch(const amdspeech_lstm_desc* d, bool bwd) {
-    const int nmt = (d->B + 15) / 16;
-    Bf3Launch r;
-    if (bwd) {
-        const int kpw = bf3_bwd_kpw(d);
-        r.kern = kpw == 1 ? lstm_layer_bwd_bf3<1, 1> : kpw == 2 ? lstm_layer_bwd_bf3<2, 1> : kpw == 4 ? lstm_layer_bwd_bf3<4, 1>
-               : kpw == 8 ? lstm_layer_bwd_bf3<8, 1> : lstm_layer_bwd_bf3<16, 1>;
-        r.ngrp = ceil_div(nmt, LBF3_BWD_MB);
-        r.nwg = d->H / LBF3_BWD_U * r.ngrp;
-        r.threads = 4 * d->H / 32 / kpw * 64;
-        r.lds = (size_t)(r.threads / 64) * LBF3_BWD_MB * LBF3_BWD_NT * 1024;
-    } else {
-        const int kpw = bf3_fwd_kpw(d);
-        r.kern = kpw == 1 ? lstm_layer_fwd_bf3<1, 1> : kpw == 2 ? lstm_layer_fwd_bf3<2, 1> : lstm_layer_fwd_bf3<4, 1>;
-        r.ngrp = ceil_div(nmt, LBF3_FWD_MB);
-        r.nwg = d->H / LBF3_FWD_U * r.ngrp;
-        r.threads = d->H / 32 / kpw * 64;
-        r.lds = (size_t)(r.threads / 64) * LBF3_FWD_MB * LBF3_FWD_NT * 1024;
-    }
-    return r;
-}
-// 2 = both directions of a layer in ONE persistent launch, 1 = one persistent launch per direction, 0 = one launch per frame
-static int bidir_path(const amdspeech_lstm_desc* d) {
-    static const int env = runtime_switch("AMDSPEECH_BIDIR_PERSISTENT", 1);      // 0: the per-frame launches
-    if (env == 0 || (d->flags & AMDSPEECH_LSTM_PER_DIAGONAL)) return 0;
-    const int cus = device_cus();
-    if (d->precision == 1) {      // one workgroup per CU, if the kernels' registers and LDS admit one at all
-        if (cus <= 0) return 0;
-        int nwg = 0;
-        for (int bwd = 0; bwd < 2; ++bwd) {
-            const Bf3Launch l = bf3_launch(d, bwd != 0);
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(l.kern), l.threads, l.lds) != hipSuccess ||
-                per_cu < 1) return 0;
-            nwg = nwg > l.nwg ? nwg : l.nwg;
-        }
-        return 2 * nwg <= cus ? 2 : (nwg <= cus ? 1 : 0);
-    }
-    const int nwg = d->H / LAYER_U;
-    return 2 * nwg <= cus ? 2 : (nwg <= cus ? 1 : 0);
-}
-static size_t bidir_lds(const amdspeech_lstm_desc* d, bool bwd) {
-    return (size_t)d->H * (bwd ? 4 * LAYER_U : LAYER_FWD_WS) * sizeof(float);
-}
-static int bidir_lds_attr(const amdspeech_lstm_desc* d) {
-    static unsigned long long seen = 0;
-    if (DeviceOnce once{&seen}) {
-        const int max_lds = (int)(1024 * LAYER_FWD_WS * sizeof(float));
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_layer_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_layer_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        const int max_bf3 = LBF3_FWD_MAXW * LBF3_FWD_MB * LBF3_FWD_NT * 1024;      // (the backward kernels take at most a quarter of it)
-        void (*bf3[])(LayerBf3Args) = {lstm_layer_fwd_bf3<1, 1>, lstm_layer_fwd_bf3<2, 1>, lstm_layer_fwd_bf3<4, 1>, lstm_layer_bwd_bf3<1, 1>,
-                                       lstm_layer_bwd_bf3<2, 1>, lstm_layer_bwd_bf3<4, 1>, lstm_layer_bwd_bf3<8, 1>, lstm_layer_bwd_bf3<16, 1>};
-        for (auto k : bf3)
-            AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, max_bf3));
-        once.done();
-    }
-    (void)d;
-    return AMDSPEECH_OK;
-}
-static uint64_t bidir_seed(const amdspeech_lstm_desc* d, int dir) { return dir ? d->seed ^ 0x5bd1e995ull : d->seed; }
-
-// One layer's recurrence (both directions) on whatever path the descriptor takes
-static int bidir_recurrence(hipStream_t s, const amdspeech_lstm_desc* d, float* ws, const BidirLayout& lo, LayerArgs a, bool bwd) {
-    const int nwg = d->H / LAYER_U, path = bidir_path(d);
-    const size_t lds = bidir_lds(d, bwd);
-    void (*kern)(LayerArgs) = bwd ? lstm_layer_bwd : lstm_layer_fwd;
-    a.err = reinterpret_cast<unsigned*>(ws + lo.sync);
-    a.limit = (d->flags & AMDSPEECH_LSTM_INJECT_TIMEOUT) ? 0ull : 100000000ull + (unsigned long long)d->T * 10000ull;
-    // the counters of both directions (the error word stays: a time-out of an earlier layer is reported, not forgotten)
-    AS_CHECK_HIP(hipMemsetAsync(ws + lo.sync + 64, 0, 2 * ((size_t)d->T + 1) * sizeof(unsigned), s));
-    if (d->precision == 1) {
-        const Bf3Launch l = bf3_launch(d, bwd);
-        LayerBf3Args x{};
-        x.a = a;
-        x.ngrp = l.ngrp;
-        for (int k = 0; k < 2; ++k) x.ring[k] = reinterpret_cast<uint4*>(ws + lo.ring[k]);
-        if (path == 2) {
-            x.a.s0 = 0; x.a.s1 = d->T;
-            hipLaunchKernelGGL(l.kern, dim3(2 * l.nwg), dim3(l.threads), l.lds, s, x);
-            AS_CHECK_LAUNCH();
-        } else if (path == 1) {
-            x.a.s0 = 0; x.a.s1 = d->T;
-            for (int k = 0; k < 2; ++k) {
-                LayerBf3Args one = x;
-                one.a.dir[0] = a.dir[k];
-                one.ring[0] = x.ring[k];
-                hipLaunchKernelGGL(l.kern, dim3(l.nwg), dim3(l.threads), l.lds, s, one);
-                AS_CHECK_LAUNCH();
-            }
-        } else {
-            for (int t = 0; t < d->T; ++t) {
-                x.a.s0 = bwd ? d->T - 1 - t : t;
-                x.a.s1 = x.a.s0 + 1;
-                hipLaunchKernelGGL(l.kern, dim3(2 * l.nwg), dim3(l.threads), l.lds, s, x);
-                AS_CHECK_LAUNCH();
-            }
-        }
-        return AMDSPEECH_OK;
-    }
-    if (path == 2) {
-        a.s0 = 0; a.s1 = d->T;
-        hipLaunchKernelGGL(kern, dim3(2 * nwg), dim3(LAYER_THREADS), lds, s, a);
-        AS_CHECK_LAUNCH();
-    } else if (path == 1) {
-        a.s0 = 0; a.s1 = d->T;
-        for (int k = 0; k < 2; ++k) {
-            LayerArgs one = a;
-            one.dir[0] = a.dir[k];
-            hipLaunchKernelGGL(kern, dim3(nwg), dim3(LAYER_THREADS), lds, s, one);
-            AS_CHECK_LAUNCH();
-        }
-    } else {
-        for (int t = 0; t < d->T; ++t) {
-            a.s0 = bwd ? d->T - 1 - t : t;
-            a.s1 = a.s0 + 1;
-            hipLaunchKernelGGL(kern, dim3(2 * nwg), dim3(LAYER_THREADS), lds, s, a);
-            AS_CHECK_LAUNCH();
-        }
-    }
-    return AMDSPEECH_OK;
-}
-
-static LayerDir bidir_dir(const amdspeech_lstm_desc* d, float* ws, const BidirLayout& lo, int l, int k, const float* kernel) {
-    const int W = l ? 2 * d->H : d->H;
-    LayerDir r{};
-    r.g = ws + lo.g[k];
-    r.w = kernel + (size_t)W * 4 * d->H;
-    r.hh = ws + bidir_at(lo, lo.hh[k], l);
-    r.hc = ws + bidir_at(lo, lo.hc[k], l);
-    r.gates = ws + bidir_at(lo, lo.gates[k], l);
-    r.y = ws + bidir_at(lo, lo.y[k], l);
-    r.dy = ws + lo.dy[k];
-    r.dg = ws + lo.g[k];
-    r.dc = ws + lo.dc[k];
-    r.cnt = reinterpret_cast<unsigned*>(ws + lo.sync + 64) + (size_t)k * (d->T + 1);
-    r.seed = bidir_seed(d, k);
-    r.rev = k;
-    return r;
-}
-
-static int bidir_fwd(hipStream_t s, const amdspeech_lstm_desc* d, float* ws, const float* const* kernels, const float* const* biases,
-                     const int* lengths, const float* h0, const float* c0) {
-    if (int rc = bidir_check(d)) return rc;
-    AS_CHECK_ARG(ws && kernels && biases && lengths, "lstm_bidir_fwd: null pointer");
-    AS_CHECK_ARG(((uintptr_t)ws % 256) == 0, "lstm_bidir_fwd: workspace must be 256-byte aligned");
-    for (int i = 0; i < 2 * d->L; ++i) AS_CHECK_ARG(kernels[i] && biases[i], "lstm_bidir_fwd: null kernel / bias of cell %d", i);
-    if (int rc = bidir_lds_attr(d)) return rc;
-    const BidirLayout lo = bidir_layout(d);
-    const int T = d->T, B = d->B, H = d->H;
-    const size_t bh = (size_t)B * H;
-    AS_CHECK_HIP(hipMemsetAsync(ws + lo.sync, 0, 64 * sizeof(float), s));      // error word
-    if (d->precision == 1)      // (the rows of the last 16-row tile past B are read, never written: zero)
-        AS_CHECK_HIP(hipMemsetAsync(ws + lo.ring[0], 0, (lo.total - lo.ring[0]) * sizeof(float), s));
-    prof_flops(0, 0.0, 0.0);
-    prof_begin(0, s);
-    for (int l = 0; l < d->L; ++l) {
-        const int W = l ? 2 * H : H;
-        const float* src0 = l ? ws + bidir_at(lo, lo.y[0], l - 1) : ws + lo.z0;
-        const float* src1 = l ? ws + bidir_at(lo, lo.y[1], l - 1) : nullptr;
-        LayerArgs a{};
-        for (int k = 0; k < 2; ++k) {
-            float* xin = ws + bidir_at(lo, lo.xin[k], l);
-            const size_t n4 = (size_t)T * B * W / 4;
-            hipLaunchKernelGGL(bidir_pack_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, s, src0, src1, xin, lengths, T, B, H, W, k,
-                               bidir_seed(d, k), l, d->keep_in);
-            AS_CHECK_LAUNCH();
-            const float* K = kernels[k * d->L + l];
-            if (int rc = gemm_batched(d, s, false, false, T * B, 4 * H, W, xin, W, K, 4 * H, ws + lo.g[k], 4 * H, biases[k * d->L + l], false))
-                return rc;
-            a.dir[k] = bidir_dir(d, ws, lo, l, k, K);
-            float* hh = ws + bidir_at(lo, lo.hh[k], l);
-            float* hc = ws + bidir_at(lo, lo.hc[k], l);
-            if (k == 0 && h0) AS_CHECK_HIP(hipMemcpyAsync(hh, h0 + l * bh, bh * sizeof(float), hipMemcpyDeviceToDevice, s));
-            else AS_CHECK_HIP(hipMemsetAsync(hh, 0, bh * sizeof(float), s));
-            if (k == 0 && c0) AS_CHECK_HIP(hipMemcpyAsync(hc, c0 + l * bh, bh * sizeof(float), hipMemcpyDeviceToDevice, s));
-            else AS_CHECK_HIP(hipMemsetAsync(hc, 0, bh * sizeof(float), s));
-            if (d->precision == 1) {      // the initial h, split, into ring slot 0: what step 0 of the bf16x3 kernel reads
-                hipLaunchKernelGGL(pack_rows_bf3_kernel, dim3(ceil_div(bh, 256)), dim3(256), 0, s, hh, bh,
-                                   reinterpret_cast<unsigned short*>(ws + lo.ring[k]), B, H, 1);
-                AS_CHECK_LAUNCH();
-            }
-        }
-        a.lengths = lengths; a.T = T; a.B = B; a.H = H; a.layer = l; a.keep_out = d->keep_out; a.forget_bias = 1.0f;
-        if (int rc = bidir_recurrence(s, d, ws, lo, a, false)) return rc;
-    }
-    prof_end(0, s, bidir_path(d) ? d->L : d->L * T);
-    return AMDSPEECH_OK;
-}
-
-static int bidir_bwd(hipStream_t s, const amdspeech_lstm_desc* d, float* ws, const float* const* kernels, float* const* dkernels,
-                     float* const* dbiases, const int* lengths) {
-    if (int rc = bidir_check(d)) return rc;
-    AS_CHECK_ARG(ws && kernels && dkernels && dbiases && lengths, "lstm_bidir_bwd: null pointer");
-    AS_CHECK_ARG(((uintptr_t)ws % 256) == 0, "lstm_bidir_bwd: workspace must be 256-byte aligned");
-    for (int i = 0; i < 2 * d->L; ++i) AS_CHECK_ARG(kernels[i] && dkernels[i] && dbiases[i], "lstm_bidir_bwd: null pointer of cell %d", i);
-    if (int rc = bidir_lds_attr(d)) return rc;
-    const BidirLayout lo = bidir_layout(d);
-    const int T = d->T, B = d->B, H = d->H, TB = T * B;
-    if (d->precision == 1)
-        AS_CHECK_HIP(hipMemsetAsync(ws + lo.ring[0], 0, (lo.total - lo.ring[0]) * sizeof(float), s));
-    prof_flops(1, 0.0, 0.0);
-    prof_begin(1, s);
-    for (int l = d->L - 1; l >= 0; --l) {
-        const int W = l ? 2 * H : H;
-        LayerArgs a{};
-        for (int k = 0; k < 2; ++k) {
-            a.dir[k] = bidir_dir(d, ws, lo, l, k, kernels[k * d->L + l]);
-            AS_CHECK_HIP(hipMemsetAsync(ws + lo.dc[k], 0, (size_t)B * H * sizeof(float), s));
-        }
-        a.lengths = lengths; a.T = T; a.B = B; a.H = H; a.layer = l; a.keep_out = d->keep_out; a.forget_bias = 1.0f;
-        if (int rc = bidir_recurrence(s, d, ws, lo, a, true)) return rc;
-        for (int k = 0; k < 2; ++k) {
-            const float* dG = ws + lo.g[k];
-            const float* K = kernels[k * d->L + l];
-            float* dK = dkernels[k * d->L + l];
-            // dK[0:W] += X^T . dG (+ db), dK[W:W+H] += Hprev^T . dG, dX = dG . W_ih^T
-            const float* X = ws + bidir_at(lo, lo.xin[k], l);
-            if (d->precision == 0) {
-                if (int rc = gemm_f32(s, true, false, W, 4 * H, TB, X, W, dG, 4 * H, dK, 4 * H, nullptr, true, dbiases[k * d->L + l])) return rc;
-            } else {
-                if (int rc = gemm_reduced(d, s, true, false, W, 4 * H, TB, X, W, dG, 4 * H, dK, 4 * H, nullptr, true)) return rc;
-                if (int rc = colsum_accumulate(s, dG, TB, 4 * H, 4 * H, dbiases[k * d->L + l])) return rc;
-            }
-            if (int rc = gemm_batched(d, s, true, false, H, 4 * H, TB, ws + bidir_at(lo, lo.hh[k], l), H, dG, 4 * H, dK + (size_t)W * 4 * H,
-                                      4 * H, nullptr, true)) return rc;
-            if (int rc = gemm_batched(d, s, false, true, TB, W, 4 * H, dG, 4 * H, K, 4 * H, ws + lo.dx[k], W, nullptr, false)) return rc;
-        }
-        const size_t n4 = (size_t)T * B * W / 4;
-        float* out0 = l ? ws + lo.dy[0] : ws + lo.dz0;
-        float* out1 = l ? ws + lo.dy[1] : nullptr;
-        hipLaunchKernelGGL(bidir_split_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, s, ws + lo.dx[0], ws + lo.dx[1], out0, out1, lengths,
-                           T, B, H, W, bidir_seed(d, 0), bidir_seed(d, 1), l, d->keep_in);
-        AS_CHECK_LAUNCH();
-    }
-    prof_end(1, s, bidir_path(d) ? d->L : d->L * T);
-    return AMDSPEECH_OK;
-}
-
-extern "C" size_t amdspeech_lstm_bidir_workspace_bytes(const amdspeech_lstm_desc* d) {
-    if (bidir_check(d) != AMDSPEECH_OK) return 0;
-    return bidir_layout(d).total * sizeof(float);
-}
-extern "C" void* amdspeech_lstm_bidir_ws_ptr(const amdspeech_lstm_desc* d, void* ws, int which) {
-    if (ws == nullptr || bidir_check(d) != AMDSPEECH_OK) return nullptr;
-    const BidirLayout lo = bidir_layout(d);
-    float* w = static_cast<float*>(ws);
-    const size_t T = d->T, bh = (size_t)d->B * d->H;
-    switch (which) {
-        case AMDSPEECH_BIDIR_WS_Z0: return w + lo.z0;
-        case AMDSPEECH_BIDIR_WS_YTOP_FW: return w + bidir_at(lo, lo.y[0], d->L - 1);
-        case AMDSPEECH_BIDIR_WS_YTOP_BW: return w + bidir_at(lo, lo.y[1], d->L - 1);
-        case AMDSPEECH_BIDIR_WS_DYTOP_FW: return w + lo.dy[0];
-        case AMDSPEECH_BIDIR_WS_DYTOP_BW: return w + lo.dy[1];
-        case AMDSPEECH_BIDIR_WS_DZ0: return w + lo.dz0;
-        case AMDSPEECH_BIDIR_WS_HFINAL: return w + lo.hh[0] + T * bh;
-        case AMDSPEECH_BIDIR_WS_CFINAL: return w + lo.hc[0] + T * bh;
-        default: set_error("lstm_bidir_ws_ptr: unknown region %d", which); return nullptr;
-    }
-}
-extern "C" long amdspeech_lstm_bidir_layer_stride(const amdspeech_lstm_desc* d) {
-    if (bidir_check(d) != AMDSPEECH_OK) return -1;
-    return (long)bidir_layout(d).per_layer;
-}
-extern "C" int amdspeech_lstm_bidir_path(const amdspeech_lstm_desc* d) {
-    if (int rc = bidir_check(d)) return rc;
-    return bidir_path(d);
-}
-extern "C" int amdspeech_lstm_bidir_fwd(void* stream, const amdspeech_lstm_desc* d, void* ws, const float* const* kernels,
-                                        const float* const* biases, const int* lengths, const float* h0, const float* c0) {
-    return bidir_fwd(static_cast<hipStream_t>(stream), d, static_cast<float*>(ws), kernels, biases, lengths, h0, c0);
-}
-extern "C" int amdspeech_lstm_bidir_bwd(void* stream, const amdspeech_lstm_desc* d, void* ws, const float* const* kernels,
-                                        float* const* dkernels, float* const* dbiases, const int* lengths) {
-    return bidir_bwd(static_cast<hipStream_t>(stream), d, static_cast<float*>(ws), kernels, dkernels, dbiases, lengths);
-}
-extern "C" int amdspeech_lstm_bidir_status(const amdspeech_lstm_desc* d, void* ws) {
-    if (int rc = bidir_check(d)) return rc;
-    AS_CHECK_ARG(ws != nullptr, "lstm_bidir_status: null workspace");
-    unsigned err = 0;
-    AS_CHECK_HIP(hipMemcpy(&err, static_cast<float*>(ws) + bidir_layout(d).sync, sizeof(err), hipMemcpyDeviceToHost));
-    if (err != 0) {
-        set_error("lstm_bidir: a bounded wait of the persistent per-layer kernels timed out (the workgroups of one launch were not "
-                  "all resident); results of this step are invalid -- repeat it with AMDSPEECH_LSTM_PER_DIAGONAL");
-        return AMDSPEECH_ETIMEOUT;
-    }
-    return AMDSPEECH_OK;
-}
-extern "C" int amdspeech_lstm_bidir_dropout_multipliers(void* stream, const amdspeech_lstm_desc* d, int dir, int which, int layer,
-                                                        float* out) {
-    if (int rc = bidir_check(d)) return rc;
-    AS_CHECK_ARG(out != nullptr && (dir == 0 || dir == 1) && (which == 0 || which == 1) && layer >= 0 && layer < d->L,
-                 "lstm_bidir_dropout_multipliers: dir 0 / 1, which 0 (input mask) / 1 (output mask), layer in [0, L)");
-    const int W = which == 1 ? d->H : (layer ? 2 * d->H : d->H);
-    const size_t n = (size_t)d->T * d->B * W;
-    hipLaunchKernelGGL(bidir_mask_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), out, n,
-                       bidir_seed(d, dir), (uint32_t)(2 * layer + which), which ? d->keep_out : d->keep_in);
-    AS_CHECK_LAUNCH();
-    return AMDSPEECH_OK;
-}
+#include "lstm_bidir.h"
 }  // namespace amdspeech

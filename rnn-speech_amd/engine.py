@@ -165,7 +165,6 @@ class Engine(object):
         self._per_diagonal = False       # the last forward ran on the launch-per-diagonal kernels by request
         self._paired = False             # the last forward ran a bidirectional model's two stacks side by side (ops.lstm_fwd_pair)
         self._ws_b = self.lstm_ws_b if self.bidirectional and not self.layerwise else None
-        self._layer_path = None          # (layer-wise mode) amdspeech_lstm_bidir_path of the last forward
         # a real (non-NULL) stream for callers that want the overlapped backward pass: see on_stream()
         self.stream = torch.cuda.Stream(device=self.device, priority=-1)      # (ahead of the side stream that prefetches the next batch)
         self._aux_stream = None          # (mini_batch: carries the "beside the forward kernel" ordering point to the caller's hook)
@@ -310,7 +309,7 @@ class Engine(object):
         B, H = self.B, self.H
         ws.set_dropout(keep_in, keep_out, seed)
         ks, bs = self._cells(self.params)
-        self._layer_path = 0 if per_diagonal else ws.path()
+        self._per_diagonal = bool(per_diagonal)
         ops.lstm_bidir_fwd(ws, ks, bs, lengths, self.state_h if use_state else None, self.state_c if use_state else None,
                            per_frame=per_diagonal)
         if after_lstm is not None:
@@ -334,7 +333,8 @@ class Engine(object):
             # (side by side: ops.lstm_fwd_pair runs the one-XCD forward kernel whatever one stack alone would take)
             path["lstm_fwd"], path["lstm_bwd"] = ("big1" if self._paired else plan["fwd_path"]), plan["bwd_path"]
         if self.layerwise:      # the layer-wise recurrence: "persistent" (one launch per layer for both directions, or per direction) or "per_frame"
-            path["layer_recurrence"] = {2: "persistent", 1: "persistent_per_direction", 0: "per_frame"}.get(self._layer_path)
+            plan = ops.lstm_bidir_plan(self._ws, per_frame=self._per_diagonal)      # (at the run length, with the call's per-frame request)
+            path["layer_recurrence"] = {2: "persistent", 1: "persistent_per_direction", 0: "per_frame"}[plan["path"]]
             path["layer_product"] = self.precision      # its recurrent product: "f32" (vector ALUs) or "bf16x3" (bf16 MFMA)
         return path
 

@@ -39,7 +39,12 @@ class LstmPlanInfo(C.Structure):     # amdspeech_lstm_plan_info (include/amdspee
                                        "xw_parts", "nfw", "w_pieces", "dz0_inkernel", "flow2_q")]
 
 
-class CtcPlanInfo(C.Structure):      # amdspeech_ctc_plan_info (include/amdspeech.h): the recursion kernel of a CTC shape, read-only
+class LstmBidirPlanInfo(C.Structure):     # amdspeech_lstm_bidir_plan_info (include/amdspeech.h): the recurrence launches of a layer-wise bidirectional call, read-only
+    _fields_ = [(n, C.c_int) for n in ("path", "cus", "fwd_kpw", "fwd_waves", "fwd_groups", "fwd_wgs", "fwd_lds", "bwd_kpw", "bwd_waves",
+                                       "bwd_groups", "bwd_wgs", "bwd_lds")]
+
+
+class CtcPlanInfo(C.Structure):     # amdspeech_ctc_plan_info (include/amdspeech.h): the recursion kernel of a CTC shape, read-only
     _fields_ = [(n, C.c_int) for n in ("kernel", "threads", "rmax", "smax")]
 
 
@@ -167,6 +172,7 @@ PROTOTYPES = {
     "amdspeech_lstm_bidir_ws_ptr": (_P, [C.POINTER(LstmDesc), _P, _I]),
     "amdspeech_lstm_bidir_layer_stride": (_L, [C.POINTER(LstmDesc)]),
     "amdspeech_lstm_bidir_path": (_I, [C.POINTER(LstmDesc)]),
+    "amdspeech_lstm_bidir_plan": (_I, [C.POINTER(LstmDesc), C.POINTER(LstmBidirPlanInfo)]),
     "amdspeech_lstm_bidir_fwd": (_I, [_P, C.POINTER(LstmDesc), _P, _P, _P, _P, _P, _P]),
     "amdspeech_lstm_bidir_bwd": (_I, [_P, C.POINTER(LstmDesc), _P, _P, _P, _P, _P]),
     "amdspeech_lstm_bidir_status": (_I, [C.POINTER(LstmDesc), _P]),

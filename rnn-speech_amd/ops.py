@@ -309,34 +309,76 @@ def batchnorm_bwd_dp(dy, xhat, inv_std, dx, group, scratch):
 
 
 # -------------------------------------------------------------------------- LSTM
-class LstmWorkspace(object):
-    """Owns the device workspace of one (T,B,H,L) LSTM stack and exposes the
-    named regions as tensor views (no copies)."""
+class _StackWorkspace(object):
+    """What LstmWorkspace and BidirWorkspace share: the device allocation of one (T,B,H,L) descriptor, or a view of a longer one's
+    (prefix()), and its named regions as tensor views (no copies).  A subclass names its library entry points (_BYTES, _PTR) and
+    its messages (_NAME, _TOO_SMALL)."""
 
-    def __init__(self, T, B, H, L, keep_in=1.0, keep_out=1.0, seed=0, device="cuda", precision=0, _share=None):
+    def __init__(self, T, B, H, L, keep_in, keep_out, seed, device, precision, _share):
         self.lib = _l.load()
         self.desc = _l.LstmDesc(T, B, H, L, keep_in, keep_out, seed, int(precision))
-        nbytes = self.lib.amdspeech_lstm_workspace_bytes(C.byref(self.desc))
+        nbytes = getattr(self.lib, self._BYTES)(C.byref(self.desc))
         if nbytes == 0:
-            raise _l.AmdSpeechError("lstm workspace: " + self.lib.amdspeech_last_error().decode())
+            raise _l.AmdSpeechError(self._NAME + ": " + self.lib.amdspeech_last_error().decode())
         self.T, self.B, self.H, self.L = T, B, H, L
         if _share is None:
             self.buf = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
         else:
-            # (amdspeech_lstm_workspace_bytes of the owner covers every shorter run length of its shape; a view that does not fit would
-            #  make the kernels write past the allocation -- an error in every build, not an assert)
+            # (the owner's byte count covers every shorter run length of its shape; a view that does not fit would make the kernels
+            #  write past the allocation -- an error in every build, not an assert)
             if _share.numel() * 4 < nbytes:
-                raise _l.AmdSpeechError("lstm workspace: the layout for T = %d needs %d bytes, the shared allocation has %d"
-                                        % (T, nbytes, _share.numel() * 4))
+                raise _l.AmdSpeechError(self._TOO_SMALL % (T, nbytes, _share.numel() * 4))
             self.buf = _share
         if self.buf.data_ptr() % 256 != 0:
-            raise _l.AmdSpeechError("lstm workspace: allocation not 256-byte aligned")
+            raise _l.AmdSpeechError(self._NAME + ": allocation not 256-byte aligned")
+        self._prefixes = {}
+        self._root = self           # the owner of the allocation (prefix() views share it)
+
+    def prefix(self, T_run):
+        """The same allocation laid out for a shorter sequence (the layout is a pure function of the
+        descriptor, and everything is time-major, so a batch whose longest utterance has T_run < T frames
+        runs T_run + L - 1 diagonals instead of T + L - 1 -- what tf.nn.dynamic_rnn's while-loop does with
+        max(sequence_length), reference models/AcousticModel.py:276-278)."""
+        if T_run >= self.T:
+            return self
+        ws = self._prefixes.get(T_run)
+        if ws is None:
+            if len(self._prefixes) > 64:
+                self._prefixes.clear()
+            ws = type(self)(T_run, self.B, self.H, self.L, device=self.buf.device, precision=self.desc.precision, _share=self.buf)
+            ws._root = self
+            self._prefixes[T_run] = ws
+        return ws
+
+    def _offset(self, which):
+        p = getattr(self.lib, self._PTR)(C.byref(self.desc), _p(self.buf), which)
+        if not p:
+            raise _l.AmdSpeechError(self._PTR[len("amdspeech_"):] + " failed")
+        return (p - self.buf.data_ptr()) // 4
+
+    def _view(self, which, shape):
+        off = self._offset(which)
+        n = 1
+        for s in shape:
+            n *= s
+        return self.buf[off:off + n].view(*shape)
+
+    def set_dropout(self, keep_in, keep_out, seed):
+        self.desc.keep_in, self.desc.keep_out, self.desc.seed = keep_in, keep_out, seed
+
+
+class LstmWorkspace(_StackWorkspace):
+    """Owns the device workspace of one (T,B,H,L) LSTM stack and exposes the
+    named regions as tensor views (no copies)."""
+    _NAME, _BYTES, _PTR = "lstm workspace", "amdspeech_lstm_workspace_bytes", "amdspeech_lstm_ws_ptr"
+    _TOO_SMALL = "lstm workspace: the layout for T = %d needs %d bytes, the shared allocation has %d"
+
+    def __init__(self, T, B, H, L, keep_in=1.0, keep_out=1.0, seed=0, device="cuda", precision=0, _share=None):
+        _StackWorkspace.__init__(self, T, B, H, L, keep_in, keep_out, seed, device, precision, _share)
         self.z0 = self._view(_l.WS_Z0, (T, B, H))
         self.ztop = self._view(_l.WS_ZTOP, (T, B, H))
         self.dztop = self._view(_l.WS_DZTOP, (T, B, H))
         self.dz0 = self._view(_l.WS_DZ0, (T, B, H))
-        self._prefixes = {}
-        self._root = self           # the owner of the allocation (prefix() views share it)
         self._armed = None          # (root only) {"fwd": (T, precision) | None, "bwd": ...}: layouts whose hand-off panels are prepared
         self._ever_armed = False    # (root only) the library keeps side-stream state (events) for this allocation
         self._fwd_seen = False      # (root only) lstm_fwd has run on this allocation: the next one may say AMDSPEECH_LSTM_SAME_WS
@@ -352,39 +394,6 @@ class LstmWorkspace(object):
                 self.lib.amdspeech_lstm_workspace_release(_stream(), _p(self.buf))
         except Exception:      # interpreter shutdown: nothing left to protect
             pass
-
-    def prefix(self, T_run):
-        """The same allocation laid out for a shorter sequence (the layout is a pure function of the
-        descriptor, and everything is time-major, so a batch whose longest utterance has T_run < T frames
-        runs T_run + L - 1 diagonals instead of T + L - 1 -- what tf.nn.dynamic_rnn's while-loop does with
-        max(sequence_length), reference models/AcousticModel.py:276-278)."""
-        if T_run >= self.T:
-            return self
-        ws = self._prefixes.get(T_run)
-        if ws is None:
-            if len(self._prefixes) > 64:
-                self._prefixes.clear()
-            ws = LstmWorkspace(T_run, self.B, self.H, self.L, device=self.buf.device,
-                               precision=self.desc.precision, _share=self.buf)
-            ws._root = self
-            self._prefixes[T_run] = ws
-        return ws
-
-    def _offset(self, which):
-        p = self.lib.amdspeech_lstm_ws_ptr(C.byref(self.desc), _p(self.buf), which)
-        if not p:
-            raise _l.AmdSpeechError("lstm_ws_ptr failed")
-        return (p - self.buf.data_ptr()) // 4
-
-    def _view(self, which, shape):
-        off = self._offset(which)
-        n = 1
-        for s in shape:
-            n *= s
-        return self.buf[off:off + n].view(*shape)
-
-    def set_dropout(self, keep_in, keep_out, seed):
-        self.desc.keep_in, self.desc.keep_out, self.desc.seed = keep_in, keep_out, seed
 
     def final_state(self):
         """(h [L,B,H], c [L,B,H]) views of the state after the last frame."""
@@ -592,25 +601,15 @@ def lstm_dropout_multipliers(ws, which, layer):
     return out
 
 
-class BidirWorkspace(object):
+class BidirWorkspace(_StackWorkspace):
     """Workspace of a layer-wise bidirectional stack (amdspeech.h: amdspeech_lstm_bidir_*): named regions as tensor views.
     precision: 0 = exact f32, 1 = bf16x3 (the recurrent and batched products as three bf16 MFMAs per product)."""
+    _NAME, _BYTES, _PTR = "lstm bidir workspace", "amdspeech_lstm_bidir_workspace_bytes", "amdspeech_lstm_bidir_ws_ptr"
+    _TOO_SMALL = "lstm bidir workspace: T = %d needs %d bytes, the shared allocation has %d"
 
     def __init__(self, T, B, H, L, device="cuda", precision=0, _share=None):
-        self.lib = _l.load()
-        self.desc = _l.LstmDesc(T, B, H, L, 1.0, 1.0, 0, precision)
-        nbytes = self.lib.amdspeech_lstm_bidir_workspace_bytes(C.byref(self.desc))
-        if nbytes == 0:
-            raise _l.AmdSpeechError("lstm bidir workspace: " + self.lib.amdspeech_last_error().decode())
-        self.T, self.B, self.H, self.L, self.precision = T, B, H, L, precision
-        if _share is None:
-            self.buf = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
-        else:
-            if _share.numel() * 4 < nbytes:
-                raise _l.AmdSpeechError("lstm bidir workspace: T = %d needs %d bytes, the shared allocation has %d"
-                                        % (T, nbytes, _share.numel() * 4))
-            self.buf = _share
-        self._root, self._prefixes = self, {}
+        _StackWorkspace.__init__(self, T, B, H, L, 1.0, 1.0, 0, device, precision, _share)
+        self.precision = precision
         self.z0 = self._view(_l.BIDIR_WS_Z0, (T, B, H))
         self.ytop_fw = self._view(_l.BIDIR_WS_YTOP_FW, (T, B, H))
         self.ytop_bw = self._view(_l.BIDIR_WS_YTOP_BW, (T, B, H))
@@ -618,41 +617,9 @@ class BidirWorkspace(object):
         self.dytop_bw = self._view(_l.BIDIR_WS_DYTOP_BW, (T, B, H))
         self.dz0 = self._view(_l.BIDIR_WS_DZ0, (T, B, H))
 
-    def prefix(self, T_run):
-        """The same allocation laid out for a shorter run (the layout is monotone in T)."""
-        if T_run >= self.T:
-            return self
-        ws = self._prefixes.get(T_run)
-        if ws is None:
-            if len(self._prefixes) > 64:
-                self._prefixes.clear()
-            ws = BidirWorkspace(T_run, self.B, self.H, self.L, device=self.buf.device, precision=self.precision, _share=self.buf)
-            ws._root = self
-            self._prefixes[T_run] = ws
-        return ws
-
-    def _offset(self, which):
-        p = self.lib.amdspeech_lstm_bidir_ws_ptr(C.byref(self.desc), _p(self.buf), which)
-        if not p:
-            raise _l.AmdSpeechError("lstm_bidir_ws_ptr failed")
-        return (p - self.buf.data_ptr()) // 4
-
-    def _view(self, which, shape):
-        off = self._offset(which)
-        n = 1
-        for s in shape:
-            n *= s
-        return self.buf[off:off + n].view(*shape)
-
-    def set_dropout(self, keep_in, keep_out, seed):
-        self.desc.keep_in, self.desc.keep_out, self.desc.seed = keep_in, keep_out, seed
-
     def path(self):
         """2: both directions of a layer in one persistent launch, 1: one persistent launch per direction, 0: one launch per frame."""
-        rc = self.lib.amdspeech_lstm_bidir_path(C.byref(self.desc))
-        if rc < 0:
-            _l.check(rc, "lstm_bidir_path")
-        return rc
+        return lstm_bidir_plan(self)["path"]
 
     def final_state(self):
         """(h [L,B,H], c [L,B,H]) of the forward cells after the last frame."""
@@ -673,6 +640,17 @@ class BidirWorkspace(object):
 
 def _ptr_array(ts):
     return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def lstm_bidir_plan(ws, per_frame=False):
+    """What lstm_bidir_fwd / lstm_bidir_bwd on this workspace layout launch for the recurrence (amdspeech.h: amdspeech_lstm_bidir_plan),
+    as a dict of ints: path, cus, and kpw / waves / groups / wgs / lds of the forward (fwd_*) and backward (bwd_*) kernel.
+    Read-only: nothing is launched and ws.desc.flags is left alone."""
+    d = _l.LstmDesc(ws.desc.T, ws.desc.B, ws.desc.H, ws.desc.L, ws.desc.keep_in, ws.desc.keep_out, ws.desc.seed, ws.desc.precision,
+                    _l.LSTM_PER_DIAGONAL if per_frame else 0)
+    info = _l.LstmBidirPlanInfo()
+    _l.check(ws.lib.amdspeech_lstm_bidir_plan(C.byref(d), C.byref(info)), "lstm_bidir_plan")
+    return _plan_dict(info)
 
 
 def lstm_bidir_fwd(ws, kernels, biases, lengths, h0=None, c0=None, per_frame=False, inject_timeout=False):

@@ -475,9 +475,9 @@ def whole_errors(got, ref, kind):
     return rel_err(got, ref)
 
 
-# ------------------------------------------------------------------------------------------------ csrc/lstm.hip's rules, mirrored
+# ------------------------------------------------------------------------------------------------ csrc/lstm_bidir.h's rules, mirrored
 def bf3_kpw(nkb, max_waves, max_kpw):
-    """bf3_kpw of csrc/lstm.hip: K blocks of 32 per wave, the smallest instantiated count whose waves take the whole K."""
+    """bf3_pick of csrc/lstm_bidir.h: K blocks of 32 per wave, the smallest instantiated count whose waves take the whole K."""
     kpw = 1
     while kpw <= max_kpw:
         if nkb % kpw == 0 and nkb // kpw <= max_waves:
@@ -487,13 +487,13 @@ def bf3_kpw(nkb, max_waves, max_kpw):
 
 
 def bf3_shape(H):
-    """((forward KPW, waves), (backward KPW, waves)) of the bf16x3 kernels at hidden size H (bf3_launch)."""
+    """((forward KPW, waves), (backward KPW, waves)) of the bf16x3 kernels at hidden size H (bidir_plan)."""
     kf, kb = bf3_kpw(H // 32, 8, 4), bf3_kpw(4 * H // 32, 8, 16)
     return (kf, H // 32 // kf), (kb, 4 * H // 32 // kb)
 
 
 def expected_path(case, cus=256):
-    """bidir_path() of csrc/lstm.hip on a device of `cus` CUs whose CUs each take (at least) one workgroup of every kernel."""
+    """The path of bidir_plan() (csrc/lstm_bidir.h) on a device of `cus` CUs whose CUs each take (at least) one workgroup of every kernel."""
     if "per_frame" in case["extras"]:
         return 0
     if case["precision"] == 1:
@@ -502,6 +502,39 @@ def expected_path(case, cus=256):
     else:
         nwg = case["H"] // 8
     return 2 if 2 * nwg <= cus else (1 if nwg <= cus else 0)
+
+
+PLAN_FIELDS = ("path", "cus", "fwd_kpw", "fwd_waves", "fwd_groups", "fwd_wgs", "fwd_lds", "bwd_kpw", "bwd_waves", "bwd_groups", "bwd_wgs",
+               "bwd_lds")
+
+
+def expected_plan(case, cus=256):
+    """The twelve ints of amdspeech_lstm_bidir_plan on a device of `cus` CUs whose CUs each take (at least) one workgroup of every
+    kernel (cus = 0: no device), from the driver's rules as they stood before the plan existed -- bf3_kpw, bf3_launch, bidir_lds and
+    bidir_path of csrc/lstm.hip then -- written out here, not read back from the library:
+      f32     8 waves, H / 8 workgroups per direction, LDS H x 36 floats forward (the padded slice) and H x 32 backward
+      bf16x3  waves = K blocks / KPW; forward 8 units x groups of 4 row tiles, backward 16 units x groups of 2;
+              LDS = waves x MB x NT KiB with (MB, NT) = (4, 2) forward and (2, 1) backward
+      path    by the larger of the two kernels' workgroups per direction against the CUs; 0 by the flag ("per_frame")"""
+    H, nmt = case["H"], (case["B"] + 15) // 16
+    if case["precision"] == 1:
+        (kf, wf), (kb, wb) = bf3_shape(H)
+        gf, gb = (nmt + 3) // 4, (nmt + 1) // 2
+        fwd = dict(kpw=kf, waves=wf, groups=gf, wgs=H // 8 * gf, lds=wf * 4 * 2 * 1024)
+        bwd = dict(kpw=kb, waves=wb, groups=gb, wgs=H // 16 * gb, lds=wb * 2 * 1 * 1024)
+    else:
+        fwd = dict(kpw=0, waves=8, groups=1, wgs=H // 8, lds=H * 36 * 4)
+        bwd = dict(kpw=0, waves=8, groups=1, wgs=H // 8, lds=H * 32 * 4)
+    nwg = max(fwd["wgs"], bwd["wgs"])
+    path = 0 if "per_frame" in case["extras"] else (2 if 2 * nwg <= cus else (1 if nwg <= cus else 0))
+    plan = dict(path=path, cus=cus)
+    plan.update({"fwd_" + k: v for k, v in fwd.items()})
+    plan.update({"bwd_" + k: v for k, v in bwd.items()})
+    assert tuple(plan) == PLAN_FIELDS
+    return plan
+
+
+WORKLOAD_SHAPES = ((998, 64, 1024, 5), (1001, 32, 512, 3))      # (T, B, H, L) of tools/bidir_layer_bench.py's two shapes
 
 
 # ------------------------------------------------------------------------------------------------ the matrix
@@ -559,12 +592,12 @@ CASES = [
     _case("bf3-saturating", 8, 10, 64, 2, 1, 2, ["bf3:saturating"], regime="saturating"),
 ]
 
-# What the matrix has to reach, each with the rule of csrc/lstm.hip (or of the kernels) it comes from
+# What the matrix has to reach, each with the rule of csrc/lstm_bidir.h (or of the kernels) it comes from
 VARIANTS = {
     "f32:H16": "bidir_check: H a multiple of 16; the smallest: two workgroups per direction, one trip of lstm_layer_fwd's K loop",
     "f32:H48": "a hidden size that is no power of two (six workgroups per direction)",
-    "f32:H1008": "bidir_path: nwg = H / 8 = 126, 2 * 126 <= 256 -> path 2; the largest size below 1024",
-    "f32:H1024": "bidir_lds: the 144 KiB forward slice; 2 * 128 workgroups = every CU",
+    "f32:H1008": "bidir_plan: nwg = H / 8 = 126, 2 * 126 <= 256 -> path 2; the largest size below 1024",
+    "f32:H1024": "bidir_plan: the 144 KiB forward slice; 2 * 128 workgroups = every CU",
     "f32:L3": "bidir_fwd / bidir_bwd: a middle layer reads a 2H-wide input and hands [h_fw ; h_bw] on both ways",
     "f32:B1": "one batch row: 63 of a pass's 64 row slots idle",
     "f32:one-pass": "lstm_layer_fwd / _bwd: for (rb = 0; rb < B; rb += LAYER_ROWS): B = 64 is exactly one pass",
@@ -578,24 +611,24 @@ VARIANTS = {
     "f32:dropout": "layer_mask in bidir_pack_kernel, the recurrence kernels and bidir_split_kernel",
     "f32:accumulate": "bidir_bwd: gemm_f32(..., accumulate, bias gradient) adds to the caller's dK / db",
     "f32:padding": "bidir_pack_kernel / lstm_layer_bwd mask s >= len: what the caller left past the lengths must not matter",
-    "f32:per-frame": "bidir_path: flags & AMDSPEECH_LSTM_PER_DIAGONAL -> 0, one launch per frame",
+    "f32:per-frame": "bidir_plan: flags & AMDSPEECH_LSTM_PER_DIAGONAL -> 0, one launch per frame",
     "f32:saturating": "gates in their tails",
-    "bf3:fwd-kpw1": "bf3_fwd_kpw: H / 32 <= 8 K blocks", "bf3:fwd-kpw2": "bf3_fwd_kpw: 9..16 K blocks, even",
-    "bf3:fwd-kpw4": "bf3_fwd_kpw: 17..32 K blocks, a multiple of 4",
-    "bf3:bwd-kpw1": "bf3_bwd_kpw: 4H / 32 <= 8", "bf3:bwd-kpw2": "bf3_bwd_kpw: <= 16, even", "bf3:bwd-kpw4": "bf3_bwd_kpw: <= 32",
-    "bf3:bwd-kpw8": "bf3_bwd_kpw: <= 64", "bf3:bwd-kpw16": "bf3_bwd_kpw: <= 128",
+    "bf3:fwd-kpw1": "bf3_fwd_kernel: H / 32 <= 8 K blocks", "bf3:fwd-kpw2": "bf3_fwd_kernel: 9..16 K blocks, even",
+    "bf3:fwd-kpw4": "bf3_fwd_kernel: 17..32 K blocks, a multiple of 4",
+    "bf3:bwd-kpw1": "bf3_bwd_kernel: 4H / 32 <= 8", "bf3:bwd-kpw2": "bf3_bwd_kernel: <= 16, even", "bf3:bwd-kpw4": "bf3_bwd_kernel: <= 32",
+    "bf3:bwd-kpw8": "bf3_bwd_kernel: <= 64", "bf3:bwd-kpw16": "bf3_bwd_kernel: <= 128",
     "bf3:waves1": "lbf3_sum over one wave (H = 32 forward)", "bf3:waves3": "three forward waves (H = 96)",
     "bf3:waves5": "five waves (H = 160 both kernels, H = 320 both kernels)", "bf3:waves6": "six waves (H = 96 backward, H = 768 both)",
     "bf3:waves7": "seven waves (H = 224 both kernels)", "bf3:waves8": "eight waves (H = 1024 both kernels)",
     "bf3:H1024": "the largest size: KPW 4 / 16",
     "bf3:B1": "one row of one tile", "bf3:B16": "exactly one 16-row tile", "bf3:B17": "a second tile of one row: mv < MB in both kernels",
-    "bf3:B33": "bf3_launch: backward ngrp = 2, its second group holds one tile",
-    "bf3:B65": "bf3_launch: forward ngrp = 2 (a fifth tile), backward ngrp = 3",
-    "bf3:path1": "bidir_path: nwg = 1024 / 8 * 2 = 256: 2 * nwg > 256 CUs >= nwg -> one persistent launch per direction",
-    "bf3:path0-by-plan": "bidir_path: nwg = 1024 / 8 * 3 = 384 > 256 CUs -> one launch per frame, chosen by the plan",
+    "bf3:B33": "bidir_plan: backward ngrp = 2, its second group holds one tile",
+    "bf3:B65": "bidir_plan: forward ngrp = 2 (a fifth tile), backward ngrp = 3",
+    "bf3:path1": "bidir_plan: nwg = 1024 / 8 * 2 = 256: 2 * nwg > 256 CUs >= nwg -> one persistent launch per direction",
+    "bf3:path0-by-plan": "bidir_plan: nwg = 1024 / 8 * 3 = 384 > 256 CUs -> one launch per frame, chosen by the plan",
     "bf3:state": "pack_rows_bf3_kernel: the initial h, split, into ring slot 0", "bf3:dropout": "layer_mask in the bf16x3 kernels",
     "bf3:accumulate": "bidir_bwd: gemm_reduced(..., accumulate) and colsum_accumulate", "bf3:padding": "as f32:padding",
-    "bf3:per-frame": "bidir_path: the flag, on the bf16x3 kernels (each launch splits its W_hh slice again)",
+    "bf3:per-frame": "bidir_plan: the flag, on the bf16x3 kernels (each launch splits its W_hh slice again)",
     "bf3:saturating": "gates in their tails",
 }
 

@@ -1,8 +1,11 @@
 """tests/bidir_layer_ref.py's per-call reference tied down without a GPU: against torch.nn.LSTM(bidirectional=True) with an initial
 state, its hand-written backward pass against autograd of bidir_layer_ref.forward, the slice metric against the whole-tensor metric
-it replaces, and the conditions the GPU matrix (tests/test_gpu_bidir_layer_paths.py) puts on its cases and its recorded table."""
+it replaces, and the conditions the GPU matrix (tests/test_gpu_bidir_layer_paths.py) puts on its cases and its recorded table.  At
+the end: the library's exported plan (amdspeech_lstm_bidir_plan, host only) against bidir_layer_ref.expected_plan."""
+import ctypes
 import os
 import sys
+import types
 
 import numpy as np
 import pytest
@@ -295,3 +298,89 @@ def test_slices_tile_every_tensor_exactly_once():
     info0 = dict(info, B=36, lengths=np.array([3] * 16 + [0] * 16 + [2] * 4, np.int32))
     assert not [s for s in R.slices("y", info0) if "rows 16:32" in s[0]] and not [s for s in R.slices("hT", info0) if "rows 16:32" in s[0]]
     assert [s for s in R.slices("hT", dict(info0, state=True)) if "rows 16:32" in s[0]]
+
+
+# ------------------------------------------------------------------------------------------------ the exported plan
+# amdspeech_lstm_bidir_plan runs on the host: everything but `path` and `cus` is the device's business on no device.  The cases of the
+# matrix, and the two shapes of tools/bidir_layer_bench.py at both precisions.
+_WORKLOAD = [dict(name="workload-T%d-B%d-H%d-L%d-p%d" % (s + (p,)), T=s[0], B=s[1], H=s[2], L=s[3], precision=p, extras=())
+             for s in R.WORKLOAD_SHAPES for p in (0, 1)]
+_PLAN_CASES = R.CASES + _WORKLOAD
+EINVAL, EUNSUPPORTED = -1, -3      # include/amdspeech.h
+
+
+def _lib():
+    from rnn_speech_amd import lib as _l
+    return _l, _l.load()
+
+
+def _desc(case, flags=0, **over):
+    c = dict(case, **over)
+    return _lib()[0].LstmDesc(c["T"], c["B"], c["H"], c["L"], 1.0, 1.0, 0, c["precision"], flags)
+
+
+def _plan(case, per_frame=False):
+    from rnn_speech_amd import ops
+    return ops.lstm_bidir_plan(types.SimpleNamespace(lib=_lib()[1], desc=_desc(case)), per_frame=per_frame)
+
+
+def test_expected_plan_takes_over_expected_path():
+    for c in R.CASES:
+        assert R.expected_plan(c)["path"] == R.expected_path(c) == c["path"], c["name"]
+        assert R.expected_plan(c, cus=0)["path"] == 0
+
+
+def test_bidir_plan_struct_layout_and_wrapper():
+    _l, handle = _lib()
+    names = [n for n, _ in _l.LstmBidirPlanInfo._fields_]
+    assert tuple(names) == R.PLAN_FIELDS
+    assert ctypes.sizeof(_l.LstmBidirPlanInfo) == 4 * 12
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "amdspeech.h")).read()
+    decl = header.split("typedef struct amdspeech_lstm_bidir_plan_info {")[1].split("}")[0]
+    assert [w.strip() for w in decl.replace("int ", "").replace(";", "").split(",")] == names
+    # the call writes its twelve ints and nothing past them
+    buf = (ctypes.c_int * 16)(*([-7] * 16))
+    d = _desc(R.CASES[0])
+    assert handle.amdspeech_lstm_bidir_plan(ctypes.byref(d), ctypes.cast(buf, ctypes.POINTER(_l.LstmBidirPlanInfo))) == 0
+    assert list(buf[12:]) == [-7] * 4 and -7 not in list(buf[:12])
+    # the wrapper is read-only: the workspace's own flags stay as they were
+    from rnn_speech_amd import ops
+    ws = types.SimpleNamespace(lib=handle, desc=_desc(R.CASES[0], flags=_l.LSTM_INJECT_TIMEOUT))
+    assert ops.lstm_bidir_plan(ws, per_frame=True)["path"] == 0 and ws.desc.flags == _l.LSTM_INJECT_TIMEOUT
+
+
+@pytest.mark.parametrize("case", _PLAN_CASES, ids=[c["name"] for c in _PLAN_CASES])
+def test_bidir_plan_is_what_the_mirror_expects(case):
+    _l, handle = _lib()
+    got, want = _plan(case), R.expected_plan(case, cus=0)
+    assert tuple(got) == R.PLAN_FIELDS
+    for name in R.PLAN_FIELDS[2:]:
+        assert got[name] == want[name], (case["name"], name, got, want)
+    if not torch.cuda.is_available():      # (with a device the path and the CUs are its own: tests/test_gpu_bidir_layer_paths.py)
+        assert (got["path"], got["cus"]) == (0, 0)
+    flagged = _plan(case, per_frame=True)
+    assert flagged["path"] == 0 and {k: v for k, v in flagged.items() if k != "path"} == {k: v for k, v in got.items() if k != "path"}
+    for flags, plan in ((0, got), (_l.LSTM_PER_DIAGONAL, flagged)):
+        assert handle.amdspeech_lstm_bidir_path(ctypes.byref(_desc(case, flags))) == plan["path"]
+
+
+def test_bidir_plan_refuses_what_the_calls_refuse_in_their_words():
+    _l, handle = _lib()
+    info = _l.LstmBidirPlanInfo()
+    base = R.CASES[0]
+
+    def refused(d, out=info):
+        rc = handle.amdspeech_lstm_bidir_plan(ctypes.byref(d), ctypes.byref(out) if out is not None else None)
+        return rc, handle.amdspeech_last_error().decode()
+
+    assert refused(_desc(base, precision=2, H=64)) == (EUNSUPPORTED, "lstm_bidir: the layer-wise bidirectional mode runs in exact f32 "
+                                                       "(precision 0) or bf16x3 (1), not plain bf16 (2)")
+    assert refused(_desc(base, H=1040)) == (EUNSUPPORTED, "lstm_bidir: hidden size 1040 above 1024 (the recurrence keeps H x 32 floats of "
+                                            "W_hh per workgroup in LDS)")
+    assert refused(_desc(base, precision=1, H=288)) == (
+        EUNSUPPORTED, "lstm_bidir: bf16x3 does not take hidden size 288: its kernels split the H (forward) and 4H (backward) rows of W_hh "
+                      "over at most 8 waves, 32 x 1, 2, 4, 8 or 16 rows each (H = 64, 128, 256, 512, 768, 1024 qualify)")
+    assert handle.amdspeech_lstm_bidir_plan(ctypes.byref(_desc(base, H=288)), ctypes.byref(info)) == 0      # (exact f32 takes it)
+    assert refused(_desc(base), out=None) == (EINVAL, "lstm_bidir_plan: null output")
+    # ... and amdspeech_lstm_bidir_path answers the same status
+    assert handle.amdspeech_lstm_bidir_path(ctypes.byref(_desc(base, precision=2, H=64))) == EUNSUPPORTED

@@ -1,9 +1,10 @@
 """ops.lstm_bidir_fwd / ops.lstm_bidir_bwd on their own -- no Engine, no Linear layers, no CTC -- against the float64 reference of
-tests/bidir_layer_ref.py, one case per kernel variant, launch path and edge of csrc/lstm.hip's layer-wise bidirectional driver,
+tests/bidir_layer_ref.py, one case per kernel variant, launch path and edge of the layer-wise bidirectional driver (csrc/lstm_bidir.h),
 judged slice by slice (layer, direction, gate block, 16 batch rows, 16 hidden units, third of the frames, x / h rows of a kernel
 gradient) so that a wrong tile cannot hide behind a tensor's largest entry.
 
-Every case names the launch path it expects on an MI355X (amdspeech_lstm_bidir_path); the path is asserted BEFORE anything runs.
+Every case names the launch path it expects on an MI355X; that path and the whole plan of the call (amdspeech_lstm_bidir_plan against
+bidir_layer_ref.expected_plan: kernel variant and launch geometry of both passes) are asserted BEFORE anything runs.
 Bounds: bidir_layer_ref.bound() -- 8 x the error the same arithmetic shows on the CPU against float64, never looser than the suite's
 whole-tensor tolerances applied per slice; nothing in this file is derived from what the kernels return."""
 import os
@@ -21,11 +22,21 @@ LAUNCHES = {2: "one persistent launch for both directions", 1: "one persistent l
 
 
 def _assert_path(case, ws):
-    got, want = ws.path(), case["path"]
+    """The library's plan for the case (amdspeech_lstm_bidir_plan) is the mirror's, field by field -- kernel variant, waves, row
+    groups, workgroups and LDS of both passes, on 256 CUs -- so what `covers` names is what runs; nothing is launched here."""
+    from rnn_speech_amd import ops
+    plan, got, want = ops.lstm_bidir_plan(ws), ws.path(), case["path"]
+    assert plan["path"] == got and plan["cus"] == 256, plan
     if "per_frame" in case["extras"]:
-        return got      # (the flag, not the plan, sends this case to the per-frame launches; what the plan says is reported)
+        # (the flag, not the plan, sends this case to the per-frame launches: without it the plan is that of the bare shape, and what
+        #  it says is reported)
+        flagged, bare = ops.lstm_bidir_plan(ws, per_frame=True), dict(case, extras=())
+        assert flagged["path"] == 0 and flagged == R.expected_plan(case), (case["name"], flagged, R.expected_plan(case))
+        assert plan == R.expected_plan(bare), (case["name"], plan, R.expected_plan(bare))
+        return got
     assert got == want, ("case %s was written for %s (path %d); amdspeech_lstm_bidir_path now answers %d (%s) -- that variant has lost "
                          "its case: give it another shape" % (case["name"], LAUNCHES[want], want, got, LAUNCHES.get(got, "?")))
+    assert plan == R.expected_plan(case), (case["name"], plan, R.expected_plan(case))
     return got
 
 
