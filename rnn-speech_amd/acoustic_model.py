@@ -17,6 +17,7 @@ import collections
 import numpy as np
 import torch
 
+from . import checkpoint
 from . import dataparallel
 from . import labels as _labels
 from . import ops
@@ -38,14 +39,6 @@ class Session(object):
 
     def __exit__(self, *exc):
         return False
-
-
-class _Variable(object):
-    def __init__(self, value):
-        self.value = value
-
-    def eval(self, session=None):
-        return self.value
 
 
 def _truth_rows(dense, num_labels):
@@ -181,7 +174,7 @@ class _AsyncBeamDecoder(object):
         self._pool.shutdown(wait=True)
 
 
-class AcousticModel(object):
+class AcousticModel(checkpoint.TrainedModel):
     def __init__(self, num_layers, hidden_size, batch_size, max_input_seq_length,
                  max_target_seq_length, input_dim, normalization, num_labels):
         self.num_layers = num_layers
@@ -192,15 +185,8 @@ class AcousticModel(object):
         self.input_dim = input_dim
         self.normalization = normalization
         self.num_labels = num_labels
-        self.engine = None
-        self.rnn_created = False
+        checkpoint.TrainedModel.__init__(self)
         self.forward_only = True
-        self.input_keep_prob = self.output_keep_prob = 1.0
-        self.grad_clip = 1.0
-        self.lr_decay_factor = 1.0
-        self.learning_rate_var = _Variable(0.0)
-        self.learning_rate_decay_op = self._decay_lr
-        self.global_step = _Variable(0)
         self.is_training = False
         self.tensorboard_dir = None
         self.timeline_enabled = False
@@ -276,15 +262,8 @@ class AcousticModel(object):
                             lr_decay_factor, use_iterator=False):
         self._make_engine()
         self.forward_only = False
-        self.input_keep_prob, self.output_keep_prob = float(input_keep_prob), float(output_keep_prob)
-        self.grad_clip = float(grad_clip)
-        self.lr_decay_factor = float(lr_decay_factor)
-        self.learning_rate_var.value = float(learning_rate)
+        self._set_training(input_keep_prob, output_keep_prob, grad_clip, learning_rate, lr_decay_factor)
         self.use_iterator = use_iterator
-
-    def _decay_lr(self):
-        self.learning_rate_var.value *= self.lr_decay_factor
-        return self.learning_rate_var.value
 
     def add_tensorboard(self, session, tensorboard_dir, tb_run_name=None, timeline_enabled=False):
         """TensorBoard summaries are out of scope; with `timeline_enabled` (stt.py --timeline) the directory receives the
@@ -312,12 +291,6 @@ class AcousticModel(object):
         with open(path, "w") as f:
             json.dump({"traceEvents": events, "displayTimeUnit": "ms"}, f)
 
-    def get_learning_rate(self):
-        return self.learning_rate_var.value
-
-    def set_learning_rate(self, sess, learning_rate):
-        self.learning_rate_var.value = float(learning_rate)
-
     def set_is_training(self, sess, is_training):
         self.is_training = bool(is_training)
 
@@ -326,50 +299,27 @@ class AcousticModel(object):
         return None   # parameters are initialised when the engine is built
 
     # ---- checkpoints -------------------------------------------------------------
-    _TF_NAMES = {"input_w": "Input_Layer/input_w", "input_b": "Input_Layer/input_b",
-                 "output_w": "Output_layer/output_w", "output_b": "Output_layer/output_b"}
+    _TF_NAMES = checkpoint.TF_NAMES
 
     def _tf_name(self, name):
-        if name in self._TF_NAMES:
-            return self._TF_NAMES[name]
-        if getattr(self.engine, "layerwise", False) and name.split("_")[-2] in ("kernel", "bias"):
-            # layer-wise bidirectional stacks: tf.contrib.rnn.stack_bidirectional_dynamic_rnn's scope names
-            d = "bw" if name.startswith("bw_") else "fw"
-            kind, l = name[3:].split("_") if d == "bw" else name.split("_")
-            return "stack_bidirectional_rnn/cell_%s/bidirectional_rnn/%s/basic_lstm_cell/%s" % (l, d, kind)
-        if name.startswith("bw_"):       # (bidirectional build only: tf.nn.bidirectional_dynamic_rnn's scope names)
-            kind, l = name[3:].split("_")
-            return "bidirectional_rnn/bw/multi_rnn_cell/cell_%s/basic_lstm_cell/%s" % (l, kind)
-        kind, l = name.split("_")
-        return "rnn/multi_rnn_cell/cell_%s/basic_lstm_cell/%s" % (l, kind)
+        return checkpoint.tf_name(name, getattr(self.engine, "layerwise", False))
 
     def save(self, session, checkpoint_dir):
-        """The reference's Saver writes weights, biases, global_step and learning_rate (:518-522) -- no Adam slots,
-        no RNN state, so its resumed runs restart Adam cold.  The native .npz keeps those names (a reference
-        checkpoint maps 1:1) and ADDS the optimiser moments, the Adam step count and the persistent RNN state under
-        `adam/...` / `rnn_state/...` keys.  Data parallel: rank 0 writes, everybody waits."""
+        """The native .npz of checkpoint.py under the reference's file stem, with the persistent RNN state beside the optimiser's
+        (`rnn_state/h|c`; neither with save_optimizer_state off), the `checkpoint` marker file and, on request, the TensorFlow
+        bundle.  Data parallel: rank 0 writes, everybody waits."""
         grp = dataparallel.current()
         if grp.rank == 0:
             os.makedirs(checkpoint_dir, exist_ok=True)
             eng = self.engine
-            arrays = {self._tf_name(k): v for k, v in eng.to_numpy().items()}
-            arrays["global_step"] = np.int32(self.global_step.value)
-            arrays["learning_rate"] = np.float32(self.learning_rate_var.value)
             stem = "acousticmodel.ckpt-%d" % self.global_step.value
-            extra = {}
-            if self.save_optimizer_state:
-                for slot, flat in (("m", eng.adam_m), ("v", eng.adam_v)):
-                    for k, v in eng.to_numpy(flat).items():
-                        extra["adam/%s/%s" % (slot, self._tf_name(k))] = v
-                extra["adam/step"] = np.int64(eng.adam_step)
-                extra["rnn_state/h"] = eng.state_h.cpu().numpy()
-                extra["rnn_state/c"] = eng.state_c.cpu().numpy()
-            tmp = os.path.join(checkpoint_dir, stem + ".tmp.npz")
-            np.savez(tmp, **arrays, **extra)
-            os.replace(tmp, os.path.join(checkpoint_dir, stem + ".npz"))      # never a half-written checkpoint
+            model = (eng, self.global_step.value, self.learning_rate_var.value, getattr(eng, "layerwise", False))
+            state = {"rnn_state/h": eng.state_h.cpu().numpy(), "rnn_state/c": eng.state_c.cpu().numpy()} if self.save_optimizer_state else None
+            checkpoint.write(os.path.join(checkpoint_dir, stem + ".npz"),
+                             checkpoint.pack(*model, optimizer=self.save_optimizer_state, extra=state))
             if self.save_tf_bundle:      # additionally the TensorFlow bundle a reference tf.train.Saver can restore
                 from . import tf_bundle
-                tf_bundle.write_bundle(os.path.join(checkpoint_dir, stem), arrays)
+                tf_bundle.write_bundle(os.path.join(checkpoint_dir, stem), checkpoint.pack(*model, optimizer=False))
             with open(os.path.join(checkpoint_dir, "checkpoint"), "w") as fh:
                 fh.write('model_checkpoint_path: "%s"\n' % stem)
             logging.info("Checkpoint saved")
@@ -397,20 +347,11 @@ class AcousticModel(object):
                 else:                        # a TensorFlow bundle written by the reference (:483-487)
                     from . import tf_bundle
                     z = tf_bundle.read_bundle(os.path.join(checkpoint_dir, stem))
-                names = eng.layout.names()
-                eng.load_numpy({k: z[self._tf_name(k)] for k in names})
-                self.global_step.value = int(z["global_step"])
-                self.learning_rate_var.value = float(z["learning_rate"])
-                keys = set(z.keys()) if hasattr(z, "keys") else set(z)
-                if "adam/step" in keys:      # native checkpoint: resume the optimiser warm
-                    eng.load_numpy({k: z["adam/m/" + self._tf_name(k)] for k in names}, flat=eng.adam_m)
-                    eng.load_numpy({k: z["adam/v/" + self._tf_name(k)] for k in names}, flat=eng.adam_v)
-                    eng.adam_step = int(z["adam/step"])
-                    if tuple(z["rnn_state/h"].shape) == tuple(eng.state_h.shape):      # (batch size may have changed)
-                        eng.state_h.copy_(torch.as_tensor(z["rnn_state/h"]))
-                        eng.state_c.copy_(torch.as_tensor(z["rnn_state/c"]))
-                else:                        # reference-style checkpoint: Adam restarts cold, like the reference
-                    eng.adam_m.zero_(); eng.adam_v.zero_(); eng.adam_step = 0
+                self.global_step.value, self.learning_rate_var.value, native = checkpoint.unpack(
+                    z, eng, getattr(eng, "layerwise", False))
+                if native and tuple(z["rnn_state/h"].shape) == tuple(eng.state_h.shape):      # (batch size may have changed)
+                    eng.state_h.copy_(torch.as_tensor(z["rnn_state/h"]))
+                    eng.state_c.copy_(torch.as_tensor(z["rnn_state/c"]))
             except Exception as exc:      # missing / corrupt file, key or shape mismatch ...
                 failure = "%s: %s" % (type(exc).__name__, exc)
         # the other ranks are about to park in a broadcast: they must hear about a failed read FIRST, or the job hangs

@@ -99,7 +99,81 @@ _FUSED_CTC = os.environ.get("AMDSPEECH_FUSED_CTC", "1") != "0"                # 
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16": 2}
 
 
-class Engine(object):
+class ParamStore(object):
+    """Everything that hangs off a ParamLayout and a device, for every model: the flat fp32 parameter / gradient / Adam buffers,
+    views and host copies by tensor name, Glorot initialisation, the optimiser step, and the health predicate and run-length clamp
+    of the engines built on it.  A subclass sets T (its padded length), says what it is in _describe() and implements check()."""
+
+    def __init__(self, layout, device):
+        self.layout, self.device = layout, torch.device(device)
+        self.params, self.grads, self.adam_m, self.adam_v = (torch.zeros(layout.total, device=self.device) for _ in range(4))
+        self.norm = torch.zeros(1, device=self.device)
+        self.adam_step = 0
+
+    def p(self, name):
+        return self.layout.view(self.params, name)
+
+    def g(self, name):
+        return self.layout.view(self.grads, name)
+
+    def init_parameters(self, seed=1234):
+        """Xavier/Glorot-uniform matrices, zero biases (TF defaults, :241-244,302-305)."""
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed(seed)
+        self.params.zero_()
+        for name in self.layout.names():
+            _, shape = self.layout.slots[name]
+            if len(shape) == 2:
+                lim = math.sqrt(6.0 / (shape[0] + shape[1]))
+                w = (torch.rand(shape, generator=gen) * 2.0 - 1.0) * lim
+                self.p(name).copy_(w)
+
+    def load_numpy(self, arrays, flat=None):
+        """Copy host arrays into the flat buffer (default: the parameters).  Shapes must match the layout exactly:
+        copy_ would silently broadcast e.g. a shape-(1,) bias from a checkpoint of another model size."""
+        flat = self.params if flat is None else flat
+        for name, a in arrays.items():
+            if name not in self.layout.slots:
+                raise KeyError("unknown parameter tensor %r (layout has %s)" % (name, ", ".join(self.layout.names())))
+            want = tuple(self.layout.slots[name][1])
+            got = tuple(np.shape(a))
+            if got != want:
+                raise ValueError("checkpoint tensor %s has shape %s, %s needs %s" % (name, got, self._describe(), want))
+            self.layout.view(flat, name).copy_(torch.as_tensor(np.asarray(a), dtype=torch.float32))
+
+    def to_numpy(self, flat=None):
+        flat = self.params if flat is None else flat
+        return {n: self.layout.view(flat, n).detach().cpu().numpy().copy() for n in self.layout.names()}
+
+    def zero_grads(self):
+        self.grads.zero_()
+
+    def apply(self, lr, clip, beta1=0.9, beta2=0.999, eps=1e-8):
+        self.adam_step += 1
+        t = self.adam_step
+        lr_t = lr * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
+        ops.clip_adam(self.params, self.grads, self.adam_m, self.adam_v, float(clip), lr_t, beta1, beta2, eps,
+                      norm_out=self.norm)
+        return self.norm
+
+    def healthy(self):
+        """check() as a predicate: False when a dataflow launch of the last mini-batch gave up waiting (its results -- logits, loss,
+        the gradient contribution, the final state -- are invalid; see mini_batch(per_diagonal=True) for the way out).  Only the
+        time-out is recoverable: any other error of the status call (a sticky HIP fault) is raised, not turned into a retry."""
+        try:
+            self.check()
+            return True
+        except _lib.DataflowTimeout:
+            return False
+
+    def _run_length(self, max_len):
+        """Steps the recurrence has to visit: the longest row of this batch when the host knows it (`max_len`, from the dataset
+        pipeline -- no device sync), else the padded length.  Mirrors tf.nn.dynamic_rnn, whose while-loop runs to
+        max(sequence_length) (reference :276-278)."""
+        return self.T if max_len is None else max(1, min(int(max_len), self.T))
+
+
+class Engine(ParamStore):
     def __init__(self, num_layers, hidden, input_dim, num_labels, batch_size, max_T, max_U,
                  device="cuda", seed=1234, normalization=False, precision="f32", bidirectional=False,
                  sync_batch_norm=False, bidirectional_mode="top"):
@@ -107,7 +181,6 @@ class Engine(object):
             raise RuntimeError("rnn_speech_amd needs a ROCm GPU (MI355X); there is no CPU path")
         self.L, self.H, self.D, self.C = num_layers, hidden, input_dim, num_labels
         self.B, self.T, self.U = batch_size, max_T, max_U
-        self.device = torch.device(device)
         # bidirectional (BASELINE configs[4]; no reference counterpart -- the reference builds a unidirectional dynamic_rnn,
         # :276-278): a second stack of the same shape reads every utterance reversed in time (tf.reverse_sequence semantics,
         # as tf.nn.bidirectional_dynamic_rnn does), the two top outputs are concatenated in front of the output layer
@@ -120,15 +193,8 @@ class Engine(object):
         if self.layerwise and precision not in ("f32", "bf16x3"):
             raise ValueError("bidirectional_mode 'layer' runs in exact f32 or bf16x3 (precision %r requested): the layer-wise kernels "
                              "have no plain-bf16 variant" % (precision,))
-        self.layout = ParamLayout(num_layers, hidden, input_dim, num_labels, bidirectional=self.bidirectional,
-                                  bidirectional_mode="layer" if self.layerwise else "top")
-        n = self.layout.total
-        self.params = torch.zeros(n, device=self.device)
-        self.grads = torch.zeros(n, device=self.device)
-        self.adam_m = torch.zeros(n, device=self.device)
-        self.adam_v = torch.zeros(n, device=self.device)
-        self.norm = torch.zeros(1, device=self.device)
-        self.adam_step = 0
+        ParamStore.__init__(self, ParamLayout(num_layers, hidden, input_dim, num_labels, bidirectional=self.bidirectional,
+                                              bidirectional_mode="layer" if self.layerwise else "top"), device)
         if precision not in PRECISIONS:
             raise ValueError("precision must be 'f32' (exact, default), 'bf16x3' (split-precision MFMA) or 'bf16' (plain bf16 "
                              "operands, f32 accumulation and master weights)")
@@ -171,42 +237,8 @@ class Engine(object):
         self._tail_stream = None         # (backward: the dense layers' weight gradients beside the LSTM's)
         self.init_parameters(seed)
 
-    # ---- parameters ------------------------------------------------------------
-    def p(self, name):
-        return self.layout.view(self.params, name)
-
-    def g(self, name):
-        return self.layout.view(self.grads, name)
-
-    def init_parameters(self, seed=1234):
-        """Xavier/Glorot-uniform matrices, zero biases (TF defaults, :241-244,302-305)."""
-        gen = torch.Generator(device="cpu")
-        gen.manual_seed(seed)
-        self.params.zero_()
-        for name in self.layout.names():
-            _, shape = self.layout.slots[name]
-            if len(shape) == 2:
-                lim = math.sqrt(6.0 / (shape[0] + shape[1]))
-                w = (torch.rand(shape, generator=gen) * 2.0 - 1.0) * lim
-                self.p(name).copy_(w)
-
-    def load_numpy(self, arrays, flat=None):
-        """Copy host arrays into the flat buffer (default: the parameters).  Shapes must match the layout exactly:
-        copy_ would silently broadcast e.g. a shape-(1,) bias from a checkpoint of another model size."""
-        flat = self.params if flat is None else flat
-        for name, a in arrays.items():
-            if name not in self.layout.slots:
-                raise KeyError("unknown parameter tensor %r (layout has %s)" % (name, ", ".join(self.layout.names())))
-            want = tuple(self.layout.slots[name][1])
-            got = tuple(np.shape(a))
-            if got != want:
-                raise ValueError("checkpoint tensor %s has shape %s, the model (L=%d, H=%d, D=%d, C=%d) needs %s"
-                                 % (name, got, self.L, self.H, self.D, self.C, want))
-            self.layout.view(flat, name).copy_(torch.as_tensor(np.asarray(a), dtype=torch.float32))
-
-    def to_numpy(self, flat=None):
-        flat = self.params if flat is None else flat
-        return {n: self.layout.view(flat, n).detach().cpu().numpy().copy() for n in self.layout.names()}
+    def _describe(self):
+        return "the model (L=%d, H=%d, D=%d, C=%d)" % (self.L, self.H, self.D, self.C)
 
     @staticmethod
     def _dp_group():
@@ -215,14 +247,10 @@ class Engine(object):
 
     # ---- one mini-batch ----------------------------------------------------------
     def _run_length(self, max_len):
-        """Frames the recurrence has to visit: the longest utterance of this batch when the host knows it
-        (`max_len`, from the dataset pipeline -- no device sync), else the padded length.  Mirrors
-        tf.nn.dynamic_rnn, whose while-loop runs to max(sequence_length) (reference :276-278)."""
-        if max_len is None:
-            return self.T
-        if self.sync_batch_norm and self._dp_group().world > 1:
+        """Frames the recurrence has to visit: ParamStore's clamp to the longest utterance, with one exception."""
+        if max_len is not None and self.sync_batch_norm and self._dp_group().world > 1:
             return self.T          # the batch moments span the ranks: every rank contributes all T frames (padding included)
-        return max(1, min(int(max_len), self.T))
+        return ParamStore._run_length(self, max_len)
 
     def forward(self, x, lengths, keep_in=1.0, keep_out=1.0, seed=0, use_state=False, max_len=None, after_lstm=None, training=False,
                 per_diagonal=False, dense_labels=None):
@@ -490,26 +518,20 @@ class Engine(object):
     def check(self):
         """Synchronous health check of the dataflow LSTM kernels: their waits are bounded, and a time-out (the
         workgroups of one launch were not all resident -- another kernel held CUs) leaves an error flag behind
-        instead of hanging.  Raises AmdSpeechError; results of that step are invalid."""
+        instead of hanging.  Raises AmdSpeechError; results of that step are invalid.  Two stacks: BOTH workspaces are asked
+        before anything is raised (the status call is what makes a workspace distrust the hand-off state an incomplete launch
+        left behind), and a fault that is no time-out goes first: it must not hide behind a recoverable one."""
         if self.layerwise:
             ops.lstm_bidir_status(self._ws)
             return
-        ops.lstm_status(self._ws)
-        if self.bidirectional:
-            ops.lstm_status(self._ws_b)
-
-    def healthy(self):
-        """check() as a predicate: False when a dataflow launch of the last mini-batch gave up waiting (its results -- logits, loss,
-        the gradient contribution, the final state -- are invalid; see mini_batch(per_diagonal=True) for the way out).  Only the
-        time-out is recoverable: any other error of the status call (a sticky HIP fault) is raised, not turned into a retry."""
-        try:
-            self.check()
-            return True
-        except _lib.DataflowTimeout:
-            return False
-
-    def zero_grads(self):
-        self.grads.zero_()
+        errors = []
+        for ws in (self._ws, self._ws_b) if self.bidirectional else (self._ws,):
+            try:
+                ops.lstm_status(ws)
+            except _lib.AmdSpeechError as exc:
+                errors.append(exc)
+        if errors:
+            raise next((e for e in errors if not isinstance(e, _lib.DataflowTimeout)), errors[0])
 
     def mini_batch(self, x, lengths, dense_labels, keep_in=1.0, keep_out=1.0, seed=0, use_state=False,
                    compute_gradients=True, max_len=None, beside_ctc=None, marks=None, beside_forward=None, per_diagonal=False):
@@ -596,7 +618,7 @@ class Engine(object):
             cur.wait_event(done)      # the next recurrence kernel must not start beside it
         return self.loss
 
-    # ---- optimiser step ------------------------------------------------------------
+    # ---- data parallel (the optimiser step itself is ParamStore.apply) ----------------
     def all_reduce_grads(self):
         """Data parallel: ONE fused fp32 SUM all-reduce of the flat gradient buffer (amdspeech_allreduce_sum_f32 =
         RCCL over xGMI, see dataparallel.py); N ranks x batch b is then the reference's mini_batch_size=N
@@ -611,11 +633,3 @@ class Engine(object):
         for flat in (self.params, self.adam_m, self.adam_v):
             grp.broadcast_(flat, root)
         self.adam_step = int(grp.broadcast_object(self.adam_step, root))
-
-    def apply(self, lr, clip, beta1=0.9, beta2=0.999, eps=1e-8):
-        self.adam_step += 1
-        t = self.adam_step
-        lr_t = lr * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
-        ops.clip_adam(self.params, self.grads, self.adam_m, self.adam_v, float(clip), lr_t, beta1, beta2, eps,
-                      norm_out=self.norm)
-        return self.norm

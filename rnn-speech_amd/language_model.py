@@ -12,20 +12,20 @@ log-softmax -> NLL.  Parameter names and the flat layout are engine.ParamLayout(
 with one-hot input.  Everything numeric is a libamdspeech call; there is no torch compute and no CPU path.
 """
 import logging
-import math
 import os
 
 import numpy as np
 import torch
 
+from . import checkpoint
 from . import labels as _labels
-from . import lib as _lib
 from . import ops
-from .engine import PRECISIONS, ParamLayout
+from .engine import PRECISIONS, ParamLayout, ParamStore
 
 
-class LmEngine(object):
-    """Flat parameter / gradient / Adam buffers and the op sequence of one language-model mini-batch and one optimiser step."""
+class LmEngine(ParamStore):
+    """The op sequence of one language-model mini-batch on the parameter store of the acoustic engine (engine.ParamStore: flat
+    parameter / gradient / Adam buffers, the optimiser step, healthy())."""
 
     def __init__(self, num_layers, hidden, num_labels, batch_size, max_len, precision="f32", seed=1234, device="cuda"):
         if not torch.cuda.is_available():
@@ -34,16 +34,8 @@ class LmEngine(object):
             raise ValueError("precision must be one of %s" % ", ".join(sorted(PRECISIONS)))
         self.L, self.H, self.V = num_layers, hidden, num_labels
         self.B, self.T = batch_size, max_len
-        self.device = torch.device(device)
         self.precision = precision
-        self.layout = ParamLayout(num_layers, hidden, num_labels, num_labels)
-        n = self.layout.total
-        self.params = torch.zeros(n, device=self.device)
-        self.grads = torch.zeros(n, device=self.device)
-        self.adam_m = torch.zeros(n, device=self.device)
-        self.adam_v = torch.zeros(n, device=self.device)
-        self.norm = torch.zeros(1, device=self.device)
-        self.adam_step = 0
+        ParamStore.__init__(self, ParamLayout(num_layers, hidden, num_labels, num_labels), device)
         self.lstm_ws = ops.LstmWorkspace(max_len, batch_size, hidden, num_layers, device=self.device, precision=PRECISIONS[precision])
         self.logits = torch.empty(max_len, batch_size, num_labels, device=self.device)
         self.dlogits = torch.empty_like(self.logits)
@@ -52,47 +44,10 @@ class LmEngine(object):
         self._ws, self._Tr, self._per_diagonal = self.lstm_ws, max_len, False
         self.init_parameters(seed)
 
-    # ---- parameters (the acoustic engine's conventions) ------------------------------
-    def p(self, name):
-        return self.layout.view(self.params, name)
-
-    def g(self, name):
-        return self.layout.view(self.grads, name)
-
-    def init_parameters(self, seed=1234):
-        """Xavier/Glorot-uniform matrices, zero biases (the TF defaults of the reference graph)."""
-        gen = torch.Generator(device="cpu")
-        gen.manual_seed(seed)
-        self.params.zero_()
-        for name in self.layout.names():
-            _, shape = self.layout.slots[name]
-            if len(shape) == 2:
-                lim = math.sqrt(6.0 / (shape[0] + shape[1]))
-                self.p(name).copy_((torch.rand(shape, generator=gen) * 2.0 - 1.0) * lim)
-
-    def load_numpy(self, arrays, flat=None):
-        flat = self.params if flat is None else flat
-        for name, a in arrays.items():
-            want, got = tuple(self.layout.slots[name][1]), tuple(np.shape(a))
-            if got != want:
-                raise ValueError("checkpoint tensor %s has shape %s, the language model (L=%d, H=%d, V=%d) needs %s"
-                                 % (name, got, self.L, self.H, self.V, want))
-            self.layout.view(flat, name).copy_(torch.as_tensor(np.asarray(a), dtype=torch.float32))
-
-    def to_numpy(self, flat=None):
-        flat = self.params if flat is None else flat
-        return {n: self.layout.view(flat, n).detach().cpu().numpy().copy() for n in self.layout.names()}
-
-    def zero_grads(self):
-        self.grads.zero_()
+    def _describe(self):
+        return "the language model (L=%d, H=%d, V=%d)" % (self.L, self.H, self.V)
 
     # ---- one mini-batch ----------------------------------------------------------------
-    def _run_length(self, max_len):
-        """Steps the recurrence has to visit: the batch's longest row when the host knows it, as Engine._run_length does."""
-        if max_len is None:
-            return self.T
-        return max(1, min(int(max_len), self.T))
-
     def _check_batch(self, tok, lengths):
         if tuple(tok.shape[:1]) != (self.B,) or tok.shape[1] < self.T + 1 or lengths.numel() != self.B:
             raise ValueError("language model batch: tok %s / lengths %s do not fit B = %d rows of %d + 1 tokens"
@@ -136,13 +91,23 @@ class LmEngine(object):
         ops.embed_bwd(tok, lengths, ws.dz0, self.g("input_w"), self.g("input_b"))
         return self.loss
 
+    def mini_batch_recovering(self, tok, lengths, kept_grads=None, compute_gradients=True, **kw):
+        """mini_batch() that survives a dataflow time-out: when a whole-sequence launch gave up waiting, the gradient buffer goes
+        back to `kept_grads` (None: to zero -- the first mini-batch of an optimiser step), the mini-batch runs again on the
+        launch-per-diagonal kernels and check() has to pass.  Returns True when it had to do that."""
+        self.mini_batch(tok, lengths, compute_gradients=compute_gradients, **kw)
+        if self.healthy():
+            return False
+        if compute_gradients:
+            self.grads.copy_(kept_grads) if kept_grads is not None else self.zero_grads()
+        self.mini_batch(tok, lengths, compute_gradients=compute_gradients, per_diagonal=True, **kw)
+        self.check()
+        return True
+
     def score(self, tok, lengths, max_len=None, per_token=False):
         """Forward only, at keep 1.0: -loss[b], the natural-log probability of each row including its closing EOS, as a host
         array [B]; with per_token the -nll [T,B] too."""
-        self.mini_batch(tok, lengths, max_len=max_len, compute_gradients=False)
-        if not self.healthy():
-            self.mini_batch(tok, lengths, max_len=max_len, compute_gradients=False, per_diagonal=True)
-            self.check()
+        self.mini_batch_recovering(tok, lengths, max_len=max_len, compute_gradients=False)
         logp = -self.loss.cpu().numpy()
         return (logp, -self.nll.cpu().numpy()) if per_token else logp
 
@@ -153,22 +118,6 @@ class LmEngine(object):
 
     def check(self):
         ops.lstm_status(self._ws)
-
-    def healthy(self):
-        """False when a whole-sequence launch of the last mini-batch gave up waiting (its results are invalid: repeat it with
-        per_diagonal=True); every other error of the status call is raised."""
-        try:
-            self.check()
-            return True
-        except _lib.DataflowTimeout:
-            return False
-
-    def apply(self, lr, clip, beta1=0.9, beta2=0.999, eps=1e-8):
-        self.adam_step += 1
-        t = self.adam_step
-        lr_t = lr * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
-        ops.clip_adam(self.params, self.grads, self.adam_m, self.adam_v, float(clip), lr_t, beta1, beta2, eps, norm_out=self.norm)
-        return self.norm
 
 
 def sentence_rows(id_lists, num_labels, width=None):
@@ -185,12 +134,7 @@ def sentence_rows(id_lists, num_labels, width=None):
     return tok, lens
 
 
-class _Variable(object):
-    def __init__(self, value):
-        self.value = value
-
-
-class LanguageModel(object):
+class LanguageModel(checkpoint.TrainedModel):
     """The reference class's surface on the GPU engine.  `session` arguments are accepted and ignored, as in AcousticModel."""
 
     def __init__(self, num_layers, hidden_size, batch_size, max_input_seq_length, max_target_seq_length, input_dim,
@@ -199,12 +143,7 @@ class LanguageModel(object):
         self.max_input_seq_length, self.max_target_seq_length = max_input_seq_length, max_target_seq_length
         self.input_dim = self.num_labels = input_dim          # the output has the input's dimension
         self.precision, self.seed = precision, seed
-        self.engine = None
-        self.rnn_created = False
-        self.input_keep_prob = self.output_keep_prob = 1.0
-        self.grad_clip, self.lr_decay_factor = 1.0, 1.0
-        self.learning_rate_var = _Variable(0.0)
-        self.global_step = _Variable(0)
+        checkpoint.TrainedModel.__init__(self)
         self.recovered_steps = 0
         self._dataset = self._iter = None
         self._dropout_seed = 0
@@ -228,15 +167,7 @@ class LanguageModel(object):
 
     def create_training_rnn(self, input_keep_prob, output_keep_prob, grad_clip, learning_rate, lr_decay_factor, use_iterator=False):
         self._create()
-        self.input_keep_prob, self.output_keep_prob = float(input_keep_prob), float(output_keep_prob)
-        self.grad_clip, self.lr_decay_factor = float(grad_clip), float(lr_decay_factor)
-        self.learning_rate_var.value = float(learning_rate)
-
-    def get_learning_rate(self):
-        return self.learning_rate_var.value
-
-    def set_learning_rate(self, sess, learning_rate):
-        self.learning_rate_var.value = float(learning_rate)
+        self._set_training(input_keep_prob, output_keep_prob, grad_clip, learning_rate, lr_decay_factor)
 
     # ---- data ------------------------------------------------------------------------------
     @staticmethod
@@ -296,20 +227,12 @@ class LanguageModel(object):
         keep = (self.input_keep_prob, self.output_keep_prob) if compute_gradients else (1.0, 1.0)
         self._dropout_seed += 1
         kept = eng.grads.clone() if compute_gradients and self._mini_batches > 0 else None
-        kw = dict(keep_in=keep[0], keep_out=keep[1], seed=self._dropout_seed, max_len=int(lens.max()),
-                  scale=1.0 / (max(n_tok, 1) * self._mini_batch_size), compute_gradients=compute_gradients)
-        eng.mini_batch(d_tok, d_len, **kw)
-        loss = eng.loss.cpu().numpy().astype(np.float64)
-        if not eng.healthy():
-            # a whole-sequence launch gave up waiting: take the contribution back and repeat on the launch-per-diagonal kernels
+        if eng.mini_batch_recovering(d_tok, d_len, kept, compute_gradients, keep_in=keep[0], keep_out=keep[1], seed=self._dropout_seed,
+                                     max_len=int(lens.max()), scale=1.0 / (max(n_tok, 1) * self._mini_batch_size)):
             self.recovered_steps += 1
             if self.recovered_steps == 1:
                 logging.warning("a whole-sequence LSTM launch timed out: repeating the mini-batch on the launch-per-diagonal kernels")
-            if compute_gradients:
-                eng.grads.copy_(kept) if kept is not None else eng.zero_grads()
-            eng.mini_batch(d_tok, d_len, per_diagonal=True, **kw)
-            loss = eng.loss.cpu().numpy().astype(np.float64)
-            eng.check()
+        loss = eng.loss.cpu().numpy().astype(np.float64)
         # token error of the arg-max prediction: the "error rate" slot the plateau rule watches
         Tr = eng._Tr
         pred = eng.logits[:Tr].cpu().numpy().argmax(axis=2)                    # [Tr, B], on the host
@@ -379,16 +302,6 @@ class LanguageModel(object):
         return out
 
     # ---- checkpoints: checkpoint_dir/language/languagemodel.npz, the reference graph's variable names + Adam state -----------
-    _TF_NAMES = {"input_w": "Input_Layer/input_w", "input_b": "Input_Layer/input_b",
-                 "output_w": "Output_layer/output_w", "output_b": "Output_layer/output_b"}
-
-    @classmethod
-    def _tf_name(cls, name):
-        if name in cls._TF_NAMES:
-            return cls._TF_NAMES[name]
-        kind, l = name.split("_")
-        return "rnn/multi_rnn_cell/cell_%s/basic_lstm_cell/%s" % (l, kind)
-
     @staticmethod
     def checkpoint_path(checkpoint_dir):
         return os.path.join(checkpoint_dir, "language", "languagemodel.npz")
@@ -396,17 +309,7 @@ class LanguageModel(object):
     def save(self, session, checkpoint_dir):
         path = self.checkpoint_path(checkpoint_dir)
         os.makedirs(os.path.dirname(path), exist_ok=True)
-        eng = self.engine
-        arrays = {self._tf_name(k): v for k, v in eng.to_numpy().items()}
-        arrays["global_step"] = np.int32(self.global_step.value)
-        arrays["learning_rate"] = np.float32(self.learning_rate_var.value)
-        for slot, flat in (("m", eng.adam_m), ("v", eng.adam_v)):
-            for k, v in eng.to_numpy(flat).items():
-                arrays["adam/%s/%s" % (slot, self._tf_name(k))] = v
-        arrays["adam/step"] = np.int64(eng.adam_step)
-        tmp = path[:-4] + ".tmp.npz"
-        np.savez(tmp, **arrays)
-        os.replace(tmp, path)                      # never a half-written checkpoint
+        checkpoint.write(path, checkpoint.pack(self.engine, self.global_step.value, self.learning_rate_var.value))
         logging.info("Language model checkpoint saved")
 
     def restore(self, session, checkpoint_dir, must_exist=False):
@@ -417,16 +320,7 @@ class LanguageModel(object):
                                    "lm_weight to 0" % (os.path.dirname(path), os.path.basename(path)))
             logging.info("Created language model with fresh parameters.")
             return False
-        eng = self.engine
-        z = np.load(path)
-        names = eng.layout.names()
-        eng.load_numpy({k: z[self._tf_name(k)] for k in names})
-        self.global_step.value = int(z["global_step"])
-        self.learning_rate_var.value = float(z["learning_rate"])
-        if "adam/step" in z.files:
-            eng.load_numpy({k: z["adam/m/" + self._tf_name(k)] for k in names}, flat=eng.adam_m)
-            eng.load_numpy({k: z["adam/v/" + self._tf_name(k)] for k in names}, flat=eng.adam_v)
-            eng.adam_step = int(z["adam/step"])
+        self.global_step.value, self.learning_rate_var.value, _ = checkpoint.unpack(np.load(path), self.engine)
         return True
 
 

@@ -260,19 +260,29 @@ def _rebuild_training_input(model, sess, iterator, train_set, hp):
 
 def train_acoustic_rnn(train_set, test_set, hyper_params, prog_params):
     hp = hyper_params
-    ckpt_dir = hp["checkpoint_dir"] + "/acoustic/"
-    epoch_limit = prog_params["max_epoch"]
-    window = hp["steps_per_checkpoint"]
     with Session() as sess:
         model, t_iterator, v_iterator = build_acoustic_training_rnn(sess, hp, prog_params, train_set, test_set)
+
+        def evaluate(step):
+            if step % hp["steps_per_evaluation"] == 0 and len(test_set) > 0:
+                model.run_evaluation(sess)
+                sess.run(v_iterator.initializer)
+
         try:
-            _train_loop(model, sess, t_iterator, v_iterator, train_set, test_set, hp, prog_params, ckpt_dir, epoch_limit, window)
+            _train_loop(model, sess, (hp["mini_batch_size"], hp["rnn_state_reset_ratio"]),
+                        lambda: _rebuild_training_input(model, sess, t_iterator, train_set, hp), evaluate,
+                        hp["checkpoint_dir"] + "/acoustic/", prog_params["max_epoch"], hp["steps_per_checkpoint"], "Model",
+                        epoch_limit_note="Max number of epochs reached, exiting train step")
         finally:
             model.close()       # the asynchronous decoder's threads and pinned buffers: not left to __del__ at interpreter shutdown
 
 
-def _train_loop(model, sess, t_iterator, v_iterator, train_set, test_set, hp, prog_params, ckpt_dir, epoch_limit, window):
-    """The reference's training loop (stt.py:171-236): windows of steps_per_checkpoint optimiser steps, checkpoint, evaluation, plateau rule."""
+def _train_loop(model, sess, step_args, rebuild, evaluate, ckpt_dir, epoch_limit, window, word, epoch_limit_note=None):
+    """The reference's training loop (stt.py:171-236), for both models: windows of `window` optimiser steps
+    (model.run_train_step(sess, *step_args)), checkpoint, evaluation, plateau rule, stop below a rate of 1e-7.  rebuild() makes the
+    next epoch's input when one ends inside the limit; evaluate(step) is called after every window's checkpoint and decides for
+    itself (None: nothing to evaluate on); `word` names the model in the decay line and `epoch_limit_note` is logged when the
+    limit is reached inside a window."""
     schedule = PlateauSchedule()
     epoch = step = 0
 
@@ -282,24 +292,23 @@ def _train_loop(model, sess, t_iterator, v_iterator, train_set, test_set, hp, pr
     while not out_of_epochs():
         window_error = 0.0
         for _ in range(window):
-            _loss, err, step, exhausted = model.run_train_step(sess, hp["mini_batch_size"],
-                                                               hp["rnn_state_reset_ratio"])
+            _loss, err, step, exhausted = model.run_train_step(sess, *step_args)
             window_error += err / window
             if exhausted:
                 epoch += 1
                 logging.info("End of epoch number : %d", epoch)
                 if out_of_epochs():
-                    logging.info("Max number of epochs reached, exiting train step")
+                    if epoch_limit_note:
+                        logging.info(epoch_limit_note)
                     break
-                _rebuild_training_input(model, sess, t_iterator, train_set, hp)
+                rebuild()
         model.save(sess, ckpt_dir)
-        if step % hp["steps_per_evaluation"] == 0 and len(test_set) > 0:
-            model.run_evaluation(sess)
-            sess.run(v_iterator.initializer)
+        if evaluate is not None:
+            evaluate(step)
         if schedule.should_decay(window_error):
-            sess.run(model.learning_rate_decay_op)
-            logging.info("Model is not improving, decaying the learning rate")
-            if model.learning_rate_var.eval() < 1e-7:
+            model.learning_rate_decay_op()
+            logging.info("%s is not improving, decaying the learning rate", word)
+            if model.get_learning_rate() < 1e-7:
                 logging.info("Learning rate is too low, exiting")
                 return
             model.save(sess, ckpt_dir)      # keep the decayed rate in the checkpoint
@@ -364,8 +373,8 @@ def load_language_dataset(speech_reco, hyper_params):
 
 
 def train_language_rnn(train_set, test_set, hyper_params, prog_params):
-    """--train_language: the loop shape of train_acoustic_rnn -- windows of steps_per_checkpoint optimiser steps, checkpoint,
-    evaluation on the test sentences, plateau rule on the window's token error rate."""
+    """--train_language: the loop of train_acoustic_rnn (_train_loop), one mini-batch per optimiser step, evaluation on the test
+    sentences after every window, plateau rule on the window's token error rate."""
     from models.LanguageModel import LanguageModel
     hp = hyper_params
     if not train_set:
@@ -377,33 +386,18 @@ def train_language_rnn(train_set, test_set, hyper_params, prog_params):
     ds_args = (hp["lm_batch_size"], hp["max_target_seq_length"], hp["char_map"])
     test_dataset = LanguageModel.build_dataset(test_set, *ds_args) if test_set else []
     model.add_dataset_input(LanguageModel.build_dataset(train_set, *ds_args))
-    schedule = PlateauSchedule()
-    epoch, epoch_limit, window = 0, prog_params["max_epoch"], hp["steps_per_checkpoint"]
-    while epoch_limit is None or epoch <= epoch_limit:
-        window_error = 0.0
-        for _ in range(window):
-            _loss, err, step, exhausted = model.run_train_step(None, 1)
-            window_error += err / window
-            if exhausted:
-                epoch += 1
-                logging.info("End of epoch number : %d", epoch)
-                if epoch_limit is not None and epoch > epoch_limit:
-                    break
-                shuffle(train_set)
-                model.add_dataset_input(LanguageModel.build_dataset(train_set, *ds_args))
-        model.save(None, hp["checkpoint_dir"])
-        if test_dataset:
-            loss, err = model.evaluate_dataset(test_dataset)
-            logging.info("Language model evaluation : loss %.5f nats per token (perplexity %.3f) - token error rate %.5f",
-                         loss, float(np.exp(min(loss, 50.0))), err)
-        if schedule.should_decay(window_error):
-            model.set_learning_rate(None, model.get_learning_rate() * hp["lm_lr_decay_factor"])
-            logging.info("Language model is not improving, decaying the learning rate")
-            if model.get_learning_rate() < 1e-7:
-                logging.info("Learning rate is too low, exiting")
-                return model
-            model.save(None, hp["checkpoint_dir"])
-    logging.info("Max number of epochs reached, exiting training session")
+
+    def rebuild():
+        shuffle(train_set)
+        model.add_dataset_input(LanguageModel.build_dataset(train_set, *ds_args))
+
+    def evaluate(step):
+        loss, err = model.evaluate_dataset(test_dataset)
+        logging.info("Language model evaluation : loss %.5f nats per token (perplexity %.3f) - token error rate %.5f",
+                     loss, float(np.exp(min(loss, 50.0))), err)
+
+    _train_loop(model, None, (1,), rebuild, evaluate if test_dataset else None, hp["checkpoint_dir"], prog_params["max_epoch"],
+                hp["steps_per_checkpoint"], "Language model")
     return model
 
 

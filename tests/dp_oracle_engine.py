@@ -10,20 +10,15 @@ import torch
 
 from oracle import model as om
 from rnn_speech_amd.acoustic_model import AcousticModel
-from rnn_speech_amd.engine import Engine, ParamLayout
+from rnn_speech_amd.engine import Engine, ParamLayout, ParamStore
+from rnn_speech_amd.language_model import LanguageModel, LmEngine
 
 
 class OracleEngine(Engine):
     def __init__(self, num_layers, hidden, input_dim, num_labels, batch_size, max_T, max_U, seed=1234, **_):
         self.L, self.H, self.D, self.C = num_layers, hidden, input_dim, num_labels
         self.B, self.T, self.U = batch_size, max_T, max_U
-        self.device = torch.device("cpu")
-        self.layout = ParamLayout(num_layers, hidden, input_dim, num_labels)
-        n = self.layout.total
-        self.params, self.grads = torch.zeros(n), torch.zeros(n)
-        self.adam_m, self.adam_v = torch.zeros(n), torch.zeros(n)
-        self.norm = torch.zeros(1)
-        self.adam_step = 0
+        ParamStore.__init__(self, ParamLayout(num_layers, hidden, input_dim, num_labels), "cpu")
         self.logits = torch.zeros(max_T, batch_size, num_labels)
         self.loss = torch.zeros(batch_size)
         self.state_h = torch.zeros(num_layers, batch_size, hidden)
@@ -101,6 +96,21 @@ class OracleAcousticModel(AcousticModel):
         import torch
         dist = torch.as_tensor([float(om.edit_distance(i, r)) for i, r in zip(ids, rows)])
         return dist, np.asarray([len(r) for r in rows], np.float64)
+
+
+class CpuLmEngine(LmEngine):
+    """The language-model engine's host side (parameter store, checkpoints) on CPU buffers; it runs no mini-batch."""
+
+    def __init__(self, num_layers, hidden, num_labels, batch_size, max_len, seed=1234, **_):
+        self.L, self.H, self.V, self.B, self.T = num_layers, hidden, num_labels, batch_size, max_len
+        ParamStore.__init__(self, ParamLayout(num_layers, hidden, num_labels, num_labels), "cpu")
+        self.init_parameters(seed)
+
+
+class CpuLanguageModel(LanguageModel):
+    def _create(self):
+        self.engine = CpuLmEngine(self.num_layers, self.hidden_size, self.num_labels, self.batch_size, self._row_len, seed=self.seed)
+        self.rnn_created = True
 
 
 class ListDataset(object):
