@@ -953,6 +953,76 @@ int amdspeech_feature_moments(void* stream, const float* x, const int* n_frames,
 int amdspeech_feature_norm(void* stream, float* x, const int* n_frames, int B, int D, int t_in,
                            const amdspeech_feature_norm_desc* desc, const double* table, void* workspace);
 
+/* ------------------------------------------- voice activity / long recordings ---
+ * What cuts a recording LONGER than the model's input at its pauses (no reference counterpart: an opt-in deviation, config key
+ * long_audio; nothing of it is called at the key's default): frame energies of raw PCM, speech flags from an adaptive threshold,
+ * and the gather of sample spans of a long row into the padded block the resampler and the front end take.  The cut planner that
+ * sits between the flags and the gather is host code (segmenter.py).  Plain launches; no kernel waits for another workgroup.
+ *   pcm        float [B][n_max]     mono samples at the FILE's rate; words at or past n_samples[b] are never read
+ *   n_samples  int32 [B] (HOST)     valid samples per row, 0 .. n_max
+ *   hop        samples per block, >= 1 (callers pass 10 ms: round-half-even(0.01 rate)); F = ceil(n / hop) frames per row
+ * amdspeech_vad_num_frames: ceil(n_samples / hop), 0 for 0 samples; host arithmetic (AMDSPEECH_EINVAL for a negative count or hop < 1).
+ *
+ * amdspeech_vad_energy -- energy_db float [B][f_max], f_max >= ceil(n_max / hop).  The arithmetic, per row:
+ *   S[t]  = sum of double(x_i)^2 over i in [t hop, min(n, (t + 1) hop))     float64; S[t] = 0 for t >= F
+ *   mean  = (S[t] + S[t + 1]) / (2 hop)            frame t covers two blocks; the divisor stays 2 hop at the ragged end
+ *   energy_db[t] = float(10 log10(max(mean, 1e-12)))   for t < F;   -120 where mean is not finite (an Inf or NaN sample: the
+ *   value of digital silence), and -120 in every word at t >= F up to f_max
+ * The order of the sum inside a block is fixed (16 lanes stride over the block's samples, or its 16-byte vectors, and meet in an
+ * 8-4-2-1 butterfly): no atomics, two calls give the same bits.  The error against a float64 evaluation is that of a float64 sum of
+ * up to 2 hop exact squares, 2 hop 2^-53 relative, and of one float64 log10 rounded to float.  `ws` is not read by this call (it
+ * is the workspace of the flags call, accepted so that one buffer serves both) and may be NULL.
+ *
+ * amdspeech_vad_flags -- speech uint8 [B][f_max], stats float [B][3] = (floor, peak, threshold), from energy_db [B][f_max] and
+ * n_frames int32 [B] (HOST; 0 .. f_max).  Every operation is one float32 operation or integer logic; per row, F = n_frames[b]:
+ *   k     = ((F - 1) percentile) / 100                  integer division
+ *   floor = the k-th smallest (0-based) of energy_db[0 .. F), EXACT (a radix select over the order-preserving uint32 image of the
+ *           floats, four 8-bit passes, counters in LDS);   peak = the largest.   energy_db must hold no NaN (the energy call writes none)
+ *   thr   = min(max(floor + margin_db, peak - range_db), peak - margin_db)
+ *   raw[t]    = energy_db[t] > thr && energy_db[t] > min_db
+ *   open[t]   = raw[t] and the run of ones around t is at least min_run long       (runs of min_run or more survive unchanged)
+ *   speech[t] = OR of open[max(t - hangover, 0) .. min(t + hangover, F - 1)];      0 for t >= F up to f_max
+ * The cap peak - margin_db makes a stationary row all speech (floor + margin_db alone would make it all silence); the gate min_db
+ * makes digital silence no speech.  A row with F = 0 gets stats (-120, -120, -120).
+ *   ws   device, at least B * f_max * 4 bytes, 4-byte aligned -- amdspeech_vad_workspace_bytes(B, n_max, hop) for f_max =
+ *        ceil(n_max / hop) (0 for a bad shape); caller-allocated.  One int per frame: the last frame at or before it that is the
+ *        min_run-th or later of its run
+ *
+ * amdspeech_gather_spans -- out float [S][w_out] (16-byte aligned) from spans (row[s], start[s], count[s]), int32 [S] each (HOST):
+ *   out[s][i] = pcm[row[s]][start[s] + i]   for i < min(count[s], n_samples[row[s]] - start[s], w_out),   0 from there up to w_out
+ * A span that reaches past its row (or starts past it) yields zeros there and never reads past the row.  ONE launch for all spans;
+ * 16-byte stores throughout, 16-byte loads where start[s] + i and the row base are multiples of four words.  S = 0 launches nothing
+ * and succeeds.  Up to 256 spans travel as kernel arguments; more go through a device buffer of the call's own, and the call then
+ * waits for the stream before it returns.  The lengths of the first two calls travel the same way (256 rows).
+ *
+ * AMDSPEECH_EINVAL with a message: hop < 1, percentile outside 0 .. 100, min_run < 1, hangover outside 0 .. 1024, a margin_db,
+ * range_db or min_db that is NaN or infinite, a count, start or length that is negative or beyond its bound, null pointers (but
+ * for `ws` of the energy call and the span arrays at S = 0), f_max < ceil(n_max / hop), B * f_max >= 2^31, w_out < 1, and a
+ * pcm that is not 16-byte aligned when the plan takes 16-byte loads: such a base is REFUSED, not run with single-word accesses.
+ * amdspeech_vad_plan: the launch geometry as plain numbers, a READ-ONLY view of the plan the energy call itself reads; host only.
+ *   load_vec         words per load of the energy kernel: 4 when hop % 4 == 0 and (B == 1 or n_max % 4 == 0) -- every block start
+ *                    is then 16-byte aligned -- else 1 (hop 441, 44.1 kHz: every second block start is odd)
+ *   frames_per_tile  63: a workgroup forms 64 block sums (16 teams of 16 lanes, four rounds) and the 63 frames between them
+ *   tiles_per_row, workgroups, threads   ceil(f_max / 63); tiles_per_row * min(B, 65535); 256.  The grid runs over (tile, row): one
+ *                    row of an hour at 16 kHz is 5715 workgroups
+ *   f_max            ceil(n_max / hop)
+ *   select_passes    4: the 8-bit passes of the radix select
+ *   row_workgroups, row_threads   the select and the flags kernel: min(B, 65535) workgroups of 1024 threads, one row each
+ *   meta_by_copy     1 when B > 256                                                                                          */
+typedef struct amdspeech_vad_plan_info {
+    int load_vec, frames_per_tile, tiles_per_row, workgroups, threads, f_max, select_passes, row_workgroups, row_threads, meta_by_copy;
+} amdspeech_vad_plan_info;
+int amdspeech_vad_num_frames(int n_samples, int hop);
+size_t amdspeech_vad_workspace_bytes(int B, int n_max, int hop);
+int amdspeech_vad_plan(int B, int n_max, int hop, amdspeech_vad_plan_info* out);
+int amdspeech_vad_energy(void* stream, const float* pcm, const int* n_samples, int B, int n_max, int hop,
+                         float* energy_db, int f_max, void* ws);
+int amdspeech_vad_flags(void* stream, const float* energy_db, const int* n_frames, int B, int f_max,
+                        int percentile, float margin_db, float range_db, float min_db, int min_run, int hangover,
+                        unsigned char* speech, float* stats, void* ws);
+int amdspeech_gather_spans(void* stream, const float* pcm, const int* n_samples, int B, int n_max,
+                           const int* row, const int* start, const int* count, int S, float* out, int w_out);
+
 /* ------------------------------------------------------------- profiling ----
  * Optional HIP-event timing of the recurrence kernels (no reference counterpart;
  * feeds bench.py's roofline line).  When enabled, lstm_fwd / lstm_bwd bracket

@@ -5,15 +5,22 @@ max_input_seq_length, UNtruncated frame count) -- but the features are computed 
 HIP front-end kernels (csrc/frontend.hip) instead of librosa/numpy.  `process_batch`
 is the fast path: a whole mini-batch of signals -> one time-major device tensor.
 """
+import collections
+
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, segmenter
 from .feature_norm import MODES, FeatureStats, describe_processor
 
 FRAME_STRIDE = 0.01
 FRAME_SIZE = 0.025
 DEFAULT_LOAD_SR = 22050   # librosa.load default used by the reference's file path (:49)
+
+
+# What AudioProcessor.segment returns: the recording on the device (pcm [1, n] at rate sr), the detector's hop, the spans
+# [(start_sample, n_samples, start_frame, end_frame), ...] (segmenter.plan_spans) and the row's stats (floor, peak, threshold in dB)
+Segments = collections.namedtuple("Segments", "pcm n sr hop spans stats")
 
 
 class AudioProcessor(object):
@@ -261,6 +268,44 @@ class AudioProcessor(object):
                 for j, i in enumerate(idx):
                     n[i] = lens[j]
         return self._features(pcm, n, self.load_sr, t_max, augment)
+
+    # ---- long recordings ----------------------------------------------------------
+    def segment(self, signal, sr, floor_percentile=10, margin_db=10.0, range_db=50.0, min_db=-70.0, min_speech_ms=50.0,
+                hangover_ms=200.0, pad_ms=100.0):
+        """Where to cut a recording longer than the model's input: signal (1-D floats at rate sr) is uploaded once, the voice-activity
+        kernels run at the file's own rate with hop = round-half-even(0.01 sr) (ops.vad_energy, ops.vad_flags; the milliseconds
+        become 10 ms frames), and the cut planner (segmenter.plan_spans) turns the flags into spans of at most the budget the
+        resampler and the front end leave of max_input_seq_length.  Returns a Segments record; process_segments takes it from there."""
+        sig = np.ascontiguousarray(signal, dtype=np.float32).ravel()
+        sr, n = int(sr), len(sig)
+        hop = int(round(sr * 0.01))
+        frames = lambda ms: int(round(float(ms) / 10.0))
+        pcm, _ = self._upload([sig])
+        if n == 0:
+            return Segments(pcm, 0, sr, hop, [], (-120.0, -120.0, -120.0))
+        F = ops.vad_num_frames(n, hop)
+        energy = ops.vad_energy(pcm, [n], hop)
+        speech, stats = ops.vad_flags(energy, [F], floor_percentile, margin_db, range_db, min_db, max(1, frames(min_speech_ms)),
+                                      frames(hangover_ms))
+        budget = segmenter.frame_budget(sr, hop, self.load_sr, self.feature_type, self.max_input_seq_length)
+        shortest = segmenter.min_span_samples(sr, self.load_sr, self.feature_type, self.n_mfcc)
+        spans = segmenter.plan_spans(speech[0, :F].cpu().numpy(), energy[0, :F].cpu().numpy(), n, hop, budget, frames(pad_ms), shortest)
+        return Segments(pcm, n, sr, hop, spans, tuple(float(v) for v in stats[0].cpu().numpy()))
+
+    def process_segments(self, pcm_device, n, sr, spans, rows=None):
+        """The features of spans of ONE long device row pcm_device [1, >= n] at rate sr, as process_files returns them for as many
+        files: one ops.gather_spans call builds the padded [rows, width] block, then the per-row resampler to load_sr and the front
+        end as for any mini-batch.  spans: (start_sample, n_samples, ...) tuples; `rows` > len(spans) pads with empty rows.
+        feature_norm : utterance normalises per span (a span is the utterance the model sees); no speed, noise or reverberation
+        draw is ever applied here."""
+        S = len(spans)
+        B = rows or S
+        counts = [int(sp[1]) for sp in spans]
+        block = torch.empty(B, max(counts + [1]), device=pcm_device.device, dtype=torch.float32)
+        ops.gather_spans(pcm_device, [int(n)], [0] * S, [int(sp[0]) for sp in spans], counts, block.shape[1], out=block[:S])
+        block[S:] = 0.0
+        pcm, lens = self._resampled(block, counts, [1000] * S, int(sr), self.load_sr)
+        return self._features(pcm, list(lens) + [0] * (B - S), self.load_sr, None, None)
 
 
 AUDIO_SUFFIXES = (".wav", ".flac", ".sph")

@@ -1,7 +1,7 @@
 """config.ini reader + checkpoint-side pickle logic (reference:
 /root/reference/util/hyperparams.py:17-141).  Same section/key names and defaults; a few
 optional keys are added for the MI355X build (n_mfcc, sample_rate, frame_stack / frame_skip, feature_norm*, spec_augment_*,
-speed_perturb_*, noise_* / reverb_* / augment_* ...) and the reference's [lm_network_params] section with this build's lm_* keys."""
+speed_perturb_*, noise_* / reverb_* / augment_*, long_audio / vad_* ...) and the reference's [lm_network_params] section with this build's lm_* keys."""
 import configparser
 import logging
 import os
@@ -99,6 +99,32 @@ def read_config_file(config_file):
     # SNR range in dB.  A part is off when its directory is empty or its probability 0 (the default).  NOT structural, like SpecAugment
     d.update(read_augment_keys(lambda key, dflt: cp.get(_TRAINING, key, fallback=dflt)))
     d.update(read_lm_keys(lambda key, dflt: cp.get(_LM, key, fallback=dflt)))
+    d.update(read_long_audio_keys(lambda key, dflt: cp.get(_GENERAL, key, fallback=dflt)))
+    return d
+
+
+LONG_AUDIO_MODES = ("truncate", "segment")
+# key -> (default, kind, lo, hi).  The defaults are the customary values of an energy detector; nobody has tuned them on a corpus
+_VAD_KEYS = {"vad_floor_percentile": ("10", int, 0, 100), "vad_margin_db": ("10", float, 0.0, 200.0),
+             "vad_range_db": ("50", float, 0.0, 400.0), "vad_min_db": ("-70", float, -120.0, 100.0),
+             "vad_min_speech_ms": ("50", float, 0.0, 10000.0), "vad_hangover_ms": ("200", float, 0.0, 10240.0),
+             "vad_pad_ms": ("100", float, 0.0, 10000.0)}
+
+
+def read_long_audio_keys(get):
+    """Recordings longer than max_input_seq_length under --file ([general]): long_audio (truncate, the default and the reference's
+    behaviour | segment: cut at the pauses a voice-activity detector finds, ops.vad_energy / ops.vad_flags / segmenter.py) and the
+    detector's vad_* keys.  None is structural.  get(key, default) -> text; a bad value raises ValueError naming its key."""
+    d = {"long_audio": (get("long_audio", "truncate") or "truncate").strip().lower()}
+    if d["long_audio"] not in LONG_AUDIO_MODES:
+        raise ValueError("long_audio : %r is not one of %s" % (d["long_audio"], " | ".join(LONG_AUDIO_MODES)))
+    for key, (dflt, kind, lo, hi) in _VAD_KEYS.items():
+        text = get(key, dflt)
+        try:
+            v = kind(str(text).strip())
+        except (ValueError, OverflowError):
+            raise ValueError("%s must be %s, not %r" % (key, "an integer" if kind is int else "a decimal", text))
+        d[key] = check_range(key, v, lo, hi)
     return d
 
 

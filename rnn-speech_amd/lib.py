@@ -79,6 +79,11 @@ class FeatureNormPlanInfo(C.Structure):     # amdspeech_feature_norm_plan_info (
     _fields_ = [(n, C.c_int) for n in ("vec", "split", "workgroups", "lds_bytes", "meta_by_copy", "workspace_bytes")]
 
 
+class VadPlanInfo(C.Structure):     # amdspeech_vad_plan_info (include/amdspeech.h): the launch geometry of the voice-activity calls, read-only
+    _fields_ = [(n, C.c_int) for n in ("load_vec", "frames_per_tile", "tiles_per_row", "workgroups", "threads", "f_max", "select_passes",
+                                       "row_workgroups", "row_threads", "meta_by_copy")]
+
+
 class ResampleRowsPlanInfo(C.Structure):     # amdspeech_resample_rows_plan_info (include/amdspeech.h): the launch geometry of a per-row resampling call, read-only
     _fields_ = [(n, C.c_int) for n in ("tile", "tiles_per_row", "workgroups", "span_max", "table_chunk", "lds_bytes", "any_copy", "meta_launches")]
 
@@ -231,6 +236,12 @@ PROTOTYPES = {
     "amdspeech_feature_norm_plan": (_I, [_I, _I, _I, _I, C.POINTER(FeatureNormPlanInfo)]),
     "amdspeech_feature_moments": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "amdspeech_feature_norm": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(FeatureNormDesc), _P, _P]),
+    "amdspeech_vad_num_frames": (_I, [_I, _I]),
+    "amdspeech_vad_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "amdspeech_vad_plan": (_I, [_I, _I, _I, C.POINTER(VadPlanInfo)]),
+    "amdspeech_vad_energy": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P]),
+    "amdspeech_vad_flags": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _I, _I, _P, _P, _P]),
+    "amdspeech_gather_spans": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _I]),
     "amdspeech_profile_enable": (_I, [_I]),
     "amdspeech_profile_get": (_I, [_I, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "amdspeech_profile_get_flops": (_I, [_I, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -1270,6 +1270,86 @@ def feature_norm(feat, n_frames, mode, norm_vars=True, var_floor=FEATURE_NORM_VA
     return feat
 
 
+# ------------------------------------------------------------ voice activity / long recordings
+_vad_ws = {}
+
+
+def vad_num_frames(n_samples, hop):
+    """ceil(n_samples / hop): the frames of a row (amdspeech.h: amdspeech_vad_num_frames).  Host arithmetic."""
+    got = _l.load().amdspeech_vad_num_frames(int(n_samples), int(hop))
+    if got < 0:
+        _l.check(got, "vad_num_frames")
+    return got
+
+
+def vad_plan(B, n_max, hop):
+    """The launch geometry of `vad_energy` / `vad_flags` for a shape (amdspeech.h: amdspeech_vad_plan), as a dict of ints.
+    Read-only: nothing is launched, no device is needed.  A shape the calls refuse raises here too."""
+    info = _l.VadPlanInfo()
+    _l.check(_l.load().amdspeech_vad_plan(int(B), int(n_max), int(hop), C.byref(info)), "vad_plan")
+    return _plan_dict(info)
+
+
+def _chk_rows_2d(what, t, dtype, name):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.is_contiguous()):
+        raise ValueError("%s: %s must be a contiguous %s device matrix" % (what, name, dtype))
+    return t.shape
+
+
+def vad_energy(pcm, n_samples, hop, out=None):
+    """pcm float32 [B, n_max] (device), n_samples python ints, hop samples per block -> energy_db float32 [B, f_max] (device), f_max =
+    ceil(n_max / hop): the decibels of the mean square of two blocks per frame, -120 past a row's frames (amdspeech.h:
+    amdspeech_vad_energy).  Words of pcm at or past a row's length are not read.  out: an [B, >= f_max] tensor to fill."""
+    B, n_max = _chk_rows_2d("vad_energy", pcm, torch.float32, "pcm")
+    lib = _l.load()
+    ns = _c_ints(n_samples, B, "vad_energy")
+    if out is None:
+        out = torch.empty(B, vad_plan(B, n_max, hop)["f_max"], device=pcm.device, dtype=torch.float32)
+    elif _chk_rows_2d("vad_energy", out, torch.float32, "out")[0] != B or out.device != pcm.device:
+        raise ValueError("vad_energy: out is %s on %s, expected [%d, f_max] beside pcm" % (tuple(out.shape), out.device, B))
+    _l.check(lib.amdspeech_vad_energy(_stream(), _p(pcm), ns, B, n_max, int(hop), _p(out), out.shape[1], None), "vad_energy")
+    return out          # stream-ordered; the lengths were kernel arguments (or the call has waited)
+
+
+def vad_flags(energy_db, n_frames, percentile=10, margin_db=10.0, range_db=50.0, min_db=-70.0, min_run=5, hangover=20, speech=None,
+              stats=None):
+    """energy_db float32 [B, f_max] (device, vad_energy's output), n_frames python ints -> (speech uint8 [B, f_max], stats float32
+    [B, 3] = floor, peak, threshold), both on the device: frames above the adaptive threshold and above min_db, runs shorter than
+    min_run frames cleared, the rest widened by hangover frames (amdspeech.h: amdspeech_vad_flags).  speech / stats: tensors to fill."""
+    B, f_max = _chk_rows_2d("vad_flags", energy_db, torch.float32, "energy_db")
+    lib = _l.load()
+    nf = _c_ints(n_frames, B, "vad_flags")
+    if speech is None:
+        speech = torch.empty(B, f_max, device=energy_db.device, dtype=torch.uint8)
+    elif tuple(_chk_rows_2d("vad_flags", speech, torch.uint8, "speech")) != (B, f_max) or speech.device != energy_db.device:
+        raise ValueError("vad_flags: speech is %s, expected %s beside energy_db" % (tuple(speech.shape), (B, f_max)))
+    if stats is None:
+        stats = torch.empty(B, 3, device=energy_db.device, dtype=torch.float32)
+    elif tuple(_chk_rows_2d("vad_flags", stats, torch.float32, "stats")) != (B, 3) or stats.device != energy_db.device:
+        raise ValueError("vad_flags: stats is %s, expected %s beside energy_db" % (tuple(stats.shape), (B, 3)))
+    ws = _cached_ws(_vad_ws, (B, f_max, energy_db.device), lambda: max(lib.amdspeech_vad_workspace_bytes(B, f_max, 1), 4))
+    _l.check(lib.amdspeech_vad_flags(_stream(), _p(energy_db), nf, B, f_max, int(percentile), float(margin_db), float(range_db),
+                                     float(min_db), int(min_run), int(hangover), _p(speech), _p(stats), _p(ws)), "vad_flags")
+    return speech, stats          # stream-ordered; the cached workspace outlives the kernels
+
+
+def gather_spans(pcm, n_samples, row, start, count, w_out, out=None):
+    """pcm float32 [B, n_max] (device), n_samples python ints; row / start / count: python ints per span -> out float32 [S, w_out]
+    (device): out[s, i] = pcm[row[s], start[s] + i] for i < min(count[s], n_samples[row[s]] - start[s], w_out), zero from there
+    on, in ONE launch (amdspeech.h: amdspeech_gather_spans).  No span reads past its row's length.  out: an [S, w_out] tensor to fill."""
+    B, n_max = _chk_rows_2d("gather_spans", pcm, torch.float32, "pcm")
+    S = len(row)
+    ns = _c_ints(n_samples, B, "gather_spans")
+    rows, starts, counts = (_c_ints(v, S, "gather_spans") for v in (row, start, count))
+    if out is None:
+        out = torch.empty(S, max(int(w_out), 1), device=pcm.device, dtype=torch.float32)
+    elif tuple(_chk_rows_2d("gather_spans", out, torch.float32, "out")) != (S, int(w_out)) or out.device != pcm.device:
+        raise ValueError("gather_spans: out is %s, expected %s beside pcm" % (tuple(out.shape), (S, int(w_out))))
+    _l.check(_l.load().amdspeech_gather_spans(_stream(), _p(pcm), ns, B, n_max, rows, starts, counts, S, _p(out) if S else None,
+                                              int(w_out)), "gather_spans")
+    return out          # stream-ordered; the spans were kernel arguments (or the call has waited)
+
+
 # ---------------------------------------------------------------- language model
 _embed_ws = {}
 _xent_ws = {}

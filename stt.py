@@ -11,6 +11,12 @@ training and test corpora, with the loop shape of --train_acoustic; single proce
 decode lm_nbest paths per utterance and return argmax(log p_ctc + lm_weight * log p_lm + lm_length_bonus * tokens); with
 lm_weight 0 (the default) nothing of the language model is loaded.
 
+--file on a recording longer than max_input_seq_length: with `long_audio : truncate` (the default, the reference's behaviour) the
+rest of the file is dropped with a warning; with `long_audio : segment` a voice-activity detector on the GPU finds the pauses
+(the vad_* keys), the recording is cut there into spans the model was trained on, the spans run as ordinary mini-batches of
+batch_size through the forward pass and the decoder above, and one line -- the spans' texts joined by spaces -- is printed, with
+one INFO line `start_s end_s text` per span.  --align and --evaluate do not segment.
+
 Not kept (out of the hot-path scope): --generate_text, --record (pyaudio), --XLA (no tracing
 compiler here; accepted and ignored), TensorBoard.  `training_dataset_dirs` takes the reference's corpus
 trees (LibriSpeech / TED-LIUM / Shtooka / Vystadial, walked by rnn_speech_amd.corpus) or a `path<TAB>transcript`
@@ -34,6 +40,8 @@ import util.audioprocessor as audioprocessor
 import util.dataprocessor as dataprocessor
 import util.hyperparams as hyperparams
 from rnn_speech_amd import dataparallel
+from rnn_speech_amd.audioprocessor import decode_files
+from rnn_speech_amd.segmenter import model_frames
 
 
 def main():
@@ -401,7 +409,39 @@ def train_language_rnn(train_set, test_set, hyper_params, prog_params):
     return model
 
 
+_VAD_OPTIONS = ("floor_percentile", "margin_db", "range_db", "min_db", "min_speech_ms", "hangover_ms", "pad_ms")
+
+
+def process_long_file(audio_processor, hyper_params, signal, sr):
+    """--file with long_audio : segment, for a recording longer than the model's input: the voice-activity detector and the cut
+    planner (AudioProcessor.segment) give spans of at most max_input_seq_length frames, which run through ONE forward model in
+    mini-batches of min(batch_size, spans) rows -- the last one padded with empty rows -- and through the decoder the lm_* keys
+    select, each span as an utterance of its own.  Logs start_s end_s text per span; prints and returns [the texts joined by spaces]."""
+    vad = {name: hyper_params["vad_" + name] for name in _VAD_OPTIONS if "vad_" + name in hyper_params}
+    seg = audio_processor.segment(signal, sr, **vad)
+    texts = []
+    if seg.spans:
+        B = min(hyper_params["batch_size"], len(seg.spans))
+        T = audio_processor.out_seq_length
+        model = _forward_model(hyper_params, B)
+        for i in range(0, len(seg.spans), B):
+            part = seg.spans[i:i + B]
+            feat, lengths = audio_processor.process_segments(seg.pcm, seg.n, seg.sr, part, rows=B)
+            predictions = model.process_input(None, feat, [min(n, T) for n in lengths])
+            for (start, count, _, _), p in zip(part, predictions):
+                texts.append(dataprocessor.DataProcessor.get_labels_str(hyper_params["char_map"], p))
+                logging.info("%.3f %.3f %s", start / float(seg.sr), (start + count) / float(seg.sr), texts[-1])
+    transcribed_text = [" ".join(texts)]
+    print(transcribed_text)
+    return transcribed_text
+
+
 def process_file(audio_processor, hyper_params, file):
+    if hyper_params.get("long_audio", "truncate") == "segment":
+        # (a file that fits is not segmented, whatever the key says: it takes the path below)
+        signal, sr = decode_files([file])[0]
+        if model_frames(len(signal), sr, audio_processor.load_sr, audio_processor.feature_type) > audio_processor.max_input_seq_length:
+            return process_long_file(audio_processor, hyper_params, signal, sr)
     feat_vec, original_length = audio_processor.process_audio_file(file)
     T = audio_processor.out_seq_length
     if original_length > T:
