@@ -97,6 +97,58 @@ int gemm_skinny_launch(hipStream_t s, const GemmPlan& p, bool transB, int M, int
 bool gemm_skinny_tn_plan(int M, int N, int K, const float* A, int lda, const float* B, int ldb, bool accumulate, bool colsum, GemmPlan* out);
 int gemm_skinny_tn_launch(hipStream_t s, const GemmPlan& p, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                           float* C, int ldc, bool accumulate, float* colsum);
+// ---- pieces every GEMM file shares.  Host: the blank plan, the split-K rule and its bookkeeping, the zero fill (defined in gemm.hip).
+static inline GemmPlan plan_blank() {
+    GemmPlan p = GemmPlan();
+    p.splits = 1; p.col_slices = 1;
+    return p;
+}
+// Split K while there are fewer than `below` workgroups: up to `target` of them, every split at least `min_k` long; the range per
+// split is a multiple of `granule` and the split count is what that range leaves.  Per family (tiles are 128 x 128):
+//   family      below / target   min K per split   granule
+//   TN-direct     256 / 256          256              2      one workgroup (one wave per SIMD) per CU keeps the MFMA pipe full, and every
+//                                                            split ends in a tile of f32 atomics; a k-pair per load
+//   KC-direct     192 / 256          256             64      (three quarters of the CUs busy: left alone); the ring holds 64 k
+//   LDS           512 / 512         16 BK            BK      >= ~2 workgroups per CU, >= 16 K tiles per split
+//   bf3           768 / 768         16 TK            TK      three workgroups per CU overlap each other's phases, >= 16 K steps per split
+struct SplitK { int k_chunk, splits; };
+static inline SplitK split_k(int K, int tiles, int below, int target, int min_k, int granule) {
+    int splits = 1;
+    if (tiles < below) {
+        splits = ceil_div(target, tiles);
+        const int max_splits = K / min_k > 0 ? K / min_k : 1;
+        if (splits > max_splits) splits = max_splits;
+    }
+    const int k_chunk = ceil_div(ceil_div(K, splits), granule) * granule;
+    return {k_chunk, ceil_div(K, k_chunk)};
+}
+// ... and what follows from it: several splits meet in C through atomics, onto zeros unless the call accumulates
+static inline void plan_finish(GemmPlan& p, SplitK sk, int tiles, bool accumulate) {
+    p.k_chunk = sk.k_chunk; p.splits = sk.splits;
+    p.atomic = (accumulate || sk.splits > 1) ? 1 : 0;
+    p.zero_fill = (!accumulate && sk.splits > 1) ? 1 : 0;
+    p.grid = tiles * sk.splits;
+}
+void gemm_zero_fill(hipStream_t s, float* C, int M, int N, int ldc);      // C[M,N] = 0 (rows ldc apart)
+
+// Device: the 2x2 accumulators of a wave's 64 x 64 sub-tile (32x32 MFMA layout: register r of lane l is row (r & 3) + 8 (r >> 2) +
+// 4 (l >> 5), column l & 31 of its block).
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+}
+// Workgroups are dealt round-robin to the 8 XCDs, each with its own L2.  The renumbering that gives XCD x a CONTIGUOUS range of the
+// `nwg` work items: with split K one XCD then works on ONE K range of the operands (every byte of A and B crosses the fabric once
+// instead of once per XCD).
+__device__ __forceinline__ int xcd_contiguous(int v, int nwg) {
+    const int x = v & 7, q = nwg >> 3, r = nwg & 7;
+    return x * q + min(x, r) + (v >> 3);
+}
+
 constexpr int GEMM_GROUP_MAX = AMDSPEECH_GEMM_GROUP_MAX;
 // `count` products C_i (+)= A_i^T . B_i of ONE shape (A_i [K][M], B_i [K][N], 16-byte aligned rows) in one launch
 int gemm_f32_tn_group(hipStream_t s, int count, int M, int N, int K, const float* const* A, int lda, const float* const* B,

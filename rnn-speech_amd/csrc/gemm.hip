@@ -10,42 +10,17 @@
 // one K-tile ahead of the MFMAs; split-K (+ f32 atomics) fills the 256 CUs when
 // M*N is small and K is the 32k-frame axis.
 #include "gemm_core.h"
-#include <string.h>
 
 namespace amdspeech {
 
-#ifndef GEMM_XCD_REMAP
-#define GEMM_XCD_REMAP 1
-#endif
 template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) float smem[];      // [buf][A|B][BK * LDS_LD]
-    if (g.gate != nullptr) {
-        if (threadIdx.x == 0) {
-            const unsigned long long t0 = wall_clock64();
-            bool late = false;
-            while (__hip_atomic_load(g.gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > g.gate_need) {
-                if (wall_clock64() - t0 > g.gate_limit) { late = true; break; }
-                __builtin_amdgcn_s_sleep(32);
-            }
-            if (late && g.gate_err != nullptr) atomicOr(g.gate_err, 4u);
-        }
-        __syncthreads();
-    }
-    // Workgroups are dealt round-robin to the 8 XCDs, each with its own L2.  Renumber them so that XCD x gets a CONTIGUOUS
-    // range of (split, tile) pairs: with split K one XCD then works on ONE K range of the operands (every byte of A and B
-    // crosses the fabric once instead of once per XCD).
-    int v = blockIdx.x;
-    const int nwg = gridDim.x;
-#if GEMM_XCD_REMAP
-    if (g.xcd_remap) {
-        const int x = v & 7, q = nwg >> 3, r = nwg & 7;
-        v = x * q + min(x, r) + (v >> 3);
-    }
-#endif
+    gemm_gate_wait(g);
+    const int v = g.xcd_remap ? xcd_contiguous(blockIdx.x, gridDim.x) : (int)blockIdx.x;      // (split K: one K range per XCD)
     const int tiles = g.tiles_n * g.tiles_m;
     WorkgroupBarrier bar;
-    gemm_tile<A_KC, B_KC>(g, v % tiles, v / tiles, smem, threadIdx.x, 0, true, bar);
+    gemm_tile<A_KC, B_KC>(g, v % tiles, v / tiles, smem, threadIdx.x, bar);
 }
 
 // Up to GEMM_GROUP_MAX problems of ONE shape in one launch (the 2 L weight-gradient GEMMs of a backward pass): with several
@@ -60,18 +35,7 @@ struct GemmGroupArgs {
 };
 __global__ __launch_bounds__(256) void gemm_f32_tn_group_kernel(GemmGroupArgs a) {
     GemmArgs g = a.g;
-    if (g.gate != nullptr) {
-        if (threadIdx.x == 0) {
-            const unsigned long long t0 = wall_clock64();
-            bool late = false;
-            while (__hip_atomic_load(g.gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > g.gate_need) {
-                if (wall_clock64() - t0 > g.gate_limit) { late = true; break; }
-                __builtin_amdgcn_s_sleep(32);
-            }
-            if (late && g.gate_err != nullptr) atomicOr(g.gate_err, 4u);
-        }
-        __syncthreads();
-    }
+    gemm_gate_wait(g);
     int problem, pair;
     if ((a.pairs & 7) == 0) {
         const int per = a.pairs >> 3, x = blockIdx.x & 7, sidx = blockIdx.x >> 3;
@@ -90,7 +54,7 @@ __global__ __launch_bounds__(256) void gemm_f32_tn_group_kernel(GemmGroupArgs a)
         const int per = a.bm * a.bn, q = tile / per, j = tile % per, blocks_n = g.tiles_n / a.bn;
         tile = ((q / blocks_n) * a.bm + j / a.bn) * g.tiles_n + (q % blocks_n) * a.bn + j % a.bn;
     }
-    gemm_tile_tn_direct(g, tile, pair / tiles, threadIdx.x, true);
+    gemm_tile_tn_direct(g, tile, pair / tiles, threadIdx.x);
 }
 
 // A k-contiguous, no LDS (gemm_tile_kc_direct).  Workgroup -> tile: XCD x (= blockIdx % 8) gets a contiguous range of tiles,
@@ -98,12 +62,7 @@ __global__ __launch_bounds__(256) void gemm_f32_tn_group_kernel(GemmGroupArgs a)
 // through its L2.
 template <bool B_KC>
 __global__ __launch_bounds__(256) void gemm_f32_kc_direct_kernel(GemmArgs g) {
-    const int nwg = gridDim.x;
-    int v = blockIdx.x;
-    {
-        const int x = v & 7, q = nwg >> 3, r = nwg & 7;
-        v = x * q + min(x, r) + (v >> 3);
-    }
+    const int v = xcd_contiguous(blockIdx.x, gridDim.x);
     const int tiles = g.tiles_n * g.tiles_m;
     const int split = v / tiles;
     int t = v % tiles, tm, tn;
@@ -119,20 +78,18 @@ __global__ __launch_bounds__(256) void gemm_f32_kc_direct_kernel(GemmArgs g) {
     gemm_tile_kc_direct<B_KC>(g, tm, tn, split, threadIdx.x);
 }
 
-__global__ void fill_strided_kernel(float* C, int M, int N, int ldc, float v) {
+__global__ void gemm_zero_fill_kernel(float* C, int M, int N, int ldc) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (long)M * N) C[(i / N) * ldc + (i % N)] = v;
+    if (i < (long)M * N) C[(i / N) * ldc + (i % N)] = 0.0f;
+}
+void gemm_zero_fill(hipStream_t s, float* C, int M, int N, int ldc) {
+    hipLaunchKernelGGL(gemm_zero_fill_kernel, dim3(ceil_div((long)M * N, 256)), dim3(256), 0, s, C, M, N, ldc);
 }
 
 // ---- the plan: which kernel a product takes and its launch geometry, as plain numbers (amdspeech.h: amdspeech_gemm_plan_info).
 // Every entry point below first PLANS (shape, strides, alignment -> GemmPlan; no pointer is dereferenced, nothing is launched) and
 // then LAUNCHES from that struct; amdspeech_gemm_plan returns the same struct to the caller.  The conditions exist once.
-static GemmPlan plan_blank() {
-    GemmPlan p;
-    memset(&p, 0, sizeof(p));
-    p.splits = 1; p.col_slices = 1;
-    return p;
-}
+// The split-K rule, its constants per family and the blank plan: common.h (plan_blank, split_k, plan_finish).
 
 // C_i [M,N] (+)= A_i^T . B_i for `count` problems of one shape, both operands row contiguous ([K][M], [K][N]); see
 // gemm_tile_tn_direct.
@@ -153,23 +110,10 @@ int gemm_f32_tn_group_plan(int count, int M, int N, int K, const float* A, int l
     p.family = AMDSPEECH_GEMM_TN_DIRECT; p.variant = count;
     p.tiles_m = ceil_div(M, BM); p.tiles_n = ceil_div(N, BN);
     const int tiles = p.tiles_m * p.tiles_n;
-    // one workgroup (one wave per SIMD) per CU keeps the MFMA pipe full here: split K up to 256 workgroups per problem,
-    // no further (every split ends in a tile of f32 atomics)
     static const int target_wgs = dev_knob("AMDSPEECH_GEMM_TN_WGS", 256);
-    int splits = 1;
-    if (tiles * count < target_wgs) {
-        splits = ceil_div(target_wgs, tiles * count);
-        const int max_splits = K / 256 > 0 ? K / 256 : 1;
-        if (splits > max_splits) splits = max_splits;
-    }
-    p.k_chunk = ceil_div(ceil_div(K, splits), 2) * 2;
-    splits = ceil_div(K, p.k_chunk);
-    p.splits = splits;
-    p.atomic = (accumulate || splits > 1) ? 1 : 0;
-    p.zero_fill = (!accumulate && splits > 1) ? 1 : 0;
+    plan_finish(p, split_k(K, tiles * count, target_wgs, target_wgs, 256, 2), tiles * count, accumulate);
     p.a_vec = p.b_vec = 1;
-    const int pairs = tiles * splits;      // (split, tile) pairs per problem
-    p.grid = count * pairs;
+    const int pairs = tiles * p.splits;      // (split, tile) pairs per problem
     // What an XCD's 32 CUs work on at one time (`per` pairs of one split of one problem) decides what crosses the fabric into its L2:
     // a row of `per` tiles streams 1 A strip and `per` B strips, a bm x bn block bm + bn.  The block must tile the output.
 #ifndef GEMM_TN_BLOCKED
@@ -191,17 +135,21 @@ int gemm_f32_tn_group_plan(int count, int M, int N, int K, const float* A, int l
     *out = p;
     return AMDSPEECH_OK;
 }
+// The shape and plan fields of the kernels' argument block; operands, bias, column sums and gate are the launcher's business.
+static GemmArgs gemm_args(const GemmPlan& p, int M, int N, int K, int lda, int ldb, int ldc) {
+    GemmArgs g = GemmArgs();
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n;
+    g.k_chunk = p.k_chunk; g.atomic = p.atomic; g.a_vec = p.a_vec; g.b_vec = p.b_vec;
+    g.gate_limit = 300000000ull;      // 3 s
+    return g;
+}
 static int tn_group_launch(hipStream_t s, const GemmPlan& p, int count, int M, int N, int K, const float* const* A, int lda,
                            const float* const* B, int ldb, float* const* C, int ldc, float* const* colsum,
                            const int* gate, int gate_need, unsigned* gate_err) {
     GemmGroupArgs a;
-    GemmArgs& g = a.g;
-    g.A = nullptr; g.B = nullptr; g.C = nullptr; g.bias = nullptr; g.colsum = nullptr;
-    g.gate = gate; g.gate_need = gate_need; g.gate_limit = 300000000ull; g.gate_err = gate_err;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n;
-    g.k_chunk = p.k_chunk; g.atomic = p.atomic;
-    g.a_vec = g.b_vec = 1; g.xcd_remap = 0;
+    a.g = gemm_args(p, M, N, K, lda, ldb, ldc);
+    a.g.gate = gate; a.g.gate_need = gate_need; a.g.gate_err = gate_err;
     a.count = count; a.pairs = p.grid / count;
     a.bm = p.bm; a.bn = p.bn;
     for (int i = 0; i < GEMM_GROUP_MAX; ++i) {
@@ -209,11 +157,8 @@ static int tn_group_launch(hipStream_t s, const GemmPlan& p, int count, int M, i
         AS_CHECK_ARG(A[j] && B[j] && C[j] && tn_direct_ok(M, N, K, A[j], lda, B[j], ldb), "gemm group: operand %d does not qualify", j);
         a.A[i] = A[j]; a.B[i] = B[j]; a.C[i] = C[j]; a.colsum[i] = colsum ? colsum[j] : nullptr;
     }
-    if (p.zero_fill) {
-        const long n = (long)M * N;
-        for (int i = 0; i < count; ++i)
-            hipLaunchKernelGGL(fill_strided_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, C[i], M, N, ldc, 0.0f);
-    }
+    if (p.zero_fill)
+        for (int i = 0; i < count; ++i) gemm_zero_fill(s, C[i], M, N, ldc);
     // occupancy: an (unused) LDS request caps the workgroups per CU
     // one workgroup = one wave per SIMD per CU: a second streaming wave on a SIMD slows both (8.5 -> 7.3 ms for the two
     // 1024 x 4096 x 64064 products of a cfg3 layer)
@@ -231,9 +176,10 @@ static int tn_group_launch(hipStream_t s, const GemmPlan& p, int count, int M, i
 int gemm_f32_tn_group(hipStream_t s, int count, int M, int N, int K, const float* const* A, int lda, const float* const* B,
                       int ldb, float* const* C, int ldc, float* const* colsum, bool accumulate,
                       const int* gate, int gate_need, unsigned* gate_err) {
-    AS_CHECK_ARG(count >= 1 && count <= GEMM_GROUP_MAX && M > 0 && N > 0 && K > 0, "gemm group: bad shape");
     GemmPlan p;
-    if (int rc = gemm_f32_tn_group_plan(count, M, N, K, A[0], lda, B[0], ldb, C[0], accumulate, &p)) return rc;
+    const bool any = count >= 1;      // (the plan refuses a bad count before it looks at an operand)
+    if (int rc = gemm_f32_tn_group_plan(count, M, N, K, any ? A[0] : nullptr, lda, any ? B[0] : nullptr, ldb, any ? C[0] : nullptr, accumulate, &p))
+        return rc;
     return tn_group_launch(s, p, count, M, N, K, A, lda, B, ldb, C, ldc, colsum, gate, gate_need, gate_err);
 }
 
@@ -253,7 +199,6 @@ int gemm_f32_plan(bool transA, bool transB, int M, int N, int K, const float* A,
     GemmPlan p = plan_blank();
     p.tiles_m = ceil_div(M, BM); p.tiles_n = ceil_div(N, BN);
     const int tiles = p.tiles_m * p.tiles_n;
-    int splits = 1;
     // A k-contiguous (no transA), K a multiple of 64, 16-byte aligned rows, output at least a tile wide, no fused column sums:
     // the LDS-free kernel for the dZ_0 / dX products (transB) and the x.W products
     static const bool kc_direct = runtime_switch("AMDSPEECH_GEMM_KC_DIRECT", 1) != 0;
@@ -263,36 +208,27 @@ int gemm_f32_plan(bool transA, bool transB, int M, int N, int K, const float* A,
         (uintptr_t)A % 16 == 0 && lda % 4 == 0 && (uintptr_t)B % 16 == 0 && ldb % 4 == 0 &&
         (size_t)M * lda * 4 < (1ull << 32) && (size_t)(transB ? N : K + 64) * ldb * 4 < (1ull << 32)) {
         p.family = AMDSPEECH_GEMM_KC_DIRECT; p.variant = transB ? 1 : 0;
-        if (tiles < 192) {
-            splits = ceil_div(256, tiles);
-            if (splits > K / 256) splits = K / 256 > 0 ? K / 256 : 1;
-        }
-        p.k_chunk = ceil_div(ceil_div(K, splits), 64) * 64;
+        plan_finish(p, split_k(K, tiles, 192, 256, 256, 64), tiles, accumulate);
         p.a_vec = p.b_vec = 1;
         // (the kernel always renumbers the workgroups per XCD; the band walk needs whole blocks of 4 column tiles)
         p.map = (p.tiles_n & 3) == 0 ? AMDSPEECH_GEMM_MAP_KC_BAND : AMDSPEECH_GEMM_MAP_XCD;
     } else {
         p.family = AMDSPEECH_GEMM_LDS; p.variant = (transA ? 0 : 2) + (transB ? 1 : 0);      // A_KC * 2 + B_KC
-        // split K until there are >= ~2 workgroups per CU, keeping >= 16 K-tiles per split
         static const int target_wgs = dev_knob("AMDSPEECH_GEMM_WGS", 512);
-        if (tiles < target_wgs) {
-            splits = ceil_div(target_wgs, tiles);
-            const int max_splits = K / (BK * 16) > 0 ? K / (BK * 16) : 1;
-            if (splits > max_splits) splits = max_splits;
-        }
-        p.k_chunk = ceil_div(ceil_div(K, splits), BK) * BK;
+        plan_finish(p, split_k(K, tiles, target_wgs, target_wgs, 16 * BK, BK), tiles, accumulate);
         p.a_vec = ((uintptr_t)A % 16 == 0) && (lda % 4 == 0);
         p.b_vec = ((uintptr_t)B % 16 == 0) && (ldb % 4 == 0);
+        p.map = p.splits > 1 ? AMDSPEECH_GEMM_MAP_XCD : AMDSPEECH_GEMM_MAP_LINEAR;
     }
-    splits = ceil_div(K, p.k_chunk);
-    p.splits = splits;
-    p.atomic = (accumulate || splits > 1) ? 1 : 0;
-    p.zero_fill = (!accumulate && splits > 1) ? 1 : 0;
-    p.grid = tiles * splits;
-    if (p.family == AMDSPEECH_GEMM_LDS) p.map = splits > 1 ? AMDSPEECH_GEMM_MAP_XCD : AMDSPEECH_GEMM_MAP_LINEAR;
     *out = p;
     return AMDSPEECH_OK;
 }
+
+// The kernels by plan variant.  A "KC" = k contiguous = NOT transposed storage [M,K]; B "KC" = stored [N,K] = transposed.
+typedef void (*GemmKernel)(GemmArgs);
+static constexpr GemmKernel LDS_KERNELS[4] = {gemm_f32_kernel<false, false>, gemm_f32_kernel<false, true>,      // A_KC * 2 + B_KC
+                                              gemm_f32_kernel<true, false>, gemm_f32_kernel<true, true>};
+static constexpr GemmKernel KC_DIRECT_KERNELS[2] = {gemm_f32_kc_direct_kernel<false>, gemm_f32_kc_direct_kernel<true>};      // B_KC
 
 int gemm_f32_launch(hipStream_t s, const GemmPlan& p, bool transA, bool transB, int M, int N, int K, const float* A, int lda,
                     const float* B, int ldb, float* C, int ldc, const float* bias, bool accumulate, float* colsum,
@@ -302,41 +238,25 @@ int gemm_f32_launch(hipStream_t s, const GemmPlan& p, bool transA, bool transB, 
     if (p.family == AMDSPEECH_GEMM_SKINNY_TN) return gemm_skinny_tn_launch(s, p, M, N, K, A, lda, B, ldb, C, ldc, accumulate, colsum);
     if (p.family == AMDSPEECH_GEMM_TN_DIRECT)
         return tn_group_launch(s, p, 1, M, N, K, &A, lda, &B, ldb, &C, ldc, colsum ? &colsum : nullptr, gate, gate_need, gate_err);
-    GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.colsum = colsum;
-    g.gate = gate; g.gate_need = gate_need; g.gate_limit = 300000000ull;    // 3 s
-    g.gate_err = gate_err;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n;
-    g.k_chunk = p.k_chunk; g.atomic = p.atomic; g.a_vec = p.a_vec; g.b_vec = p.b_vec;
-    if (p.zero_fill) {
-        const long n = (long)M * N;
-        hipLaunchKernelGGL(fill_strided_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, C, M, N, ldc, 0.0f);
-    }
+    GemmArgs g = gemm_args(p, M, N, K, lda, ldb, ldc);
+    g.A = A; g.B = B; g.C = C; g.bias = bias;
+    if (p.zero_fill) gemm_zero_fill(s, C, M, N, ldc);
     const dim3 grid(p.grid), block(256);
-    if (p.family == AMDSPEECH_GEMM_KC_DIRECT) {
-        g.colsum = nullptr; g.gate = nullptr; g.gate_err = nullptr; g.gate_need = 0; g.gate_limit = 0;
-        g.xcd_remap = 1;
-        if (transB) hipLaunchKernelGGL(gemm_f32_kc_direct_kernel<true>, grid, block, 0, s, g);
-        else hipLaunchKernelGGL(gemm_f32_kc_direct_kernel<false>, grid, block, 0, s, g);
+    if (p.family == AMDSPEECH_GEMM_KC_DIRECT) {      // (never planned with column sums or a gate)
+        hipLaunchKernelGGL(KC_DIRECT_KERNELS[p.variant], grid, block, 0, s, g);
         AS_CHECK_LAUNCH();
         return AMDSPEECH_OK;
     }
-    g.xcd_remap = p.splits > 1 ? 1 : 0;
+    g.colsum = colsum; g.gate = gate; g.gate_need = gate_need; g.gate_err = gate_err;
+    g.xcd_remap = p.map == AMDSPEECH_GEMM_MAP_XCD;
     constexpr size_t lds = (size_t)2 * 2 * BK * LDS_LD * sizeof(float);
     static unsigned long long lds_seen = 0;
     if (DeviceOnce once{&lds_seen}) {
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        for (GemmKernel k : LDS_KERNELS)
+            AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         once.done();
     }
-    // A "KC" = k contiguous = NOT transposed storage [M,K]; B "KC" = stored [N,K] = transposed.
-    if (!transA && !transB) hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, block, lds, s, g);
-    else if (!transA && transB) hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, block, lds, s, g);
-    else if (transA && !transB) hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, block, lds, s, g);
-    else hipLaunchKernelGGL((gemm_f32_kernel<false, true>), grid, block, lds, s, g);
+    hipLaunchKernelGGL(LDS_KERNELS[p.variant], grid, block, lds, s, g);
     AS_CHECK_LAUNCH();
     return AMDSPEECH_OK;
 }
@@ -456,10 +376,7 @@ extern "C" int amdspeech_gemm_plan(int precision, int transA, int transB, int M,
 extern "C" int amdspeech_gemm_f32_tn_group(void* stream, int count, int M, int N, int K, const float* const* A, int lda,
                                            const float* const* B, int ldb, float* const* C, int ldc, float* const* colsum,
                                            int accumulate) {
-    AS_CHECK_ARG(count >= 1 && count <= GEMM_GROUP_MAX && M > 0 && N > 0 && K > 0, "gemm group: bad shape");
-    AS_CHECK_ARG(A && B && C, "gemm group: null operand array");
-    for (int i = 0; i < count; ++i)
-        AS_CHECK_ARG(A[i] && B[i] && C[i] && gemm_f32_tn_group_ok(M, N, K, A[i], lda, B[i], ldb), "gemm group: operand %d does not qualify", i);
+    AS_CHECK_ARG(A && B && C, "gemm group: null operand array");      // (shape and operands: the plan and the launch refuse them)
     return gemm_f32_tn_group(static_cast<hipStream_t>(stream), count, M, N, K, A, lda, B, ldb, C, ldc, colsum, accumulate != 0);
 }
 

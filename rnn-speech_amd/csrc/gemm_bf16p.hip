@@ -18,7 +18,6 @@
 //   3. split K (the weight gradients: M x N = 1024 x 4096 is 64 tiles) writes f32 partial tiles to scratch; one reduce pass adds
 //      them to C (no atomics).
 #include "common.h"
-#include <string.h>
 
 namespace amdspeech {
 namespace {
@@ -301,11 +300,10 @@ size_t bf16p_partial_bytes_max() { return (size_t)SPLIT_TILES_MAX * BM * BN * si
 // The plan of the product kernel (common.h: GemmPlan): tiles, splits and grid as bf16p_gemm launches them and as
 // amdspeech_gemm_bf16_packed_plan reports them (which adds the variant: the copies are not this function's business).
 static GemmPlan bf16p_plan(int M, int N, int K) {
-    GemmPlan p;
-    memset(&p, 0, sizeof(p));
+    GemmPlan p = plan_blank();
     p.family = AMDSPEECH_GEMM_BF16P;
     p.tiles_m = ceil_div(M, BM); p.tiles_n = ceil_div(N, BN);
-    p.col_slices = 1; p.a_vec = p.b_vec = 1;
+    p.a_vec = p.b_vec = 1;
     p.splits = bf16p_splits(M, N, K);
     p.k_chunk = BKT * ceil_div(K / BKT, p.splits);
     p.grid = p.tiles_m * p.tiles_n * p.splits;

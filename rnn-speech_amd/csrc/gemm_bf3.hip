@@ -18,8 +18,6 @@
 // rows = 256 contiguous bytes per instruction) so that a thread owns eight consecutive k of ONE row and writes them as one
 // 16-byte LDS word per plane.  Register-staged one K step ahead of the MFMAs; one 32 KiB LDS stage, three workgroups per CU.
 #include "common.h"
-#include <stdlib.h>
-#include <string.h>
 
 namespace amdspeech {
 
@@ -138,23 +136,14 @@ __global__ __launch_bounds__(256) void gemm_bf3_kernel(Bf3Args g) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     // XCD x (= blockIdx % 8) gets a contiguous range of (split, tile) pairs: it streams ONE K range / neighbouring tiles
-    int v = blockIdx.x;
-    {
-        const int nwg = gridDim.x, x = v & 7, q = nwg >> 3, r = nwg & 7;
-        v = x * q + min(x, r) + (v >> 3);
-    }
+    const int v = xcd_contiguous(blockIdx.x, gridDim.x);
     const int tiles = g.tiles_n * ((g.M + TM - 1) / TM);
     const int tile = v % tiles, split = v / tiles;
     const int m0 = (tile / g.tiles_n) * TM, n0 = (tile % g.tiles_n) * TN;
     const int kbeg = split * g.k_chunk, kend = min(g.K, kbeg + g.k_chunk);
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    zero_acc(acc);
 
     float ra[16], rb[16];
     const int nsteps = (kend - kbeg + TK - 1) / TK;
@@ -229,11 +218,6 @@ __global__ __launch_bounds__(256) void gemm_bf3_kernel(Bf3Args g) {
         }
 }
 
-__global__ void bf3_fill_kernel(float* C, int M, int N, int ldc, float v) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (long)M * N) C[(i / N) * ldc + (i % N)] = v;
-}
-
 }  // namespace
 
 // The plan of the two reduced-precision products (common.h: GemmPlan): this file's kernel, or the exact-f32 ladder's choice.
@@ -249,26 +233,12 @@ int gemm_bf_plan(bool single, bool transA, bool transB, int M, int N, int K, con
                         (!b_kc || (K % TK == 0 && ldb % 4 == 0));
         if (!ok) return gemm_f32_plan(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, false, false, out);
     }
-    GemmPlan p;
-    memset(&p, 0, sizeof(p));
+    GemmPlan p = plan_blank();
     p.family = AMDSPEECH_GEMM_BF3; p.variant = (single ? 4 : 0) + (transA ? 0 : 2) + (transB ? 1 : 0);
     p.tiles_m = ceil_div(M, TM); p.tiles_n = ceil_div(N, TN);
-    p.col_slices = 1; p.a_vec = p.b_vec = 1;
+    p.a_vec = p.b_vec = 1;
     const int tiles = p.tiles_m * p.tiles_n;
-    // split K until every CU has its three workgroups (they overlap each other's phases), as long as a split keeps >= 16 K steps
-    int splits = 1;
-    if (tiles < 768) {
-        splits = ceil_div(768, tiles);
-        const int max_splits = K / (16 * TK);
-        if (splits > max_splits) splits = max_splits;
-        if (splits < 1) splits = 1;
-    }
-    p.k_chunk = ceil_div(ceil_div(K, splits), TK) * TK;
-    splits = ceil_div(K, p.k_chunk);
-    p.splits = splits;
-    p.atomic = (accumulate || splits > 1) ? 1 : 0;
-    p.zero_fill = (!accumulate && splits > 1) ? 1 : 0;
-    p.grid = tiles * splits;
+    plan_finish(p, split_k(K, tiles, 768, 768, 16 * TK, TK), tiles, accumulate);
     *out = p;
     return AMDSPEECH_OK;
 }
@@ -286,37 +256,22 @@ static int gemm_bf_any(hipStream_t s, bool single, bool transA, bool transB, int
     g.tiles_n = p.tiles_n;
     g.k_chunk = p.k_chunk;
     g.atomic = p.atomic;
-    if (p.zero_fill) {
-        const long n = (long)M * N;
-        hipLaunchKernelGGL(bf3_fill_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, C, M, N, ldc, 0.0f);
-    }
+    if (p.zero_fill) gemm_zero_fill(s, C, M, N, ldc);
     constexpr size_t lds = (size_t)STAGE_BYTES;           // 32 KiB
+    // The kernels by plan variant: single * 4 + A_KC * 2 + B_KC.  A "KC" = k contiguous = NOT transposed storage [M,K]; B "KC" = stored
+    // [N,K] = transposed.  (single: the same 32 KiB request -- the lo planes stay unused, the occupancy is what the kernel was tuned at)
+    typedef void (*Bf3Kernel)(Bf3Args);
+    static constexpr Bf3Kernel KERNELS[8] = {
+        gemm_bf3_kernel<false, false>, gemm_bf3_kernel<false, true>, gemm_bf3_kernel<true, false>, gemm_bf3_kernel<true, true>,
+        gemm_bf3_kernel<false, false, true>, gemm_bf3_kernel<false, true, true>, gemm_bf3_kernel<true, false, true>, gemm_bf3_kernel<true, true, true>};
     static unsigned long long seen = 0;
     if (DeviceOnce once{&seen}) {
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf3_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf3_kernel<true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf3_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf3_kernel<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf3_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf3_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf3_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf3_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
+        for (Bf3Kernel k : KERNELS)
+            AS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
         once.done();
     }
-    dim3 grid(p.grid), block(256);
     static const size_t lds_req = (size_t)dev_knob("AMDSPEECH_BF3_LDS", (int)(lds / 1024)) * 1024;      // dev: occupancy probe
-    // A "KC" = k contiguous = NOT transposed storage [M,K]; B "KC" = stored [N,K] = transposed.
-    if (single) {      // (same 32 KiB request: the lo planes stay unused, the occupancy is what the kernel was tuned at)
-        if (!transA && !transB) hipLaunchKernelGGL((gemm_bf3_kernel<true, false, true>), grid, block, lds_req, s, g);
-        else if (!transA && transB) hipLaunchKernelGGL((gemm_bf3_kernel<true, true, true>), grid, block, lds_req, s, g);
-        else if (transA && !transB) hipLaunchKernelGGL((gemm_bf3_kernel<false, false, true>), grid, block, lds_req, s, g);
-        else hipLaunchKernelGGL((gemm_bf3_kernel<false, true, true>), grid, block, lds_req, s, g);
-    } else {
-        if (!transA && !transB) hipLaunchKernelGGL((gemm_bf3_kernel<true, false>), grid, block, lds_req, s, g);
-        else if (!transA && transB) hipLaunchKernelGGL((gemm_bf3_kernel<true, true>), grid, block, lds_req, s, g);
-        else if (transA && !transB) hipLaunchKernelGGL((gemm_bf3_kernel<false, false>), grid, block, lds_req, s, g);
-        else hipLaunchKernelGGL((gemm_bf3_kernel<false, true>), grid, block, lds_req, s, g);
-    }
+    hipLaunchKernelGGL(KERNELS[p.variant], dim3(p.grid), dim3(256), lds_req, s, g);
     AS_CHECK_LAUNCH();
     return AMDSPEECH_OK;
 }

@@ -1,18 +1,24 @@
-// Core of the f32 MFMA GEMM (see gemm.hip): tile constants, argument block, operand staging and the
-// per-tile body as a device function, shared by gemm_f32_kernel and the in-kernel GEMM workers of lstm_bwd_flow.
+// Core of the f32 MFMA GEMM (see gemm.hip), shared by its kernels and the in-kernel GEMM workers of lstm_bwd_flow.  Exports:
+//   BM, BN, BK, KSUB, LDS_LD      tile constants (128 x 128 x 16, one staging round per K tile) and the LDS row pitch
+//   GemmArgs                      the argument block of every tile body
+//   load_tile / store_tile        operand staging of the LDS tile
+//   WorkgroupBarrier, TeamBarrier barrier policies of gemm_tile
+//   gemm_tile<A_KC, B_KC>         one output tile over one K split through LDS, any layout
+//   gemm_tile_tn_direct           ... both operands row contiguous, straight from L2 (GEMM_TN_DEPTH k-pairs ahead)
+//   gemm_tile_kc_direct<B_KC>     ... A k-contiguous, straight from L2
+//   gemm_gate_wait                the bounded wait for a concurrent producer
+//   commit_acc<ROW_IL, COL_IL>    the accumulators' write-out of the LDS-free bodies
+// Every body starts from zero_acc; the LDS-free ones end in commit_acc (zero_acc and xcd_contiguous: common.h).  gemm_tile keeps its
+// staging loops over KSUB and its own write-out: routed through commit_acc, or with the loops written out for KSUB = 1, hipcc moves
+// the register count and the s_waitcnt vmcnt counts of the lstm_bwd_flow2 kernels it is inlined into (gemm_bf3.hip likewise keeps its
+// write-out: 3 VGPRs).
 #pragma once
 #include "common.h"
 #include <type_traits>
 
 namespace amdspeech {
 
-#ifndef GEMM_PRELOAD
-#define GEMM_PRELOAD 0
-#endif
-#ifndef GEMM_BK
-#define GEMM_BK 16
-#endif
-constexpr int BM = 128, BN = 128, BK = GEMM_BK, KSUB = BK / 16;      // a K tile is KSUB sub-tiles of 16 (one staging round each)
+constexpr int BM = 128, BN = 128, BK = 16, KSUB = BK / 16;      // a K tile is KSUB sub-tiles of 16 (one staging round each)
 constexpr int LDS_LD = BM + 4;  // +4 floats: breaks the 128-float stride for the transposing writes
 
 struct GemmArgs {
@@ -29,6 +35,50 @@ struct GemmArgs {
     unsigned long long gate_limit;   // wall_clock64 ticks the wait may last
     unsigned* gate_err;              // bit 2 is raised when the wait times out (the operands are then NOT complete)
 };
+
+// The whole workgroup waits (bounded by wall clock) until the producer has counted *gate down to gate_need.
+__device__ __forceinline__ void gemm_gate_wait(const GemmArgs& g) {
+    if (g.gate != nullptr) {
+        if (threadIdx.x == 0) {
+            const unsigned long long t0 = wall_clock64();
+            bool late = false;
+            while (__hip_atomic_load(g.gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > g.gate_need) {
+                if (wall_clock64() - t0 > g.gate_limit) { late = true; break; }
+                __builtin_amdgcn_s_sleep(32);
+            }
+            if (late && g.gate_err != nullptr) atomicOr(g.gate_err, 4u);
+        }
+        __syncthreads();
+    }
+}
+
+// The 2x2 accumulators' way into C (the LDS-free tile bodies): bias on split 0, row / column bounds, atomics or plain stores as the
+// plan says.  Block (i, j) holds rows i * 32 .. and columns j * 32 .. of the wave's sub-tile -- or, where the fragments came from
+// 8-byte loads of two ADJACENT rows / columns (ROW_IL / COL_IL), the rows 2 x + i / columns 2 x + j.  l32 = lane & 31 and
+// half = lane >> 5 come from the caller: the bodies share them with their load offsets, and a second derivation from the lane costs
+// them two registers.
+template <bool ROW_IL, bool COL_IL>
+__device__ __forceinline__ void commit_acc(const GemmArgs& g, const f32x16 (&acc)[2][2], int m0, int n0, int wm, int wn, int l32, int half, int split) {
+    const bool add_bias = g.bias != nullptr && split == 0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int col = COL_IL ? n0 + wn * 64 + 2 * l32 + j : n0 + wn * 64 + j * 32 + l32;
+            if (col >= g.N) continue;
+            const float bv = add_bias ? g.bias[col] : 0.0f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = ROW_IL ? m0 + wm * 64 + 2 * ((r & 3) + 8 * (r >> 2) + 4 * half) + i
+                                       : m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                if (row >= g.M) continue;
+                float* c = g.C + (size_t)row * g.ldc + col;
+                const float v = acc[i][j][r] + bv;
+                if (g.atomic) unsafeAtomicAdd(c, v);
+                else *c = v;
+            }
+        }
+}
 
 // One operand tile = 128 "rows" (m or n) x 16 k.
 //   KC ("k contiguous"): element (r, k) at P[r*ld + k]
@@ -81,8 +131,7 @@ __device__ __forceinline__ void store_tile(float* __restrict__ S, const float (&
 
 // One 128x128 output tile over one K split: the body of gemm_f32_kernel, also run by the GEMM worker workgroups
 // inside lstm_bwd_flow (two 256-thread teams per 512-thread workgroup, each with its own LDS area and its own
-// TeamBarrier).  `nk_force` > 0 runs exactly that many K tiles (tiles past the split's end load zeros); `commit`
-// false computes but stores nothing.
+// TeamBarrier).
 // Barrier policies of gemm_tile: the whole workgroup (gemm_f32_kernel: one 256-thread team per workgroup), or one
 // 256-thread team of a larger workgroup through an LDS counter (the GEMM workers of lstm_bwd_flow: two teams per
 // workgroup that must NOT run in lock step -- one team's operand staging overlaps the other's MFMAs).
@@ -103,8 +152,7 @@ struct TeamBarrier {
 };
 
 template <bool A_KC, bool B_KC, class Barrier>
-__device__ __forceinline__ void gemm_tile(const GemmArgs& g, int tile, int split, float* smem_base, int tid,
-                                          int nk_force, bool commit, Barrier& bar) {
+__device__ __forceinline__ void gemm_tile(const GemmArgs& g, int tile, int split, float* smem_base, int tid, Barrier& bar) {
     float (*smem)[2][BK * LDS_LD] = reinterpret_cast<float (*)[2][BK * LDS_LD]>(smem_base);   // [buf][A|B]
     const int tm = tile / g.tiles_n, tn = tile % g.tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
@@ -114,19 +162,14 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, int tile, int split
     const int wm = wave >> 1, wn = wave & 1;
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    zero_acc(acc);
 
     float ra[KSUB][8], rb[KSUB][8];
     // bias gradient fused into the weight-gradient GEMM: the first row of tiles also sums its B tile
     // over k (B is dY [K = frames, N]); every B element is visited by exactly one such workgroup
     const bool do_colsum = g.colsum != nullptr && tm == 0 && tid < BN;
     float csum = 0.0f;
-    const int nk = nk_force > 0 ? nk_force : (kend - kbeg + BK - 1) / BK;
+    const int nk = (kend - kbeg + BK - 1) / BK;
     if (nk > 0) {
 #pragma unroll
         for (int u = 0; u < KSUB; ++u) {
@@ -155,24 +198,6 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, int tile, int split
 #pragma unroll
             for (int kk = 0; kk < BK; ++kk) csum += smem[cur][1][kk * LDS_LD + tid];
         }
-#if GEMM_PRELOAD
-        // all fragments of this K tile first (BK x 2 registers), then the MFMAs back to back: the compiler otherwise reuses
-        // four registers and waits for LDS (lgkmcnt(0)) in front of every group of four MFMAs
-        float af[BK / 2][2], bf[BK / 2][2];
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
-            af[kk / 2][0] = As[kk * LDS_LD]; af[kk / 2][1] = As[kk * LDS_LD + 32];
-            bf[kk / 2][0] = Bs[kk * LDS_LD]; bf[kk / 2][1] = Bs[kk * LDS_LD + 32];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int kk = 0; kk < BK / 2; ++kk) {
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk][0], bf[kk][0], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk][0], bf[kk][1], acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk][1], bf[kk][0], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk][1], bf[kk][1], acc[1][1], 0, 0, 0);
-        }
-#else
 #pragma unroll
         for (int kk = 0; kk < BK; kk += 2) {
             float a0 = As[kk * LDS_LD], a1 = As[kk * LDS_LD + 32];
@@ -182,7 +207,6 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, int tile, int split
             acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
             acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
         }
-#endif
         if (kt + 1 < nk) {
 #pragma unroll
             for (int u = 0; u < KSUB; ++u) {
@@ -193,7 +217,6 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, int tile, int split
         bar.sync();
     }
 
-    if (!commit) return;
     if (do_colsum && n0 + (int)tid < g.N) unsafeAtomicAdd(g.colsum + n0 + tid, csum);
     const bool add_bias = g.bias != nullptr && split == 0;
 #pragma unroll
@@ -227,7 +250,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, int tile, int split
 #define GEMM_TN_DEPTH 12
 #endif
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void gemm_tile_tn_direct(const GemmArgs& g, int tile, int split, int tid, bool commit) {
+__device__ __forceinline__ void gemm_tile_tn_direct(const GemmArgs& g, int tile, int split, int tid) {
     constexpr int D = GEMM_TN_DEPTH;
     const int tm = tile / g.tiles_n, tn = tile % g.tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
@@ -256,12 +279,7 @@ __device__ __forceinline__ void gemm_tile_tn_direct(const GemmArgs& g, int tile,
     // "+v" keeps every fragment in ONE physical register for the whole loop; the MFMAs hang on the wait through it.
 #define TN_LOAD(dst, rsrc, vo, so) asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen" : "+v"(dst) : "v"(vo), "s"(rsrc), "s"(so))
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    zero_acc(acc);
     const bool do_colsum = g.colsum != nullptr && tm == 0 && wm == 0;      // (uniform per wave)
     f32x2 cs = {0.0f, 0.0f};
     const int nsteps = (krows + 1) / 2;
@@ -303,7 +321,6 @@ __device__ __forceinline__ void gemm_tile_tn_direct(const GemmArgs& g, int tile,
     if (do_colsum) run(std::true_type{}); else run(std::false_type{});
     float cs0 = cs[0], cs1 = cs[1];
 #undef TN_LOAD
-    if (!commit) return;
     if (do_colsum) {
         cs0 += __shfl_xor(cs0, 32); cs1 += __shfl_xor(cs1, 32);
         const int col = n0 + wn * 64 + 2 * l32;
@@ -312,24 +329,7 @@ __device__ __forceinline__ void gemm_tile_tn_direct(const GemmArgs& g, int tile,
             if (col + 1 < g.N) unsafeAtomicAdd(g.colsum + col + 1, cs1);
         }
     }
-    const bool add_bias = g.bias != nullptr && split == 0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = n0 + wn * 64 + 2 * l32 + j;
-            if (col >= g.N) continue;
-            const float bv = add_bias ? g.bias[col] : 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * 64 + 2 * ((r & 3) + 8 * (r >> 2) + 4 * half) + i;
-                if (row >= g.M) continue;
-                float* c = g.C + (size_t)row * g.ldc + col;
-                const float v = acc[i][j][r] + bv;
-                if (g.atomic) unsafeAtomicAdd(c, v);
-                else *c = v;
-            }
-        }
+    commit_acc<true, true>(g, acc, m0, n0, wm, wn, l32, half, split);
 }
 
 // ---- C[M,N] (+)= A . op(B) with A "k contiguous" ([M][K] row-major: the dZ_0 / dX products A = dG, and every x.W product),
@@ -366,12 +366,7 @@ __device__ __forceinline__ void gemm_tile_kc_direct(const GemmArgs& g, int tile_
 #define KC_LOAD4(dst, rsrc, vo, so) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "+v"(dst) : "v"(vo), "s"(rsrc), "s"(so))
 #define KC_LOAD2(dst, rsrc, vo, so) asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen" : "+v"(dst) : "v"(vo), "s"(rsrc), "s"(so))
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    zero_acc(acc);
     f32x4 fa[D][2];
     f32x4 fbk[B_KC ? D : 1][2];         // NT: B fragments like A's
     f32x2 fbm[B_KC ? 1 : D][4];         // NN: per step one 8-byte load (two columns)
@@ -433,24 +428,7 @@ __device__ __forceinline__ void gemm_tile_kc_direct(const GemmArgs& g, int tile_
     }
 #undef KC_LOAD4
 #undef KC_LOAD2
-    const bool add_bias = g.bias != nullptr && split == 0;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = n0 + wn * 64 + (B_KC ? j * 32 + l32 : 2 * l32 + j);
-            if (col >= g.N) continue;
-            const float bv = add_bias ? g.bias[col] : 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (row >= g.M) continue;
-                float* c = g.C + (size_t)row * g.ldc + col;
-                const float v = acc[i][j][r] + bv;
-                if (g.atomic) unsafeAtomicAdd(c, v);
-                else *c = v;
-            }
-        }
+    commit_acc<false, !B_KC>(g, acc, m0, n0, wm, wn, l32, half, split);
 }
 
 }  // namespace amdspeech

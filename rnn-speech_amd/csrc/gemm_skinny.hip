@@ -19,7 +19,6 @@
 // The k index of MFMA j inside a 16-k group is 4 (lane >> 4) + j for both operands (any permutation of k is a valid product), which
 // is what makes a lane's b128 the operand of four consecutive MFMAs.
 #include "common.h"
-#include <string.h>
 
 namespace amdspeech {
 
@@ -468,11 +467,6 @@ __global__ __launch_bounds__(512) void gemm_skinny_tn_kernel(SkinnyTnArgs g) {
     if (cs_small && tid < g.s) unsafeAtomicAdd(g.colsum + tid, red_cs[tid]);
 }
 
-__global__ void skinny_zero_kernel(float* C, int rows, int cols, int ldc) {
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < (long)rows * cols) C[(e / cols) * ldc + e % cols] = 0.f;
-}
-
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // C[M,N] (+)= A^T . B with A [K,M], B [K,N] (+ colsum[N] += column sums of B).  The plan: true = this kernel takes the product
@@ -492,8 +486,7 @@ bool gemm_skinny_tn_plan(int M, int N, int K, const float* A, int lda, const flo
     const int s_eff = s + ((colsum && small_is_a) ? 1 : 0);
     const int full = s_eff / 64, rt = ceil_div(s_eff - 64 * full, 16);
     if (full > 1 || rt > 4 || full * 8 + rt == 0) return false;
-    GemmPlan p;
-    memset(&p, 0, sizeof(p));
+    GemmPlan p = plan_blank();
     p.family = AMDSPEECH_GEMM_SKINNY_TN; p.variant = full * 8 + rt;
     p.tiles_m = 1; p.tiles_n = ceil_div(wide, 64); p.col_slices = p.tiles_n;
     int nchunks = ceil_div(256, p.tiles_n);
@@ -519,10 +512,7 @@ int gemm_skinny_tn_launch(hipStream_t st, const GemmPlan& p, int M, int N, int K
     g.colsum_small = small_is_a ? 0 : 1;             // (the GEMM's B is the operand whose columns are summed)
     g.nslices = p.tiles_n;
     g.chunk = p.k_chunk;
-    if (p.zero_fill) {
-        const long n = (long)M * N;
-        hipLaunchKernelGGL(skinny_zero_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, C, M, N, ldc);
-    }
+    if (p.zero_fill) gemm_zero_fill(st, C, M, N, ldc);
     const dim3 grid(p.grid), block(512);
     const int full = p.variant / 8, rt = p.variant % 8;
     const size_t lds = (size_t)2 * (4 * full + rt) * 4 * 64 * 16;          // two waves' accumulators (>= red + red_cs)
@@ -567,9 +557,8 @@ bool gemm_skinny_plan(bool transB, int M, int N, int K, const float* A, int lda,
     // (the OUTPUT too: its store offsets are 32-bit with SK_OOB as the "outside" mark -- a wide or strided C of 2 GiB and more
     //  would have its stores dropped or wrapped instead of going to the general kernel)
     if (((size_t)(M - 1) * ldc + N) * 4 >= lim) return false;
-    GemmPlan p;
-    memset(&p, 0, sizeof(p));
-    p.splits = 1; p.col_slices = 1; p.k_chunk = K; p.a_vec = p.b_vec = 1; p.tiles_n = 1;
+    GemmPlan p = plan_blank();
+    p.k_chunk = K; p.a_vec = p.b_vec = 1; p.tiles_n = 1;
     if (K <= 80 && N >= 64) {
         const size_t be = transB ? (size_t)(N - 1) * ldb + K : (size_t)(K - 1) * ldb + N;
         if (be * 4 >= lim) return false;
@@ -601,27 +590,16 @@ int gemm_skinny_launch(hipStream_t s, const GemmPlan& p, bool transB, int M, int
     SkinnyArgs g;
     g.A = A; g.B = B; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.accumulate = accumulate ? 1 : 0;
+    typedef void (*SkinnyKernel)(SkinnyArgs);
     const dim3 block(256);
-    if (p.family == AMDSPEECH_GEMM_SKINNY_K) {
-        const dim3 grid(p.tiles_m, p.col_slices);
-#define SK_K(KT)                                                                                           \
-        do {                                                                                               \
-            if (transB) hipLaunchKernelGGL((gemm_skinny_k_kernel<KT, true>), grid, block, 0, s, g);        \
-            else hipLaunchKernelGGL((gemm_skinny_k_kernel<KT, false>), grid, block, 0, s, g);              \
-        } while (0)
-        if (p.variant / 2 == 3) SK_K(3);
-        else SK_K(5);
-#undef SK_K
-    } else {
-        const dim3 grid(p.grid);
-        switch (p.variant) {
-            case 1: hipLaunchKernelGGL(gemm_skinny_n_kernel<1>, grid, block, 0, s, g); break;
-            case 2: hipLaunchKernelGGL(gemm_skinny_n_kernel<2>, grid, block, 0, s, g); break;
-            case 3: hipLaunchKernelGGL(gemm_skinny_n_kernel<3>, grid, block, 0, s, g); break;
-            case 4: hipLaunchKernelGGL(gemm_skinny_n_kernel<4>, grid, block, 0, s, g); break;
-            case 5: hipLaunchKernelGGL(gemm_skinny_n_kernel<5>, grid, block, 0, s, g); break;
-            default: hipLaunchKernelGGL(gemm_skinny_n_kernel<6>, grid, block, 0, s, g); break;
-        }
+    if (p.family == AMDSPEECH_GEMM_SKINNY_K) {      // variant = KT * 2 + transB, KT = 3 or 5
+        static constexpr SkinnyKernel KERNELS[4] = {gemm_skinny_k_kernel<3, false>, gemm_skinny_k_kernel<3, true>,
+                                                    gemm_skinny_k_kernel<5, false>, gemm_skinny_k_kernel<5, true>};
+        hipLaunchKernelGGL(KERNELS[(p.variant / 2 == 3 ? 0 : 2) + (p.variant & 1)], dim3(p.tiles_m, p.col_slices), block, 0, s, g);
+    } else {                                        // variant = NT = 1 .. 6
+        static constexpr SkinnyKernel KERNELS[6] = {gemm_skinny_n_kernel<1>, gemm_skinny_n_kernel<2>, gemm_skinny_n_kernel<3>,
+                                                    gemm_skinny_n_kernel<4>, gemm_skinny_n_kernel<5>, gemm_skinny_n_kernel<6>};
+        hipLaunchKernelGGL(KERNELS[p.variant >= 1 && p.variant <= 6 ? p.variant - 1 : 5], dim3(p.grid), block, 0, s, g);
     }
     AS_CHECK_LAUNCH();
     return AMDSPEECH_OK;

@@ -110,7 +110,7 @@ __device__ void bwd_gemm_worker(const FlowBwdArgs& a, float* smem, int worker, i
             g.B = dg;
             g.C = a.dk + l * a.kstride + (part ? (size_t)H * 4 * H : 0);
             g.colsum = part == 0 ? a.dbias + l * a.bstride : nullptr;
-            gemm_tile_tn_direct(g, tile, split, tid_, true);     // (no LDS, no barrier: the two teams of a workgroup run free)
+            gemm_tile_tn_direct(g, tile, split, tid_);     // (no LDS, no barrier: the two teams of a workgroup run free)
         };
         if (a.w_counters != nullptr && a.w_mode == 0) {
             // Fused CTC head: the teams that ran ctc_leader arrive here late.  The quarter tiles (one wave each: the tile code has no
@@ -139,7 +139,7 @@ __device__ void bwd_gemm_worker(const FlowBwdArgs& a, float* smem, int worker, i
         g.tiles_n = H / BN; g.atomic = 0; g.k_chunk = 4 * H;
         const int ndz = ((rows + BM - 1) / BM) * g.tiles_n;
         for (int task = team; task < ndz; task += nteams)
-            gemm_tile<true, true>(g, task, 0, lds, tid, 0, true, bar);
+            gemm_tile<true, true>(g, task, 0, lds, tid, bar);
     }
 }
 

@@ -312,6 +312,54 @@ def query(ops, c):
     return ops.gemm_plan(**plan_args(c))
 
 
+# ---- the recorded plan sweep: tests/golden/gemm_plans.npz, written by tools/make_golden.py --gemm-plans from the build of the commit
+# BEFORE a change of the planning code; test_cpu_gemm_ref.py holds today's answers against it, field for field, in both switch modes.
+SWEEP_COLUMNS = ("entry", "precision", "ta", "tb", "M", "N", "K", "lda", "ldb", "ldc", "offa", "offb", "offc", "bias", "acc", "colsum", "count")
+SWEEP_GEMM, SWEEP_PACKED = 0, 1      # column "entry": ops.gemm_plan / ops.gemm_bf16_packed_plan
+SWEEP_FILE = "gemm_plans.npz"
+
+
+def sweep_row(c):
+    """A case of the table above as a row of the sweep."""
+    sh = shapes(c)
+    return (SWEEP_PACKED if c["entry"] == "packed" else SWEEP_GEMM, c["precision"], int(c["ta"]), int(c["tb"]), c["M"], c["N"], c["K"],
+            sh["A"][2], sh["B"][2], sh["C"][2]) + tuple(c["off"]) + (int(bool(c["bias"])), int(c["acc"]),
+            int(c["colsum"] and c["entry"] != "tn_group"), c["count"])
+
+
+def sweep_call(ops, row):
+    """The plan query one row names (ld* in elements; off*: element offset of the nominal address, 1 = aligned to 4 bytes only)."""
+    r = dict(zip(SWEEP_COLUMNS, (int(v) for v in row)))
+    a = (r["K"], r["M"]) if r["ta"] else (r["M"], r["K"])
+    b = (r["N"], r["K"]) if r["tb"] else (r["K"], r["N"])
+    if r["entry"] == SWEEP_PACKED:
+        return ops.gemm_bf16_packed_plan(a + (r["lda"],), b + (r["ldb"],), trans_a=bool(r["ta"]), trans_b=bool(r["tb"]))
+    return ops.gemm_plan(a=a + (r["lda"], 4096 + 4 * r["offa"]), b=b + (r["ldb"], 4096 + 4 * r["offb"]),
+                         out=(r["M"], r["N"], r["ldc"], 4096 + 4 * r["offc"]), trans_a=bool(r["ta"]), trans_b=bool(r["tb"]), bias=bool(r["bias"]),
+                         accumulate=bool(r["acc"]), colsum=bool(r["colsum"]), count=r["count"], precision=r["precision"])
+
+
+def sweep_answers(ops, calls, fields, messages):
+    """Today's answer to every row: (plans [n, len(fields)] int32 with the family as its index in lib.GEMM_FAMILIES, status [n] int32).
+    status -1: planned; >= 0: refused (the plan row stays zero), with the index of the message's CLASS -- the library's text with every
+    word that is a number replaced by '#' -- in `messages`, which is extended by classes it does not hold yet."""
+    from rnn_speech_amd import lib
+    plans = np.zeros((len(calls), len(fields)), np.int32)
+    status = np.full(len(calls), -1, np.int32)
+    for i, row in enumerate(calls):
+        try:
+            p = sweep_call(ops, row)
+        except lib.AmdSpeechError as e:
+            cls = " ".join("#" if word.isdigit() else word for word in str(e).split("): ", 1)[1].split(" "))
+            if cls not in messages:
+                messages.append(cls)
+            status[i] = messages.index(cls)
+            continue
+        p["family"] = lib.GEMM_FAMILIES.index(p["family"])
+        plans[i] = [p[f] for f in fields]
+    return plans, status
+
+
 def arith(c, plan):
     """How a product carries one operand value: "f32" (all 24 bits; also where reduced precision falls back to the f32 ladder),
     "bf16x3" (hi + lo) or "bf16"."""

@@ -60,6 +60,48 @@ def test_every_expected_plan_under_the_fallback_switches(ops):
     assert all(c["plan"]["fallback"]["family"] == "lds" for c in PLANNED if "fallback" in c["plan"])
 
 
+def sweep_mismatches(ops, mode):
+    """Rows of tests/golden/gemm_plans.npz whose recorded answer (plan fields, or refusal and message class) is not today's."""
+    from rnn_speech_amd import lib
+    g = np.load(os.path.join(ROOT, "tests", "golden", R.SWEEP_FILE))
+    fields, messages = [str(f) for f in g["fields"]], [str(m) for m in g["messages"]]
+    assert tuple(str(c) for c in g["columns"]) == R.SWEEP_COLUMNS and fields == [n for n, _ in lib.GemmPlanInfo._fields_]
+    assert tuple(str(f) for f in g["families"]) == lib.GEMM_FAMILIES
+    plans, status = R.sweep_answers(ops, g["calls"], fields, messages)
+    want_plans, want_status = g["plans_" + mode], g["status_" + mode]
+    bad = np.flatnonzero((plans != want_plans).any(1) | (status != want_status))
+    text = lambda s: "planned" if s < 0 else "refused: " + messages[s]
+    return [(dict(zip(R.SWEEP_COLUMNS, g["calls"][i].tolist())), text(want_status[i]), text(status[i]),
+             {f: (int(w), int(p)) for f, w, p in zip(fields, want_plans[i], plans[i]) if w != p}) for i in bad[:20]], len(status)
+
+
+def test_every_recorded_plan_of_the_sweep_is_todays_plan(ops):
+    """The file was written by the build of the commit before the planning code was last restructured (tools/make_golden.py
+    --gemm-plans): 79 thousand calls over shapes, layouts, options, strides and alignments."""
+    from rnn_speech_amd import lib
+    assert os.environ.get("AMDSPEECH_GEMM_DIRECT", "1") != "0" and os.environ.get("AMDSPEECH_GEMM_KC_DIRECT", "1") != "0"
+    g = np.load(os.path.join(ROOT, "tests", "golden", R.SWEEP_FILE))
+    planned = g["plans_default"][g["status_default"] < 0]
+    seen = {(lib.GEMM_FAMILIES[f], int(v)) for f, v in np.unique(planned[:, :2], axis=0)}
+    assert {f for f, _ in seen} == set(lib.GEMM_FAMILIES) and set(R.VARIANTS) <= seen
+    assert (g["status_default"] >= 0).sum() > 1000 and len({str(m) for m in g["messages"]}) >= 3      # refusals are recorded as such
+    fallback = {lib.GEMM_FAMILIES[f] for f in np.unique(g["plans_fallback"][g["status_fallback"] < 0][:, 0])}
+    assert "lds" in fallback and not fallback & {"tn_direct", "kc_direct"}      # (the second mode was recorded with the switches off)
+    bad, n = sweep_mismatches(ops, "default")
+    assert n == len(g["calls"]) > 50000 and not bad, bad
+
+
+def test_every_recorded_plan_of_the_sweep_under_the_fallback_switches(ops):
+    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import test_cpu_gemm_ref as T\nfrom rnn_speech_amd import ops\n"
+            "bad, n = T.sweep_mismatches(ops, 'fallback')\nprint('FALLBACK-SWEEP', n, bad)\n"
+            "sys.exit(1 if bad else 0)\n" % (ROOT, os.path.join(ROOT, "tests")))
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **R.FALLBACK_ENV), capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    n = len(np.load(os.path.join(ROOT, "tests", "golden", R.SWEEP_FILE))["calls"])
+    assert "FALLBACK-SWEEP %d []" % n in out.stdout, out.stdout[-2000:]
+
+
 def test_the_table_reaches_every_variant_and_every_launch_property(ops):
     from rnn_speech_amd import lib
     assert R.GROUP_MAX == lib.GEMM_GROUP_MAX

@@ -11,6 +11,7 @@ reference-generated vectors ("parity unpinned" -- see oracle/*.py headers).
 
 Usage:  python tools/make_golden.py
         python tools/make_golden.py --checkpoints <checkout of 9bbf15b>     (checkpoint_*.npz only; needs no reference)
+        AMDSPEECH_LIB=<libamdspeech.so of the parent commit> python tools/make_golden.py --gemm-plans     (gemm_plans.npz only; no reference, no GPU)
 """
 import json
 import os
@@ -211,7 +212,81 @@ def checkpoint_goldens(root):
         print(name, len(np.load(os.path.join(OUT, name)).files), "keys")
 
 
+def gemm_plan_sweep():
+    """The rows of tests/golden/gemm_plans.npz (tests/gemm_ref.py: SWEEP_COLUMNS).  Every K; of the 14 x 14 (M, N) pairs the diagonal and
+    every pair with (i + 2 j) % 7 == 0 (the full grid is ~1.2 M calls: past the size a committed file may have) -- every value still
+    stands on both axes; every call option; the plain placement and one of the six others in turn.  The case table of gemm_ref goes in
+    whole, so that no (family, variant) it names can be thinned away."""
+    import gemm_ref as R
+    MN = (1, 2, 40, 80, 96, 97, 124, 127, 128, 129, 256, 512, 1024, 4096)
+    KS = (1, 16, 31, 32, 64, 80, 255, 256, 1024, 2048, 4095, 4096, 19860, 32032, 63872)
+    # (pad of lda, ldb, ldc; element offset of A, B, C): ld = cols / cols + 1 / cols + 4, an address aligned to 16 / to 4 only
+    PLACES = ((0, 0, 0, 0, 0, 0), (1, 0, 0, 0, 0, 0), (0, 1, 0, 0, 0, 0), (4, 4, 4, 0, 0, 0), (0, 0, 0, 1, 0, 0), (0, 0, 0, 0, 1, 0),
+              (0, 0, 1, 0, 0, 1))
+    rows, turn = [R.sweep_row(c) for c in R.CASES if c["entry"] not in R.UNPLANNED], 0
+    for i, M in enumerate(MN):
+        for j, N in enumerate(MN):
+            if i != j and (i + 2 * j) % 7 != 0:
+                continue
+            for K in KS:
+                for ta in (0, 1):
+                    for tb in (0, 1):
+                        cols = (M if ta else K, K if tb else N, N)
+                        options = [(p, bias, acc, 0, 1) for p in (0, 1, 2) for bias in (0, 1) for acc in (0, 1)]
+                        if not tb:      # fused column sums: exact f32, B stored [K][N]
+                            options += [(0, bias, acc, 1, 1) for bias in (0, 1) for acc in (0, 1)]
+                        if ta and not tb:      # the grouped entry
+                            options += [(0, 0, acc, 0, count) for acc in (0, 1) for count in (2, 10)]
+                        for precision, bias, acc, colsum, count in options:
+                            turn += 1
+                            for place in (PLACES[0], PLACES[1 + turn % 6]):
+                                ld = tuple(c + p for c, p in zip(cols, place[:3]))
+                                rows.append((R.SWEEP_GEMM, precision, ta, tb, M, N, K) + ld + place[3:] + (bias, acc, colsum, count))
+                        for pad in (0, 1, 4):
+                            rows.append((R.SWEEP_PACKED, 2, ta, tb, M, N, K, cols[0] + pad, cols[1] + pad, N, 0, 0, 0, 0, 0, 0, 1))
+    return np.asarray(rows, np.int32)
+
+
+def gemm_plan_goldens(child_out=None):
+    """tests/golden/gemm_plans.npz: what ops.gemm_plan / ops.gemm_bf16_packed_plan answer over gemm_plan_sweep(), with the switches at
+    their defaults (in this process) and with AMDSPEECH_GEMM_DIRECT=0 AMDSPEECH_GEMM_KC_DIRECT=0 (read once per process: a child).
+    Needs no GPU -- the query dereferences nothing -- and no reference.  Run it on the build of the commit BEFORE a change of the
+    planning code (AMDSPEECH_LIB=<that build's libamdspeech.so>), never on the tree under test."""
+    import subprocess
+    import tempfile
+    root = os.path.dirname(OUT)
+    sys.path[:0] = [os.path.dirname(root), root]
+    import gemm_ref as R
+    from rnn_speech_amd import lib, ops
+    fields = [n for n, _ in lib.GemmPlanInfo._fields_]
+    calls, messages = gemm_plan_sweep(), []
+    plans, status = R.sweep_answers(ops, calls, fields, messages)
+    if child_out is not None:      # (the child: its answers and message classes go back through a file)
+        np.savez(child_out, plans=plans, status=status, messages=np.asarray(messages, dtype=str))
+        return
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "fallback.npz")
+        subprocess.check_call([sys.executable, os.path.abspath(__file__), "--gemm-plans-child", path], env=dict(os.environ, **R.FALLBACK_ENV))
+        child = np.load(path)
+        child_messages = [str(m) for m in child["messages"]]
+        for m in child_messages:
+            if m not in messages:
+                messages.append(m)
+        fb_status = np.asarray([-1 if s < 0 else messages.index(child_messages[s]) for s in child["status"]], np.int32)
+        fb_plans = child["plans"]
+    np.savez_compressed(os.path.join(OUT, R.SWEEP_FILE), columns=np.asarray(R.SWEEP_COLUMNS, dtype=str), fields=np.asarray(fields, dtype=str),
+                        families=np.asarray(lib.GEMM_FAMILIES, dtype=str), messages=np.asarray(messages, dtype=str), calls=calls,
+                        plans_default=plans, status_default=status, plans_fallback=fb_plans, status_fallback=fb_status)
+    seen = sorted({(lib.GEMM_FAMILIES[f], int(v)) for f, v in plans[status < 0][:, :2]})
+    print(R.SWEEP_FILE, len(calls), "calls,", int((status >= 0).sum()), "refused,", os.path.getsize(os.path.join(OUT, R.SWEEP_FILE)), "bytes")
+    print("message classes:", messages)
+    print("variants:", seen)
+
+
 if __name__ == "__main__":
+    if "--gemm-plans" in sys.argv or "--gemm-plans-child" in sys.argv:      # AMDSPEECH_LIB=<parent build> python tools/make_golden.py --gemm-plans
+        gemm_plan_goldens(sys.argv[sys.argv.index("--gemm-plans-child") + 1] if "--gemm-plans-child" in sys.argv else None)
+        sys.exit(0)
     if "--checkpoints" in sys.argv:      # python tools/make_golden.py --checkpoints <checkout of 9bbf15b>
         checkpoint_goldens(os.path.abspath(sys.argv[sys.argv.index("--checkpoints") + 1]))
         sys.exit(0)
