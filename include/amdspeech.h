@@ -953,6 +953,61 @@ int amdspeech_feature_moments(void* stream, const float* x, const int* n_frames,
 int amdspeech_feature_norm(void* stream, float* x, const int* n_frames, int B, int D, int t_in,
                            const amdspeech_feature_norm_desc* desc, const double* table, void* workspace);
 
+/* ------------------------------------------------------ lookahead convolution ---
+ * A row convolution above the top layer of a UNIDIRECTIONAL LSTM stack (Deep Speech 2's "lookahead convolution"; no reference
+ * counterpart: an opt-in deviation, off at context 0, where no caller makes these calls and no parameter exists): a depth-wise
+ * filter over the next `context` frames, one weight per future frame and hidden unit.  (context + 1) * H parameters, no bias, no
+ * activation.
+ *   x, y, dy, dx  float [T][B][H]        time-major, contiguous
+ *   w, dw         float [context + 1][H]
+ *   lengths       int32 [B] (DEVICE)     frames of each row;  Lb = min(lengths[b], T), a negative length counts as 0
+ *   context       1 .. 32
+ *   fwd:  y[t][b][h]  = sum_{j = 0 .. context, t + j < Lb} w[j][h] * x[t + j][b][h]      for t < Lb,   0 for t >= Lb
+ *   bwd:  dx[t][b][h] = sum_{j = 0 .. context, t - j >= 0} w[j][h] * dy[t - j][b][h]     for t < Lb,   0 for t >= Lb
+ *         dw[j][h]   += sum_b sum_{t, t + j < Lb} dy[t][b][h] * x[t + j][b][h]            (ACCUMULATES, as amdspeech_linear_bwd does)
+ * The arithmetic: every element of y and dx is ONE chain of fmaf in ascending j that starts from the rounded product of the j = 0
+ * tap; taps outside the row are not added at all (they are not zeros that take part).  With w[0] = 1 and w[j > 0] = 0, y therefore
+ * equals x as numbers wherever t < Lb.  dw is summed in three fixed stages: per (time chunk, row b) one fmaf chain in ascending t
+ * over the at most `dw_terms` frames of the chunk (a partial [context + 1][H] tile in the workspace); per element `reduce_slices`
+ * plain float sums, each over a contiguous run of at most `reduce_terms` partials in index order (index = chunk * B + b); the slices
+ * added in slice order, and one add into dw.  No floating-point atomics anywhere: y, dx and dw are bit-identical from run to run
+ * and do not depend on what else the chip is doing.
+ * y and dx are written in EVERY element; frames of x and dy at or past Lb are never read and may hold anything (NaN included).
+ * The workspace is written in every word the second stage reads: it needs no fill.  Asynchronous on `stream`; nothing is copied to
+ * the host.  Three launches backward (dx, the dw partials, their sum), one forward.
+ * Each kernel walks time with a sliding window of context + 1 frames in LDS: a frame is loaded from memory once per time chunk, and
+ * a chunk re-reads only its halo of `context` frames (at most a quarter of `t_chunk`).
+ * AMDSPEECH_EINVAL with a message and no launch: null pointers (the workspace included), non-positive sizes, B * H or T * B >= 2^31,
+ * a context outside 1 .. 32, x / y ranges that overlap (fwd), dy / dx or x / dx ranges that overlap (bwd).
+ * amdspeech_lookahead_bwd_workspace_bytes: bytes of `ws` (device, caller-allocated, 16-byte aligned for the 16-byte path); 0 for a
+ * shape the calls refuse.  The figure covers the shape and every SHORTER T at the same B, H and context (a caller sizes it once
+ * for its padded length): min(ceil(1024 / col_blocks), ceil(T / the chunk floor)) * B tiles of (context + 1) * H floats, which is
+ * at least dw_partials tiles.
+ * amdspeech_lookahead_plan: the launch geometry as plain numbers, a READ-ONLY view of the plan the launches themselves read (one
+ * function decides for all of them); no device is needed, the shape is checked as the calls check it.
+ *   vec                words per lane and access: 4 when H % 4 == 0, else 1.  The query assumes 16-byte aligned bases; a call whose
+ *                      x, w, y (bwd: x, w, dy, dx, ws) are not all 16-byte aligned plans with 1 instead -- its chunks are then no
+ *                      more than the query's, so the queried workspace still covers it
+ *   unroll             frames per block of the walk = independent loads in flight per lane (8)
+ *   col_blocks         workgroups along a [B][H] frame: ceil(B * H / vec / 64), 64 threads each, lanes along the frame
+ *   t_chunk, chunks    frames per time chunk, the same for all three walks: ceil(T / ceil(1024 / col_blocks)) so that the grid covers
+ *                      the chip, but at least 4 * context, rounded up to whole blocks;  chunks = ceil(T / t_chunk)
+ *   workgroups         col_blocks * chunks: of the forward launch, of the dx launch and of the dw-partials launch
+ *   lds_bytes          dynamic LDS of each of those: (2 * context + unroll + 1) * 64 * vec * 4 -- the window ring and, beside it,
+ *                      the lane's weights (fwd, dx) or its running dw sums
+ *   dw_partials        partial dw tiles in the workspace = chunks * B;   dw_terms: frames summed into one = t_chunk
+ *   reduce_slices      threads per dw element in the second stage (8);   reduce_terms: partials per slice = ceil(dw_partials / 8)
+ *   reduce_workgroups  of 256 threads: ceil((context + 1) * H / 32)                                                              */
+typedef struct amdspeech_lookahead_plan_info {
+    int vec, unroll, col_blocks, t_chunk, chunks, workgroups, lds_bytes, dw_partials, dw_terms, reduce_slices, reduce_terms, reduce_workgroups;
+} amdspeech_lookahead_plan_info;
+int amdspeech_lookahead_fwd(void* stream, const float* x, const float* w, const int* lengths, int T, int B, int H, int context,
+                            float* y);
+size_t amdspeech_lookahead_bwd_workspace_bytes(int T, int B, int H, int context);
+int amdspeech_lookahead_bwd(void* stream, const float* x, const float* w, const float* dy, const int* lengths, int T, int B, int H,
+                            int context, float* dx, float* dw, void* ws);
+int amdspeech_lookahead_plan(int T, int B, int H, int context, amdspeech_lookahead_plan_info* out);
+
 /* ------------------------------------------- voice activity / long recordings ---
  * What cuts a recording LONGER than the model's input at its pauses (no reference counterpart: an opt-in deviation, config key
  * long_audio; nothing of it is called at the key's default): frame energies of raw PCM, speech flags from an adaptive threshold,

@@ -220,6 +220,8 @@ class AcousticModel(checkpoint.TrainedModel):
         # with the MODEL length (AudioProcessor.out_seq_length) and input_dim = AudioProcessor.feature_size; evaluate_full builds
         # its AudioProcessor from them
         self.frame_stack = self.frame_skip = 1
+        # config key `lookahead_context`: future frames the row convolution above the top layer reads (Engine(lookahead=...)); 0: none
+        self.lookahead_context = 0
         # config keys `feature_norm` / `feature_norm_variance` / `feature_norm_stats`: feature normalisation in front of the frame
         # stacking (AudioProcessor).  The model only reads normalised features; evaluate_full builds its AudioProcessor from these
         self.feature_norm, self.feature_norm_variance, self.feature_stats = "none", True, None
@@ -250,7 +252,7 @@ class AcousticModel(checkpoint.TrainedModel):
                              self.batch_size, self.max_input_seq_length, self.max_target_seq_length,
                              normalization=bool(self.normalization), precision=self.precision,
                              bidirectional=bool(self.bidirectional), sync_batch_norm=bool(self.sync_batch_norm),
-                             bidirectional_mode=self.bidirectional_mode)
+                             bidirectional_mode=self.bidirectional_mode, lookahead=int(self.lookahead_context))
         self.rnn_created = True
 
     def create_forward_rnn(self):

@@ -12,7 +12,8 @@ import os
 import numpy as np
 
 TF_NAMES = {"input_w": "Input_Layer/input_w", "input_b": "Input_Layer/input_b",
-            "output_w": "Output_layer/output_w", "output_b": "Output_layer/output_b"}
+            "output_w": "Output_layer/output_w", "output_b": "Output_layer/output_b",
+            "lookahead_w": "Lookahead_Layer/lookahead_w"}       # (the row convolution's taps; only a model with lookahead > 0 has them)
 
 
 def tf_name(name, layerwise=False):

@@ -24,12 +24,13 @@ def _pad64(n):
 
 
 class ParamLayout(object):
-    """Flat fp32 layout [input_w | input_b | (kernel_l | bias_l)*L | output_w | output_b],
+    """Flat fp32 layout [input_w | input_b | (kernel_l | bias_l)*L | output_w | output_b | lookahead_w (lookahead > 0 only)],
     every tensor starting on a 256-byte boundary (pads are zero and stay zero)."""
 
-    def __init__(self, num_layers, hidden, input_dim, num_labels, bidirectional=False, bidirectional_mode="top"):
+    def __init__(self, num_layers, hidden, input_dim, num_labels, bidirectional=False, bidirectional_mode="top", lookahead=0):
         self.L, self.H, self.D, self.C = num_layers, hidden, input_dim, num_labels
         self.bidirectional = bool(bidirectional)
+        self.lookahead = int(lookahead)
         # "layer" (stack_bidirectional_dynamic_rnn): the cells above layer 0 read [h_fw ; h_bw], kernels (3H, 4H) there -- the stride
         # between layers is not uniform (kernel_stride / bias_stride are None)
         self.layerwise = self.bidirectional and bidirectional_mode == "layer"
@@ -58,6 +59,8 @@ class ParamLayout(object):
                 take("bw_bias_%d" % l, (4 * hidden,))
         take("output_w", ((2 if self.bidirectional else 1) * hidden, num_labels))
         take("output_b", (num_labels,))
+        if self.lookahead > 0:           # the row convolution's taps: LAST, so that no other tensor moves when the option is on
+            take("lookahead_w", (self.lookahead + 1, hidden))
         self.total = off
         if self.layerwise:
             self.kernel_stride = self.bias_stride = None
@@ -117,13 +120,16 @@ class ParamStore(object):
         return self.layout.view(self.grads, name)
 
     def init_parameters(self, seed=1234):
-        """Xavier/Glorot-uniform matrices, zero biases (TF defaults, :241-244,302-305)."""
+        """Xavier/Glorot-uniform matrices, zero biases (TF defaults, :241-244,302-305).  The lookahead taps start as the identity
+        (w[0] = 1, the future taps 0) and draw nothing: every other tensor has the values it has without them."""
         gen = torch.Generator(device="cpu")
         gen.manual_seed(seed)
         self.params.zero_()
         for name in self.layout.names():
             _, shape = self.layout.slots[name]
-            if len(shape) == 2:
+            if name == "lookahead_w":
+                self.p(name)[0].fill_(1.0)
+            elif len(shape) == 2:
                 lim = math.sqrt(6.0 / (shape[0] + shape[1]))
                 w = (torch.rand(shape, generator=gen) * 2.0 - 1.0) * lim
                 self.p(name).copy_(w)
@@ -176,7 +182,7 @@ class ParamStore(object):
 class Engine(ParamStore):
     def __init__(self, num_layers, hidden, input_dim, num_labels, batch_size, max_T, max_U,
                  device="cuda", seed=1234, normalization=False, precision="f32", bidirectional=False,
-                 sync_batch_norm=False, bidirectional_mode="top"):
+                 sync_batch_norm=False, bidirectional_mode="top", lookahead=0):
         if not torch.cuda.is_available():
             raise RuntimeError("rnn_speech_amd needs a ROCm GPU (MI355X); there is no CPU path")
         self.L, self.H, self.D, self.C = num_layers, hidden, input_dim, num_labels
@@ -193,8 +199,16 @@ class Engine(ParamStore):
         if self.layerwise and precision not in ("f32", "bf16x3"):
             raise ValueError("bidirectional_mode 'layer' runs in exact f32 or bf16x3 (precision %r requested): the layer-wise kernels "
                              "have no plain-bf16 variant" % (precision,))
+        # lookahead (row) convolution between the top layer and the output layer (ops.lookahead_fwd; no reference counterpart, off at
+        # 0: nothing of it is allocated or launched): `lookahead` future frames of context for a model that stays unidirectional
+        self.lookahead = int(lookahead)
+        if not 0 <= self.lookahead <= ops.LOOKAHEAD_MAX_CONTEXT:
+            raise ValueError("lookahead must be 0 (off) .. %d future frames, not %r" % (ops.LOOKAHEAD_MAX_CONTEXT, lookahead))
+        if self.lookahead and self.bidirectional:
+            raise ValueError("lookahead %d with a bidirectional model: the row convolution gives a UNIDIRECTIONAL stack its future "
+                             "context; a bidirectional stack already reads the whole utterance" % self.lookahead)
         ParamStore.__init__(self, ParamLayout(num_layers, hidden, input_dim, num_labels, bidirectional=self.bidirectional,
-                                              bidirectional_mode="layer" if self.layerwise else "top"), device)
+                                              bidirectional_mode="layer" if self.layerwise else "top", lookahead=self.lookahead), device)
         if precision not in PRECISIONS:
             raise ValueError("precision must be 'f32' (exact, default), 'bf16x3' (split-precision MFMA) or 'bf16' (plain bf16 "
                              "operands, f32 accumulation and master weights)")
@@ -208,6 +222,10 @@ class Engine(ParamStore):
                                                precision=PRECISIONS[precision])
             self.ytop_b = torch.empty(max_T, batch_size, hidden, device=self.device)      # backward stack's output, in forward time
             self.dytop_b = torch.empty(max_T, batch_size, hidden, device=self.device)
+        if self.lookahead:               # f32 in every precision mode
+            self.la_y = torch.empty(max_T, batch_size, hidden, device=self.device)        # the convolution's output: what the output layer reads
+            self.la_dy = torch.empty(max_T, batch_size, hidden, device=self.device)
+            self.la_ws = ops.LookaheadWorkspace(max_T, batch_size, hidden, self.lookahead, device=self.device)
         self.ctc_ws = ops.CtcWorkspace(max_T, batch_size, num_labels, max_U, self.device)
         self.logits = torch.empty(max_T, batch_size, num_labels, device=self.device)
         self.dlogits = torch.empty_like(self.logits)
@@ -284,7 +302,7 @@ class Engine(ParamStore):
         # log-softmax and alpha follow the forward recurrence, beta and the gradient lead the backward one
         self._per_diagonal = bool(per_diagonal)
         self._head = None
-        if (dense_labels is not None and _FUSED_CTC and not self.bidirectional
+        if (dense_labels is not None and _FUSED_CTC and not self.bidirectional and not self.lookahead
                 and ops.lstm_ctc_fusable(ws, self.C, dense_labels.shape[1], per_diagonal=per_diagonal)):
             self._head = ops.CtcHead(self.p("output_w"), self.p("output_b"), self.logits[:Tr], dense_labels, self.loss,
                                      self.dlogits[:Tr], self.ctc_ws)
@@ -306,8 +324,11 @@ class Engine(ParamStore):
         if not self.bidirectional:
             if after_lstm is not None:
                 after_lstm()           # (mini_batch: from here on other streams may use the chip -- see beside_ctc)
+            top = ws.ztop
+            if self.lookahead:           # (the fused head is never taken with it: the output layer reads the convolution's output)
+                top = ops.lookahead_fwd(ws.ztop, self.p("lookahead_w"), lengths, out=self.la_y[:Tr])
             if self._head is None:
-                ops.linear_fwd(ws.ztop.view(Tr * B, H), self.p("output_w"), self.p("output_b"),
+                ops.linear_fwd(top.view(Tr * B, H), self.p("output_w"), self.p("output_b"),
                                out=self.logits[:Tr].view(Tr * B, self.C))
         else:
             # backward-direction stack on the time-reversed input-layer output (its own dropout stream; it always starts
@@ -353,9 +374,10 @@ class Engine(ParamStore):
         """Which shape-driven choices the LAST forward made -- what a parity test has to assert before it may claim to have checked
         them: `fused_ctc_head` (the CTC stage ran inside the two whole-sequence LSTM launches, ops.CtcHead), `paired` (a
         bidirectional model's two stacks side by side on one-XCD groups, ops.lstm_fwd_pair), `run_length` (frames visited), and
-        `lstm_fwd` / `lstm_bwd`: the kernel path of that forward and of the backward that belongs to it ("flow", "big1", "big",
-        "hoist", "diag", "diag_bf3": ops.lstm_plan at the run length, with the head and the per-diagonal request of the call)."""
-        path = {"fused_ctc_head": self._head is not None, "paired": self._paired, "run_length": self._Tr}
+        `lookahead` (the row convolution's context, 0 = none: with it the fused head is never taken), `lstm_fwd` / `lstm_bwd`: the
+        kernel path of that forward and of the backward that belongs to it ("flow", "big1", "big", "hoist", "diag", "diag_bf3":
+        ops.lstm_plan at the run length, with the head and the per-diagonal request of the call)."""
+        path = {"fused_ctc_head": self._head is not None, "lookahead": self.lookahead, "paired": self._paired, "run_length": self._Tr}
         if not self.layerwise:
             plan = ops.lstm_plan(self._ws, head=self._head, per_diagonal=self._per_diagonal)
             # (side by side: ops.lstm_fwd_pair runs the one-XCD forward kernel whatever one stack alone would take)
@@ -435,6 +457,11 @@ class Engine(ParamStore):
             raise _lib.AmdSpeechError("backward(per_diagonal=True) after a forward with the fused CTC head: repeat the forward too")
         if head is not None:
             pass                         # dlogits and dZ_top are formed inside lstm_bwd; dW_o / db_o follow it
+        elif self.lookahead:             # the output layer read the convolution's output; its dx is the convolution's dy
+            ops.linear_bwd(self.la_y[:Tr].view(Tr * B, H), self.p("output_w"), dl,
+                           self.g("output_w"), self.g("output_b"), need_dx=True, dx=self.la_dy[:Tr].view(Tr * B, H))
+            ops.lookahead_bwd(ws.ztop, self.p("lookahead_w"), self.la_dy[:Tr], lengths, dx=ws.dztop, dw=self.g("lookahead_w"),
+                              ws=self.la_ws)
         elif not self.bidirectional:
             ops.linear_bwd(ws.ztop.view(Tr * B, H), self.p("output_w"), dl,
                            self.g("output_w"), self.g("output_b"), need_dx=True, dx=ws.dztop.view(Tr * B, H))

@@ -1,6 +1,6 @@
 """config.ini reader + checkpoint-side pickle logic (reference:
 /root/reference/util/hyperparams.py:17-141).  Same section/key names and defaults; a few
-optional keys are added for the MI355X build (n_mfcc, sample_rate, frame_stack / frame_skip, feature_norm*, spec_augment_*,
+optional keys are added for the MI355X build (n_mfcc, sample_rate, frame_stack / frame_skip, lookahead_context, feature_norm*, spec_augment_*,
 speed_perturb_*, noise_* / reverb_* / augment_*, long_audio / vad_* ...) and the reference's [lm_network_params] section with this build's lm_* keys."""
 import configparser
 import logging
@@ -12,11 +12,13 @@ _ACOUSTIC, _GENERAL, _TRAINING, _LOGGING = "acoustic_network_params", "general",
 # a change of any of these makes an existing checkpoint unusable (the reference compares the first four,
 # util/hyperparams.py:75-92; n_mfcc / sample_rate are this build's extra keys and change the input layer's
 # shape / the features' meaning; so do frame_stack / frame_skip, the low frame rate input, and feature_norm /
-# feature_norm_variance: a model trained on normalised features is useless on raw ones.  The statistics file's path is not)
+# feature_norm_variance: a model trained on normalised features is useless on raw ones.  The statistics file's path is not.
+# lookahead_context adds a parameter tensor and a layer)
 _STRUCTURAL = ("num_layers", "hidden_size", "signal_processing", "language", "n_mfcc", "sample_rate", "bidirectional",
-               "bidirectional_mode", "frame_stack", "frame_skip", "feature_norm", "feature_norm_variance")
+               "bidirectional_mode", "frame_stack", "frame_skip", "feature_norm", "feature_norm_variance", "lookahead_context")
 _STRUCTURAL_DEFAULTS = {"signal_processing": "mfcc", "language": "", "n_mfcc": 20, "sample_rate": 22050, "bidirectional": False,
-                        "bidirectional_mode": "top", "frame_stack": 1, "frame_skip": 1, "feature_norm": "none", "feature_norm_variance": True}
+                        "bidirectional_mode": "top", "frame_stack": 1, "frame_skip": 1, "feature_norm": "none", "feature_norm_variance": True,
+                        "lookahead_context": 0}
 
 
 def read_config_file(config_file):
@@ -65,6 +67,12 @@ def read_config_file(config_file):
     # (1 / 1: off, the reference's behaviour).  max_input_seq_length stays in source frames
     for key in ("frame_stack", "frame_skip"):
         d[key] = check_range(key, cp.getint(_ACOUSTIC, key, fallback=1), 1, 16)
+    # lookahead (row) convolution above the top layer of a unidirectional stack (ops.lookahead_fwd): future model frames each output
+    # frame sees.  0: off, the reference's graph
+    d["lookahead_context"] = check_range("lookahead_context", cp.getint(_ACOUSTIC, "lookahead_context", fallback=0), 0, 32)
+    if d["lookahead_context"] and d["bidirectional"]:
+        raise ValueError("lookahead_context : %d with bidirectional : True -- the row convolution gives a unidirectional stack its "
+                         "future context; a bidirectional one already reads the whole utterance" % d["lookahead_context"])
     # feature normalisation between the front end and the frame stacking (ops.feature_norm): none (the reference's behaviour) |
     # utterance (mean / variance of the utterance itself) | global (of the training corpus, from the file feature_norm_stats names,
     # which `stt.py --feature_stats` writes).  feature_norm_variance False: means only

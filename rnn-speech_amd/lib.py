@@ -79,6 +79,11 @@ class FeatureNormPlanInfo(C.Structure):     # amdspeech_feature_norm_plan_info (
     _fields_ = [(n, C.c_int) for n in ("vec", "split", "workgroups", "lds_bytes", "meta_by_copy", "workspace_bytes")]
 
 
+class LookaheadPlanInfo(C.Structure):     # amdspeech_lookahead_plan_info (include/amdspeech.h): the launch geometry of the lookahead-convolution calls, read-only
+    _fields_ = [(n, C.c_int) for n in ("vec", "unroll", "col_blocks", "t_chunk", "chunks", "workgroups", "lds_bytes", "dw_partials", "dw_terms",
+                                       "reduce_slices", "reduce_terms", "reduce_workgroups")]
+
+
 class VadPlanInfo(C.Structure):     # amdspeech_vad_plan_info (include/amdspeech.h): the launch geometry of the voice-activity calls, read-only
     _fields_ = [(n, C.c_int) for n in ("load_vec", "frames_per_tile", "tiles_per_row", "workgroups", "threads", "f_max", "select_passes",
                                        "row_workgroups", "row_threads", "meta_by_copy")]
@@ -236,6 +241,10 @@ PROTOTYPES = {
     "amdspeech_feature_norm_plan": (_I, [_I, _I, _I, _I, C.POINTER(FeatureNormPlanInfo)]),
     "amdspeech_feature_moments": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "amdspeech_feature_norm": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(FeatureNormDesc), _P, _P]),
+    "amdspeech_lookahead_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "amdspeech_lookahead_bwd_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "amdspeech_lookahead_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "amdspeech_lookahead_plan": (_I, [_I, _I, _I, _I, C.POINTER(LookaheadPlanInfo)]),
     "amdspeech_vad_num_frames": (_I, [_I, _I]),
     "amdspeech_vad_workspace_bytes": (_SZ, [_I, _I, _I]),
     "amdspeech_vad_plan": (_I, [_I, _I, _I, C.POINTER(VadPlanInfo)]),

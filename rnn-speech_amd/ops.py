@@ -1270,6 +1270,79 @@ def feature_norm(feat, n_frames, mode, norm_vars=True, var_floor=FEATURE_NORM_VA
     return feat
 
 
+# ------------------------------------------------------------ lookahead convolution
+LOOKAHEAD_MAX_CONTEXT = 32
+
+
+def lookahead_plan(T, B, H, context):
+    """The launch geometry of `lookahead_fwd` / `lookahead_bwd` for a shape (amdspeech.h: amdspeech_lookahead_plan), as a dict of ints
+    with "workspace_bytes" (amdspeech_lookahead_bwd_workspace_bytes) beside the struct's fields.  Read-only: nothing is launched, no
+    device is needed.  A shape the calls refuse raises here too."""
+    info = _l.LookaheadPlanInfo()
+    lib = _l.load()
+    _l.check(lib.amdspeech_lookahead_plan(int(T), int(B), int(H), int(context), C.byref(info)), "lookahead_plan")
+    out = _plan_dict(info)
+    out["workspace_bytes"] = int(lib.amdspeech_lookahead_bwd_workspace_bytes(int(T), int(B), int(H), int(context)))
+    return out
+
+
+class LookaheadWorkspace(object):
+    """The partial weight-gradient tiles of lookahead_bwd for calls of up to T frames (a shorter run length needs no more).  The call
+    writes every word it reads: no fill."""
+
+    def __init__(self, T, B, H, context, device="cuda"):
+        self.shape = (T, B, H, context)
+        n = lookahead_plan(T, B, H, context)["workspace_bytes"]
+        self.buf = torch.empty(max(n, 16), device=device, dtype=torch.uint8)
+
+    def fits(self, T, B, H, context):
+        return self.shape[1:] == (B, H, context) and T <= self.shape[0]
+
+
+def _lookahead_args(what, x, w, lengths, others):
+    T, B, H = _chk_f32_3d(what, x, "[T, B, H]")
+    _chk_f32(w, *others)
+    _chk_i32(lengths)
+    if w.dim() != 2 or w.shape[1] != H or w.shape[0] < 2:
+        raise ValueError("%s: w %s is not [context + 1, %d]" % (what, tuple(w.shape), H))
+    if lengths.numel() != B:
+        raise ValueError("%s: %d lengths for %d rows" % (what, lengths.numel(), B))
+    for t in others:
+        if t is not None and tuple(t.shape) != (T, B, H):
+            raise ValueError("%s: a tensor of shape %s beside x %s" % (what, tuple(t.shape), (T, B, H)))
+    return T, B, H, w.shape[0] - 1
+
+
+def lookahead_fwd(x, w, lengths, out=None):
+    """y [T,B,H] = the row convolution of x [T,B,H] with w [context+1, H] over each row's own frames, zeros past its length
+    (amdspeech.h: amdspeech_lookahead_fwd).  lengths: int32 [B] on the device."""
+    T, B, H, context = _lookahead_args("lookahead_fwd", x, w, lengths, (out,))
+    if out is None:
+        out = torch.empty_like(x)
+    _l.check(_l.load().amdspeech_lookahead_fwd(_stream(), _p(x), _p(w), _p(lengths), T, B, H, context, _p(out)), "lookahead_fwd")
+    return out
+
+
+def lookahead_bwd(x, w, dy, lengths, dx=None, dw=None, ws=None):
+    """dx [T,B,H] (written in every element) and dw [context+1, H] += the weight gradient (amdspeech.h: amdspeech_lookahead_bwd).
+    Returns (dx, dw); a dw made here starts from zeros."""
+    T, B, H, context = _lookahead_args("lookahead_bwd", x, w, lengths, (dy, dx))
+    if dy is None:
+        raise ValueError("lookahead_bwd: dy is required")
+    _chk_f32(dw)
+    if dx is None:
+        dx = torch.empty_like(x)
+    if dw is None:
+        dw = torch.zeros_like(w)
+    if tuple(dw.shape) != tuple(w.shape):
+        raise ValueError("lookahead_bwd: dw %s beside w %s" % (tuple(dw.shape), tuple(w.shape)))
+    if ws is None or not ws.fits(T, B, H, context):
+        ws = LookaheadWorkspace(T, B, H, context, x.device)
+    _l.check(_l.load().amdspeech_lookahead_bwd(_stream(), _p(x), _p(w), _p(dy), _p(lengths), T, B, H, context, _p(dx), _p(dw), _p(ws.buf)),
+             "lookahead_bwd")
+    return dx, dw
+
+
 # ------------------------------------------------------------ voice activity / long recordings
 _vad_ws = {}
 

@@ -188,6 +188,7 @@ def _set_model_options(model, hyper_params):
     model.precision = hyper_params.get("precision", "f32")
     model.bidirectional = hyper_params.get("bidirectional", False)
     model.bidirectional_mode = hyper_params.get("bidirectional_mode", "top")
+    model.lookahead_context = hyper_params.get("lookahead_context", 0)
     model.sync_batch_norm = hyper_params.get("sync_batch_norm", False)
     model.spec_augment = hyper_params.get("spec_augment")       # (build_audio_processor; only run_step with gradients masks)
     opts = pipeline_options(hyper_params)                       # (evaluate_full builds its AudioProcessor from these five)
