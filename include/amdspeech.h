@@ -1008,6 +1008,64 @@ int amdspeech_lookahead_bwd(void* stream, const float* x, const float* w, const 
                             int context, float* dx, float* dw, void* ws);
 int amdspeech_lookahead_plan(int T, int B, int H, int context, amdspeech_lookahead_plan_info* out);
 
+/* ------------------------------------------- time-frequency convolution (front) ---
+ * A strided 2-D convolution between the features and the input Linear (Deep Speech 2's convolutional front; no reference
+ * counterpart: an opt-in deviation, off at 0 channels, where no caller makes these calls and no parameter exists).  "Same" padding,
+ * pt = (kt - 1) / 2, pf = (kf - 1) / 2; the clipped ReLU min(max(., 0), 20).  First layer of the model: there is no dx.
+ *   x             float [T][B][G][F]     the front end's frame seen as G groups of F bins (fbank: 3 x 40, mfcc: 1 x n_mfcc)
+ *   w, dw         float [K][C]           K = G * kt * kf, row k = (g * kt + i) * kf + j
+ *   bias, db      float [C]
+ *   y, dy         float [T'][B][F' * C]  T' = ceil(T / st), F' = ceil(F / sf), channel fastest
+ *   lengths       int32 [B] (DEVICE)     source frames of each row;  Lb = min(max(lengths[b], 0), T)
+ *   lengths_out   int32 [B] (DEVICE)     L'b = ceil(Lb / st), written by the forward launch
+ *   G 1 .. 3, F 1 .. 128, C 16 | 32 | 48 | 64, kt odd 1 .. 11, kf odd 1 .. 41, st and sf 1 .. 4, F' * C <= 4096
+ *   fwd:  pre[t'][b][f'][c] = bias[c] + sum_{g,i,j} w[k][c] * x[t' st + i - pt][b][g][f' sf + j - pf]
+ *                              over the terms whose source frame lies in 0 .. Lb - 1 and whose source bin lies in 0 .. F - 1
+ *         y[t'][b][f' C + c] = min(max(pre, 0), 20) for t' < L'b,  0 for t' >= L'b
+ *   bwd:  mask = 0 < y < 20 (read from y itself: no pre-activation is kept)
+ *         dw[k][c] += sum_{b, t' < L'b, f'} patch_k(t', b, f') * dy * mask      db[c] += sum dy * mask      (both ACCUMULATE, as
+ *         amdspeech_linear_bwd does)
+ * The arithmetic is a matrix product on v_mfma_f32_16x16x4_f32, exact f32: every pre is one f32 accumulation chain over the k_pad
+ * products in ascending k (terms outside the row or the band take part as exact zeros; K is padded to a multiple of 4 with zero
+ * weights), then one add of the bias.  dw and db are summed in three fixed stages: per partial one chain over at most `dw_terms`
+ * output positions (tiles in index order t'-tile * B + b, positions in order inside a tile); per element `reduce_slices` plain sums
+ * over contiguous runs of at most `reduce_terms` partials; the slices in slice order and one add into the output.  No
+ * floating-point atomics: y, dw and db are bit-identical from run to run.
+ * y is written in EVERY element; frames of x at or past Lb and frames of y / dy at or past L'b are never read and may hold anything
+ * (NaN included).  The workspace is written in every word the second stage reads: it needs no fill.  Asynchronous on `stream`;
+ * nothing is copied to the host.  One launch forward, two backward.
+ * AMDSPEECH_EINVAL with a message and no launch: null pointers (workspace included), sizes outside the ranges above, T * B * G * F or
+ * T' * B * F' * C >= 2^31, B > 65535, x / y ranges that overlap (fwd), dw / db / workspace ranges that overlap (bwd).
+ * amdspeech_conv2d_bwd_workspace_bytes: bytes of `ws` (device, caller-allocated, 4-byte aligned); 0 for a shape the calls refuse.
+ * The figure covers the shape and every SHORTER T at the same other sizes: dw_partials only grows with T.
+ * amdspeech_conv2d_plan: the launch geometry as plain numbers, a READ-ONLY view of the plan the launches themselves read (one
+ * function decides for all of them); no device is needed, the shape is checked as the calls check it.
+ *   t_out, f_out       T', F'
+ *   k, k_pad           K and K rounded up to the instruction's k of 4 (zero weights)
+ *   tile_t, tile_f     output frames and bins of one tile: tile_f = F' (all bins), tile_t = floor(128 / F'), fewer where the source
+ *                      span of the tile, ((tile_t - 1) st + kt) * G * (F + 2 pf) words, would not fit LDS beside the other tenants
+ *                      of either pass.  Independent of T and B.  A tile is one row b
+ *   vec                words per global access (1: there is no vector path, any 4-byte aligned base takes the same kernels)
+ *   fwd_workgroups     ceil(T' / tile_t) * B, 256 threads each;   fwd_lds_bytes: patch + k offsets + the weight chunk
+ *   weights_resident   1: the whole [k_pad][C] passes through LDS once per workgroup (k_chunk = k_pad); 0: streamed from L2 in chunks
+ *                      of k_chunk = 64 rows
+ *   k_rows, k_groups   rows of a partial tile, K + 1 (the bias row) rounded up to 16, and workgroups along them (256 rows each)
+ *   dw_partials        partial tiles = min(tiles, ceil(512 / k_groups));   bwd_workgroups = dw_partials * k_groups
+ *   bwd_lds_bytes      patch + position offsets + dy * mask of one tile
+ *   dw_terms           output positions summed into one partial: ceil(tiles / dw_partials) * tile_t * F'
+ *   reduce_slices      threads per element in the second stage (8);   reduce_terms = ceil(dw_partials / 8)
+ *   reduce_workgroups  of 256 threads: ceil((K + 1) * C / 32)                                                                     */
+typedef struct amdspeech_conv2d_plan_info {
+    int t_out, f_out, k, k_pad, tile_t, tile_f, vec, fwd_workgroups, fwd_lds_bytes, weights_resident, k_chunk, k_rows, k_groups,
+        dw_partials, bwd_workgroups, bwd_lds_bytes, dw_terms, reduce_slices, reduce_terms, reduce_workgroups;
+} amdspeech_conv2d_plan_info;
+int amdspeech_conv2d_fwd(void* stream, const float* x, const float* w, const float* bias, const int* lengths, int T, int B, int G, int F,
+                         int C, int kt, int kf, int st, int sf, float* y, int* lengths_out);
+size_t amdspeech_conv2d_bwd_workspace_bytes(int T, int B, int G, int F, int C, int kt, int kf, int st, int sf);
+int amdspeech_conv2d_bwd(void* stream, const float* x, const float* y, const float* dy, const int* lengths, int T, int B, int G, int F,
+                         int C, int kt, int kf, int st, int sf, float* dw, float* db, void* ws);
+int amdspeech_conv2d_plan(int T, int B, int G, int F, int C, int kt, int kf, int st, int sf, amdspeech_conv2d_plan_info* out);
+
 /* ------------------------------------------- voice activity / long recordings ---
  * What cuts a recording LONGER than the model's input at its pauses (no reference counterpart: an opt-in deviation, config key
  * long_audio; nothing of it is called at the key's default): frame energies of raw PCM, speech flags from an adaptive threshold,

@@ -222,6 +222,11 @@ class AcousticModel(checkpoint.TrainedModel):
         self.frame_stack = self.frame_skip = 1
         # config key `lookahead_context`: future frames the row convolution above the top layer reads (Engine(lookahead=...)); 0: none
         self.lookahead_context = 0
+        # config keys `conv_channels` / `conv_kernel` / `conv_stride`: the strided time-frequency convolution between the features and
+        # the input Linear (Engine(conv=...)), None (off) or (C, kt, kf, st, sf, G).  With it the model is still constructed with
+        # the SOURCE length and width and fed source frames and lengths; the engine's logits are ceil(T / st) model frames, and
+        # everything that reads them takes the model lengths (Engine.model_lengths)
+        self.conv = None
         # config keys `feature_norm` / `feature_norm_variance` / `feature_norm_stats`: feature normalisation in front of the frame
         # stacking (AudioProcessor).  The model only reads normalised features; evaluate_full builds its AudioProcessor from these
         self.feature_norm, self.feature_norm_variance, self.feature_stats = "none", True, None
@@ -252,7 +257,7 @@ class AcousticModel(checkpoint.TrainedModel):
                              self.batch_size, self.max_input_seq_length, self.max_target_seq_length,
                              normalization=bool(self.normalization), precision=self.precision,
                              bidirectional=bool(self.bidirectional), sync_batch_norm=bool(self.sync_batch_norm),
-                             bidirectional_mode=self.bidirectional_mode, lookahead=int(self.lookahead_context))
+                             bidirectional_mode=self.bidirectional_mode, lookahead=int(self.lookahead_context), conv=self.conv)
         self.rnn_created = True
 
     def create_forward_rnn(self):
@@ -432,6 +437,15 @@ class AcousticModel(checkpoint.TrainedModel):
         a = np.asarray(lengths)
         return int(a.max()) if a.size else None
 
+    def _model_lengths_host(self, lengths):
+        """Host lengths in model frames: ceil(n / st) behind the front convolution, the lengths themselves without it."""
+        a = np.asarray(lengths)
+        return a if self.conv is None else -(-np.maximum(a, 0) // self.conv[3])
+
+    def _model_lengths_dev(self, dlen):
+        """... and on the device, for what reads the logits of the forward pass just queued (Engine.model_lengths)."""
+        return dlen if self.conv is None else self.engine.model_lengths(dlen)
+
     def _to_device(self, inputs, lengths, dense):
         dev = self.engine.device
         x = inputs if torch.is_tensor(inputs) else torch.as_tensor(np.asarray(inputs, np.float32))
@@ -482,7 +496,7 @@ class AcousticModel(checkpoint.TrainedModel):
             if self._async_beam is None:
                 self._async_beam = _AsyncBeamDecoder(eng, self.beam_width, self.merge_repeated, self.train_decoder_lag)
 
-            def decode_hook(after, _self=self, _lengths=lengths, _dense=dense):
+            def decode_hook(after, _self=self, _lengths=self._model_lengths_host(lengths), _dense=dense):
                 # (the logits of THIS mini-batch exist behind `after`: their way to the host starts beside the CTC stage)
                 _self._async_beam.submit(after, eng._Tr, _lengths, _dense, _self.num_labels)
                 return None
@@ -503,7 +517,7 @@ class AcousticModel(checkpoint.TrainedModel):
             # another mini-batch, so that no rank ever enters a gradient all-reduce the others skip
             self._next_agreed = grp.all_true(self._has_next())
         # the error rate's kernels go out BEFORE the loss is read back: one drain of the stream covers both read-backs
-        pending_err = self._error_rate_launch(dlen, dense) if (self.compute_error_rate and not use_async) else None
+        pending_err = self._error_rate_launch(self._model_lengths_dev(dlen), dense) if (self.compute_error_rate and not use_async) else None
         loss = eng.loss.cpu().numpy().astype(np.float64)
         mini_batch_valid = True                               # (an invalid mini-batch adds nothing to the logged loss / error rate)
         if not eng.healthy():                                 # (the stream is drained by the read-back above)
@@ -538,7 +552,7 @@ class AcousticModel(checkpoint.TrainedModel):
                 eng.mini_batch(x, dlen, dlab, keep[0], keep[1], seed=self._dropout_seed, use_state=True,
                                compute_gradients=compute_gradients, max_len=self._host_max(lengths),
                                beside_ctc=decode_hook, per_diagonal=True)
-                pending_err = self._error_rate_launch(dlen, dense) if (self.compute_error_rate and not use_async) else None
+                pending_err = self._error_rate_launch(self._model_lengths_dev(dlen), dense) if (self.compute_error_rate and not use_async) else None
                 loss = eng.loss.cpu().numpy().astype(np.float64)
                 if not eng.healthy() or not np.all(np.isfinite(loss[np.asarray(lengths) > 0])):
                     mini_batch_valid = False
@@ -548,7 +562,7 @@ class AcousticModel(checkpoint.TrainedModel):
         if mini_batch_valid:
             eng.keep_state()                                  # rnn_keep_state_op, fetched on every step (:642)
             with np.errstate(divide="ignore", invalid="ignore"):
-                self._acc_loss += float(np.mean(loss / np.asarray(lengths, np.float64)))   # :361
+                self._acc_loss += float(np.mean(loss / np.asarray(self._model_lengths_host(lengths), np.float64)))   # :361 (per model frame)
             self._loss_batches += 1
         if pending_err is not None:
             dist, tlen = pending_err
@@ -735,7 +749,7 @@ class AcousticModel(checkpoint.TrainedModel):
         if self._async_beam is not None:
             self._async_beam.guard(torch.cuda.current_stream(self.engine.device))
         self.engine.forward(x, dlen, max_len=self._host_max(input_seq_lengths))
-        pred = self._decode(dlen)          # (reads the result back: the stream is drained)
+        pred = self._decode(self._model_lengths_dev(dlen))          # (reads the result back: the stream is drained)
         self.engine.check()                # a bounded-wait time-out of the dataflow kernels invalidates the logits
         return pred
 
@@ -744,7 +758,8 @@ class AcousticModel(checkpoint.TrainedModel):
         """Forced alignment: inputs [T_max, B, D], lengths [B], labels the transcripts' token ids (a 0-padded dense matrix
         [B, U] as the labels placeholder takes it, or one id list per utterance; an EOS ends a transcript).  Returns per utterance
         a list of (token, first_frame, last_frame, confidence) in transcript order, confidence = exp(mean log p of the token over
-        its frames); the list is empty for an utterance the CTC loss would ignore or whose transcript cannot be aligned."""
+        its frames); the list is empty for an utterance the CTC loss would ignore or whose transcript cannot be aligned.  Frames
+        are MODEL frames: behind the front convolution frame t is centred on source frame t * st."""
         U = self.max_target_seq_length
         dense = np.zeros((self.batch_size, U), np.int32)
         for b, row in enumerate(labels):

@@ -13,7 +13,8 @@ import numpy as np
 
 TF_NAMES = {"input_w": "Input_Layer/input_w", "input_b": "Input_Layer/input_b",
             "output_w": "Output_layer/output_w", "output_b": "Output_layer/output_b",
-            "lookahead_w": "Lookahead_Layer/lookahead_w"}       # (the row convolution's taps; only a model with lookahead > 0 has them)
+            "lookahead_w": "Lookahead_Layer/lookahead_w",       # (the row convolution's taps; only a model with lookahead > 0 has them)
+            "conv_w": "Conv_Layer/conv_w", "conv_b": "Conv_Layer/conv_b"}       # (the front convolution; only a model with conv_channels > 0)
 
 
 def tf_name(name, layerwise=False):

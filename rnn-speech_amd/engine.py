@@ -24,13 +24,15 @@ def _pad64(n):
 
 
 class ParamLayout(object):
-    """Flat fp32 layout [input_w | input_b | (kernel_l | bias_l)*L | output_w | output_b | lookahead_w (lookahead > 0 only)],
-    every tensor starting on a 256-byte boundary (pads are zero and stay zero)."""
+    """Flat fp32 layout [input_w | input_b | (kernel_l | bias_l)*L | output_w | output_b | lookahead_w (lookahead > 0 only) |
+    conv_w | conv_b (conv only)], every tensor starting on a 256-byte boundary (pads are zero and stay zero).  `input_dim` is the
+    width the input Linear reads: with `conv` = (C, kt, kf, st, sf, G) that is F' * C, the convolution's output."""
 
-    def __init__(self, num_layers, hidden, input_dim, num_labels, bidirectional=False, bidirectional_mode="top", lookahead=0):
+    def __init__(self, num_layers, hidden, input_dim, num_labels, bidirectional=False, bidirectional_mode="top", lookahead=0, conv=None):
         self.L, self.H, self.D, self.C = num_layers, hidden, input_dim, num_labels
         self.bidirectional = bool(bidirectional)
         self.lookahead = int(lookahead)
+        self.conv = tuple(int(v) for v in conv) if conv else None
         # "layer" (stack_bidirectional_dynamic_rnn): the cells above layer 0 read [h_fw ; h_bw], kernels (3H, 4H) there -- the stride
         # between layers is not uniform (kernel_stride / bias_stride are None)
         self.layerwise = self.bidirectional and bidirectional_mode == "layer"
@@ -61,6 +63,10 @@ class ParamLayout(object):
         take("output_b", (num_labels,))
         if self.lookahead > 0:           # the row convolution's taps: LAST, so that no other tensor moves when the option is on
             take("lookahead_w", (self.lookahead + 1, hidden))
+        if self.conv:                    # the front convolution's filter bank and bias: behind everything else, for the same reason
+            c, kt, kf, _, _, g = self.conv
+            take("conv_w", (g * kt * kf, c))
+            take("conv_b", (c,))
         self.total = off
         if self.layerwise:
             self.kernel_stride = self.bias_stride = None
@@ -121,7 +127,8 @@ class ParamStore(object):
 
     def init_parameters(self, seed=1234):
         """Xavier/Glorot-uniform matrices, zero biases (TF defaults, :241-244,302-305).  The lookahead taps start as the identity
-        (w[0] = 1, the future taps 0) and draw nothing: every other tensor has the values it has without them."""
+        (w[0] = 1, the future taps 0) and draw nothing: every other tensor has the values it has without them.  The front
+        convolution's filters are Glorot-uniform over their receptive fields: fan-in K = G kt kf, fan-out kt kf C."""
         gen = torch.Generator(device="cpu")
         gen.manual_seed(seed)
         self.params.zero_()
@@ -131,6 +138,9 @@ class ParamStore(object):
                 self.p(name)[0].fill_(1.0)
             elif len(shape) == 2:
                 lim = math.sqrt(6.0 / (shape[0] + shape[1]))
+                if name == "conv_w":
+                    c, kt, kf = self.layout.conv[:3]
+                    lim = math.sqrt(6.0 / (shape[0] + kt * kf * c))
                 w = (torch.rand(shape, generator=gen) * 2.0 - 1.0) * lim
                 self.p(name).copy_(w)
 
@@ -182,9 +192,21 @@ class ParamStore(object):
 class Engine(ParamStore):
     def __init__(self, num_layers, hidden, input_dim, num_labels, batch_size, max_T, max_U,
                  device="cuda", seed=1234, normalization=False, precision="f32", bidirectional=False,
-                 sync_batch_norm=False, bidirectional_mode="top", lookahead=0):
+                 sync_batch_norm=False, bidirectional_mode="top", lookahead=0, conv=None):
         if not torch.cuda.is_available():
             raise RuntimeError("rnn_speech_amd needs a ROCm GPU (MI355X); there is no CPU path")
+        # strided time-frequency convolution between the features and the input Linear (ops.conv2d_fwd; no reference counterpart,
+        # off at None: nothing of it is allocated or launched).  conv = (C, kt, kf, st, sf, G).  The caller hands SOURCE frames
+        # [T_in, B, D_in = G * F] and source lengths; everything from the input Linear on sees T = ceil(T_in / st) model frames of
+        # D = ceil(F / sf) * C values and the model lengths the convolution's launch writes (model_lengths)
+        self.conv = tuple(int(v) for v in conv) if conv else None
+        self.T_in, self.D_in = max_T, input_dim
+        if self.conv:
+            c, kt, kf, st, sf, g = self.conv
+            if g < 1 or input_dim % g:
+                raise ValueError("conv: %d feature groups do not divide the %d values of a source frame" % (g, input_dim))
+            ops.conv2d_check(c, kt, kf, st, sf, F=input_dim // g)
+            max_T, input_dim = ops.conv2d_out_shape(max_T, input_dim // g, c, st, sf)
         self.L, self.H, self.D, self.C = num_layers, hidden, input_dim, num_labels
         self.B, self.T, self.U = batch_size, max_T, max_U
         # bidirectional (BASELINE configs[4]; no reference counterpart -- the reference builds a unidirectional dynamic_rnn,
@@ -208,7 +230,8 @@ class Engine(ParamStore):
             raise ValueError("lookahead %d with a bidirectional model: the row convolution gives a UNIDIRECTIONAL stack its future "
                              "context; a bidirectional stack already reads the whole utterance" % self.lookahead)
         ParamStore.__init__(self, ParamLayout(num_layers, hidden, input_dim, num_labels, bidirectional=self.bidirectional,
-                                              bidirectional_mode="layer" if self.layerwise else "top", lookahead=self.lookahead), device)
+                                              bidirectional_mode="layer" if self.layerwise else "top", lookahead=self.lookahead,
+                                              conv=self.conv), device)
         if precision not in PRECISIONS:
             raise ValueError("precision must be 'f32' (exact, default), 'bf16x3' (split-precision MFMA) or 'bf16' (plain bf16 "
                              "operands, f32 accumulation and master weights)")
@@ -226,6 +249,12 @@ class Engine(ParamStore):
             self.la_y = torch.empty(max_T, batch_size, hidden, device=self.device)        # the convolution's output: what the output layer reads
             self.la_dy = torch.empty(max_T, batch_size, hidden, device=self.device)
             self.la_ws = ops.LookaheadWorkspace(max_T, batch_size, hidden, self.lookahead, device=self.device)
+        if self.conv:                    # f32 in every precision mode
+            c, kt, kf, st, sf, g = self.conv
+            self.cv_y = torch.empty(max_T, batch_size, input_dim, device=self.device)     # the convolution's output: what the input Linear reads
+            self.cv_dy = torch.empty(max_T, batch_size, input_dim, device=self.device)
+            self.cv_len = torch.zeros(batch_size, device=self.device, dtype=torch.int32)  # model lengths of the last forward
+            self.cv_ws = ops.Conv2dWorkspace(self.T_in, batch_size, g, self.D_in // g, c, kt, kf, st, sf, device=self.device)
         self.ctc_ws = ops.CtcWorkspace(max_T, batch_size, num_labels, max_U, self.device)
         self.logits = torch.empty(max_T, batch_size, num_labels, device=self.device)
         self.dlogits = torch.empty_like(self.logits)
@@ -274,14 +303,24 @@ class Engine(ParamStore):
                 per_diagonal=False, dense_labels=None):
         """x [T,B,D] device float32, lengths int32 [B] device.  Returns logits [T,B,C]
         (a view of the engine's buffer).  Rows past `max_len` are the output bias (what the
-        reference produces there, since the LSTM output is zero past the length)."""
+        reference produces there, since the LSTM output is zero past the length).
+        With the front convolution x is [T_in,B,D_in], lengths and max_len count SOURCE frames, and the logits are the T model
+        frames; model_lengths() has the rows' lengths in model frames."""
         T, B, D = x.shape
-        assert (T, B, D) == (self.T, self.B, self.D), ((T, B, D), (self.T, self.B, self.D))
+        assert (T, B, D) == (self.T_in, self.B, self.D_in), ((T, B, D), (self.T_in, self.B, self.D_in))
+        T, D = self.T, self.D
         x = x.contiguous()
+        if self.conv and max_len is not None:
+            max_len = -(-max(int(max_len), 0) // self.conv[3])       # the run length is counted in model frames
         Tr = self._run_length(max_len)
         ws = self.lstm_ws.prefix(Tr)
         self._ws, self._Tr = ws, Tr
         ws.set_dropout(keep_in, keep_out, seed)
+        if self.conv:
+            c, kt, kf, st, sf, g = self.conv
+            ops.conv2d_fwd(x[:self._source_run(Tr)], self.p("conv_w"), self.p("conv_b"), lengths, g, (kt, kf), (st, sf),
+                           out=self.cv_y[:Tr], lengths_out=self.cv_len)
+            x, lengths = self.cv_y, self.cv_len          # from here on: model frames, model lengths
         ops.linear_fwd(x[:Tr].view(Tr * B, D), self.p("input_w"), self.p("input_b"), out=ws.z0.view(Tr * B, self.H))
         if self.normalization:
             grp = self._dp_group() if self.sync_batch_norm else None
@@ -347,6 +386,29 @@ class Engine(ParamStore):
             self.logits[Tr:] = self.p("output_b")          # broadcast fill of the never-visited tail
         return self.logits
 
+    def _source_run(self, Tr):
+        """Source frames behind a run of Tr model frames (ceil(that / st) == Tr)."""
+        return min(self.T_in, Tr * self.conv[3])
+
+    def model_lengths(self, lengths):
+        """The rows' lengths as everything behind the input Linear counts them: the device tensor the front convolution's launch of
+        the LAST forward wrote (ceil(min(length, run) / st)), or `lengths` itself without that layer."""
+        return self.cv_len if getattr(self, "conv", None) else lengths      # (getattr: engines that stand in for this one in tests)
+
+    def _input_linear_bwd(self, x, lengths, ws, Tr):
+        """The input Linear's weight gradients from dZ_0; with the front convolution also dZ_0 . W_i^T into its dy buffer and the
+        convolution's own gradients (x and lengths are the SOURCE ones), queued on the current stream."""
+        B = self.B
+        dz0 = ws.dz0.view(Tr * B, self.H)
+        if not self.conv:
+            ops.linear_bwd(x[:Tr].view(Tr * B, self.D), self.p("input_w"), dz0, self.g("input_w"), self.g("input_b"), need_dx=False)
+            return
+        c, kt, kf, st, sf, g = self.conv
+        ops.linear_bwd(self.cv_y[:Tr].view(Tr * B, self.D), self.p("input_w"), dz0, self.g("input_w"), self.g("input_b"),
+                       need_dx=True, dx=self.cv_dy[:Tr].view(Tr * B, self.D))
+        ops.conv2d_bwd(x[:self._source_run(Tr)], self.cv_y[:Tr], self.cv_dy[:Tr], lengths, g, (kt, kf), (st, sf),
+                       self.g("conv_w"), self.g("conv_b"), ws=self.cv_ws)
+
     def _cells(self, flat):
         """The 2L cell kernels and biases of the layer-wise mode (forward cells first) as views into `flat`."""
         L = self.L
@@ -374,10 +436,12 @@ class Engine(ParamStore):
         """Which shape-driven choices the LAST forward made -- what a parity test has to assert before it may claim to have checked
         them: `fused_ctc_head` (the CTC stage ran inside the two whole-sequence LSTM launches, ops.CtcHead), `paired` (a
         bidirectional model's two stacks side by side on one-XCD groups, ops.lstm_fwd_pair), `run_length` (frames visited), and
-        `lookahead` (the row convolution's context, 0 = none: with it the fused head is never taken), `lstm_fwd` / `lstm_bwd`: the
+        `lookahead` (the row convolution's context, 0 = none: with it the fused head is never taken), `conv` (the front
+        convolution's channels, 0 = none: with it `run_length` counts model frames of its output), `lstm_fwd` / `lstm_bwd`: the
         kernel path of that forward and of the backward that belongs to it ("flow", "big1", "big", "hoist", "diag", "diag_bf3":
         ops.lstm_plan at the run length, with the head and the per-diagonal request of the call)."""
-        path = {"fused_ctc_head": self._head is not None, "lookahead": self.lookahead, "paired": self._paired, "run_length": self._Tr}
+        path = {"fused_ctc_head": self._head is not None, "lookahead": self.lookahead, "paired": self._paired, "run_length": self._Tr,
+                "conv": self.conv[0] if self.conv else 0}
         if not self.layerwise:
             plan = ops.lstm_plan(self._ws, head=self._head, per_diagonal=self._per_diagonal)
             # (side by side: ops.lstm_fwd_pair runs the one-XCD forward kernel whatever one stack alone would take)
@@ -404,6 +468,7 @@ class Engine(ParamStore):
 
     def ctc(self, dense_labels, lengths, stage=0):
         Tr = self._Tr
+        lengths = self.model_lengths(lengths)
         if self._head is not None:       # (the loss is the forward launch's; dlogits will be the backward launch's)
             if Tr < self.T and stage != 1:
                 self.dlogits[Tr:].zero_()
@@ -423,7 +488,7 @@ class Engine(ParamStore):
         shape = (self.T, self.B, self.C, dense_labels.shape[1])
         if getattr(self, "_align_ws", None) is None or self._align_ws.shape != shape:
             self._align_ws = ops.CtcAlignWorkspace(*shape, device=self.device)
-        return ops.ctc_align(self.logits, dense_labels.contiguous(), lengths, ws=self._align_ws)
+        return ops.ctc_align(self.logits, dense_labels.contiguous(), self.model_lengths(lengths), ws=self._align_ws)
 
     @contextlib.contextmanager
     def on_stream(self):
@@ -449,8 +514,9 @@ class Engine(ParamStore):
         ws, Tr = self._ws, self._Tr
         H = self.H
         dl = self.dlogits[:Tr].view(Tr * B, self.C)
+        src_lengths, lengths = lengths, self.model_lengths(lengths)      # (the source lengths are the front convolution's alone)
         if self.layerwise:
-            self._backward_layerwise(x, lengths, wait_for, per_diagonal)
+            self._backward_layerwise(x, src_lengths, wait_for, per_diagonal)
             return
         head = self._head if not per_diagonal else None
         if self._head is not None and head is None:
@@ -496,9 +562,8 @@ class Engine(ParamStore):
                 with torch.cuda.stream(side):
                     if head is not None:
                         ops.linear_bwd(ws.ztop.view(Tr * B, H), self.p("output_w"), dl, self.g("output_w"), self.g("output_b"), need_dx=False)
-                    if flags & 2:
-                        ops.linear_bwd(x[:Tr].view(Tr * B, D), self.p("input_w"), ws.dz0.view(Tr * B, self.H), self.g("input_w"),
-                                       self.g("input_b"), need_dx=False)
+                    if flags & 2:        # (with the front convolution: its gradients too, queued before the join below)
+                        self._input_linear_bwd(x, src_lengths, ws, Tr)
                 torch.cuda.current_stream(self.device).wait_stream(side)
                 if flags & 2:
                     return
@@ -517,11 +582,11 @@ class Engine(ParamStore):
                 ops.batchnorm_bwd_dp(ws.dz0, self.bn_xhat, self.bn_inv_std, ws.dz0, grp, self.bn_scratch)
             else:
                 ops.batchnorm_bwd(ws.dz0, self.bn_xhat[:Tr], self.bn_inv_std[:Tr], ws.dz0)
-        ops.linear_bwd(x[:Tr].view(Tr * B, D), self.p("input_w"), ws.dz0.view(Tr * B, self.H), self.g("input_w"),
-                       self.g("input_b"), need_dx=False)
+        self._input_linear_bwd(x, src_lengths, ws, Tr)
 
-    def _backward_layerwise(self, x, lengths, wait_for, per_diagonal):
+    def _backward_layerwise(self, x, src_lengths, wait_for, per_diagonal):
         ws, Tr, B, H, D = self._ws, self._Tr, self.B, self.H, self.D
+        lengths = self.model_lengths(src_lengths)
         dl = self.dlogits[:Tr].view(Tr * B, self.C)
         wo, gwo = self.p("output_w"), self.g("output_w")
         ops.linear_bwd(ws.ytop_fw.view(Tr * B, H), wo[:H], dl, gwo[:H], self.g("output_b"), need_dx=True,
@@ -539,8 +604,7 @@ class Engine(ParamStore):
                 ops.batchnorm_bwd_dp(ws.dz0, self.bn_xhat, self.bn_inv_std, ws.dz0, grp, self.bn_scratch)
             else:
                 ops.batchnorm_bwd(ws.dz0, self.bn_xhat[:Tr], self.bn_inv_std[:Tr], ws.dz0)
-        ops.linear_bwd(x[:Tr].view(Tr * B, D), self.p("input_w"), ws.dz0.view(Tr * B, H), self.g("input_w"),
-                       self.g("input_b"), need_dx=False)
+        self._input_linear_bwd(x, src_lengths, ws, Tr)
 
     def check(self):
         """Synchronous health check of the dataflow LSTM kernels: their waits are bounded, and a time-out (the

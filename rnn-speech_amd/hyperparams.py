@@ -1,6 +1,6 @@
 """config.ini reader + checkpoint-side pickle logic (reference:
 /root/reference/util/hyperparams.py:17-141).  Same section/key names and defaults; a few
-optional keys are added for the MI355X build (n_mfcc, sample_rate, frame_stack / frame_skip, lookahead_context, feature_norm*, spec_augment_*,
+optional keys are added for the MI355X build (n_mfcc, sample_rate, frame_stack / frame_skip, lookahead_context, conv_*, feature_norm*, spec_augment_*,
 speed_perturb_*, noise_* / reverb_* / augment_*, long_audio / vad_* ...) and the reference's [lm_network_params] section with this build's lm_* keys."""
 import configparser
 import logging
@@ -13,12 +13,15 @@ _ACOUSTIC, _GENERAL, _TRAINING, _LOGGING = "acoustic_network_params", "general",
 # util/hyperparams.py:75-92; n_mfcc / sample_rate are this build's extra keys and change the input layer's
 # shape / the features' meaning; so do frame_stack / frame_skip, the low frame rate input, and feature_norm /
 # feature_norm_variance: a model trained on normalised features is useless on raw ones.  The statistics file's path is not.
-# lookahead_context adds a parameter tensor and a layer)
+# lookahead_context adds a parameter tensor and a layer; so do conv_channels / conv_kernel / conv_stride, which also set the input
+# layer's shape and the frame rate of everything above)
 _STRUCTURAL = ("num_layers", "hidden_size", "signal_processing", "language", "n_mfcc", "sample_rate", "bidirectional",
-               "bidirectional_mode", "frame_stack", "frame_skip", "feature_norm", "feature_norm_variance", "lookahead_context")
+               "bidirectional_mode", "frame_stack", "frame_skip", "feature_norm", "feature_norm_variance", "lookahead_context",
+               "conv_channels", "conv_kernel", "conv_stride")
 _STRUCTURAL_DEFAULTS = {"signal_processing": "mfcc", "language": "", "n_mfcc": 20, "sample_rate": 22050, "bidirectional": False,
                         "bidirectional_mode": "top", "frame_stack": 1, "frame_skip": 1, "feature_norm": "none", "feature_norm_variance": True,
-                        "lookahead_context": 0}
+                        "lookahead_context": 0, "conv_channels": 0, "conv_kernel": (11, 21), "conv_stride": (2, 2)}
+CONV_CHANNELS = (0, 16, 32, 48, 64)
 
 
 def read_config_file(config_file):
@@ -73,6 +76,11 @@ def read_config_file(config_file):
     if d["lookahead_context"] and d["bidirectional"]:
         raise ValueError("lookahead_context : %d with bidirectional : True -- the row convolution gives a unidirectional stack its "
                          "future context; a bidirectional one already reads the whole utterance" % d["lookahead_context"])
+    # strided time-frequency convolution between the features and the input Linear (ops.conv2d_fwd): conv_channels 0 (off, the
+    # reference's graph: the other two keys are then only checked) | 16 | 32 | 48 | 64; conv_kernel "kt, kf" taps in time and in
+    # frequency, both odd; conv_stride "st, sf".  The time stride is the learned form of frame_stack / frame_skip: refused with them
+    d.update(read_conv_keys(lambda key, dflt: cp.get(_ACOUSTIC, key, fallback=dflt), d["signal_processing"], d["n_mfcc"],
+                            d["frame_stack"], d["frame_skip"]))
     # feature normalisation between the front end and the frame stacking (ops.feature_norm): none (the reference's behaviour) |
     # utterance (mean / variance of the utterance itself) | global (of the training corpus, from the file feature_norm_stats names,
     # which `stt.py --feature_stats` writes).  feature_norm_variance False: means only
@@ -108,6 +116,43 @@ def read_config_file(config_file):
     d.update(read_augment_keys(lambda key, dflt: cp.get(_TRAINING, key, fallback=dflt)))
     d.update(read_lm_keys(lambda key, dflt: cp.get(_LM, key, fallback=dflt)))
     d.update(read_long_audio_keys(lambda key, dflt: cp.get(_GENERAL, key, fallback=dflt)))
+    return d
+
+
+def read_conv_keys(get, signal_processing="fbank", n_mfcc=20, frame_stack=1, frame_skip=1):
+    """conv_channels / conv_kernel / conv_stride from get(key, default) -> text, checked; a bad value raises ValueError that says
+    why.  The frequency axis is the 40 mel bins of fbank (static, delta, delta-delta are the layer's three input groups) or the
+    n_mfcc cepstra of mfcc."""
+    def ints(key, dflt, count):
+        text = get(key, dflt)
+        try:
+            vals = tuple(int(tok) for tok in str(text).split(","))
+        except (ValueError, OverflowError):
+            vals = ()
+        if len(vals) != count:
+            raise ValueError("%s must be %d integers separated by commas, not %r" % (key, count, text))
+        return vals
+
+    d = {"conv_channels": ints("conv_channels", "0", 1)[0], "conv_kernel": ints("conv_kernel", "11, 21", 2),
+         "conv_stride": ints("conv_stride", "2, 2", 2)}
+    if d["conv_channels"] not in CONV_CHANNELS:
+        raise ValueError("conv_channels must be one of %s (0: no convolution), not %r" % (", ".join(map(str, CONV_CHANNELS)), d["conv_channels"]))
+    (kt, kf), (st, sf) = d["conv_kernel"], d["conv_stride"]
+    if not (1 <= kt <= 11 and 1 <= kf <= 41):
+        raise ValueError("conv_kernel : %d, %d -- time taps 1 .. 11, frequency taps 1 .. 41" % (kt, kf))
+    if kt % 2 == 0 or kf % 2 == 0:
+        raise ValueError("conv_kernel : %d, %d -- both sizes must be odd (the padding is (k - 1) / 2 on each side)" % (kt, kf))
+    if not (1 <= st <= 4 and 1 <= sf <= 4):
+        raise ValueError("conv_stride : %d, %d -- each stride 1 .. 4" % (st, sf))
+    if d["conv_channels"]:
+        if frame_stack != 1 or frame_skip != 1:
+            raise ValueError("conv_channels : %d with frame_stack : %d / frame_skip : %d -- the convolution's time stride is the "
+                             "learned form of those two; use one or the other" % (d["conv_channels"], frame_stack, frame_skip))
+        bins = 40 if signal_processing == "fbank" else int(n_mfcc)
+        width = -(-bins // sf) * d["conv_channels"]
+        if width > 4096:
+            raise ValueError("conv_channels : %d at conv_stride : %d, %d -- %d output bins x %d channels = %d inputs of the input "
+                             "layer, more than 4096" % (d["conv_channels"], st, sf, -(-bins // sf), d["conv_channels"], width))
     return d
 
 

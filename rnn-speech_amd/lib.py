@@ -84,6 +84,12 @@ class LookaheadPlanInfo(C.Structure):     # amdspeech_lookahead_plan_info (inclu
                                        "reduce_slices", "reduce_terms", "reduce_workgroups")]
 
 
+class Conv2dPlanInfo(C.Structure):     # amdspeech_conv2d_plan_info (include/amdspeech.h): the launch geometry of the front convolution's calls, read-only
+    _fields_ = [(n, C.c_int) for n in ("t_out", "f_out", "k", "k_pad", "tile_t", "tile_f", "vec", "fwd_workgroups", "fwd_lds_bytes",
+                                       "weights_resident", "k_chunk", "k_rows", "k_groups", "dw_partials", "bwd_workgroups", "bwd_lds_bytes",
+                                       "dw_terms", "reduce_slices", "reduce_terms", "reduce_workgroups")]
+
+
 class VadPlanInfo(C.Structure):     # amdspeech_vad_plan_info (include/amdspeech.h): the launch geometry of the voice-activity calls, read-only
     _fields_ = [(n, C.c_int) for n in ("load_vec", "frames_per_tile", "tiles_per_row", "workgroups", "threads", "f_max", "select_passes",
                                        "row_workgroups", "row_threads", "meta_by_copy")]
@@ -245,6 +251,10 @@ PROTOTYPES = {
     "amdspeech_lookahead_bwd_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "amdspeech_lookahead_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "amdspeech_lookahead_plan": (_I, [_I, _I, _I, _I, C.POINTER(LookaheadPlanInfo)]),
+    "amdspeech_conv2d_fwd": (_I, [_P, _P, _P, _P, _P] + [_I] * 9 + [_P, _P]),
+    "amdspeech_conv2d_bwd_workspace_bytes": (_SZ, [_I] * 9),
+    "amdspeech_conv2d_bwd": (_I, [_P, _P, _P, _P, _P] + [_I] * 9 + [_P, _P, _P]),
+    "amdspeech_conv2d_plan": (_I, [_I] * 9 + [C.POINTER(Conv2dPlanInfo)]),
     "amdspeech_vad_num_frames": (_I, [_I, _I]),
     "amdspeech_vad_workspace_bytes": (_SZ, [_I, _I, _I]),
     "amdspeech_vad_plan": (_I, [_I, _I, _I, C.POINTER(VadPlanInfo)]),

@@ -1343,6 +1343,103 @@ def lookahead_bwd(x, w, dy, lengths, dx=None, dw=None, ws=None):
     return dx, dw
 
 
+# ------------------------------------------------------------ time-frequency convolution (front)
+CONV2D_CHANNELS = (16, 32, 48, 64)
+CONV2D_MAX_KT, CONV2D_MAX_KF, CONV2D_MAX_STRIDE, CONV2D_MAX_WIDTH = 11, 41, 4, 4096
+
+
+def conv2d_out_shape(T, F, C, st, sf):
+    """(T', F' * C): model frames and input-Linear width behind the convolution."""
+    return -(-int(T) // int(st)), -(-int(F) // int(sf)) * int(C)
+
+
+def conv2d_check(C, kt, kf, st, sf, F=None):
+    """The ranges of the layer's sizes (amdspeech.h), as a ValueError that says which one is wrong; with F also the output width."""
+    if C not in CONV2D_CHANNELS:
+        raise ValueError("conv_channels must be 0 (off) or one of %s, not %r" % (", ".join(map(str, CONV2D_CHANNELS)), C))
+    if not (1 <= kt <= CONV2D_MAX_KT and 1 <= kf <= CONV2D_MAX_KF):
+        raise ValueError("conv_kernel %d, %d: time taps 1 .. %d, frequency taps 1 .. %d" % (kt, kf, CONV2D_MAX_KT, CONV2D_MAX_KF))
+    if kt % 2 == 0 or kf % 2 == 0:
+        raise ValueError("conv_kernel %d, %d: both sizes must be odd (the padding is (k - 1) / 2 on each side)" % (kt, kf))
+    if not (1 <= st <= CONV2D_MAX_STRIDE and 1 <= sf <= CONV2D_MAX_STRIDE):
+        raise ValueError("conv_stride %d, %d: each 1 .. %d" % (st, sf, CONV2D_MAX_STRIDE))
+    if F is not None and conv2d_out_shape(1, F, C, st, sf)[1] > CONV2D_MAX_WIDTH:
+        raise ValueError("conv: %d output bins x %d channels = %d inputs of the input layer, more than %d"
+                         % (-(-F // sf), C, conv2d_out_shape(1, F, C, st, sf)[1], CONV2D_MAX_WIDTH))
+
+
+def conv2d_plan(T, B, G, F, C, kt, kf, st, sf):
+    """The launch geometry of `conv2d_fwd` / `conv2d_bwd` for a shape (amdspeech.h: amdspeech_conv2d_plan), as a dict of ints with
+    "workspace_bytes" (amdspeech_conv2d_bwd_workspace_bytes) beside the struct's fields.  Read-only: nothing is launched, no device
+    is needed.  A shape the calls refuse raises here too."""
+    info = _l.Conv2dPlanInfo()
+    lib = _l.load()
+    dims = [int(v) for v in (T, B, G, F, C, kt, kf, st, sf)]
+    _l.check(lib.amdspeech_conv2d_plan(*dims, _l.C.byref(info)), "conv2d_plan")      # (the parameter C hides this module's ctypes)
+    out = _plan_dict(info)
+    out["workspace_bytes"] = int(lib.amdspeech_conv2d_bwd_workspace_bytes(*dims))
+    return out
+
+
+class Conv2dWorkspace(object):
+    """The partial weight-gradient tiles of conv2d_bwd for calls of up to T source frames (a shorter run needs no more).  The call
+    writes every word it reads: no fill."""
+
+    def __init__(self, T, B, G, F, C, kt, kf, st, sf, device="cuda"):
+        self.shape = (T, B, G, F, C, kt, kf, st, sf)
+        n = conv2d_plan(*self.shape)["workspace_bytes"]
+        self.buf = torch.empty(max(n, 16), device=device, dtype=torch.uint8)
+
+    def fits(self, T, *rest):
+        return self.shape[1:] == tuple(rest) and T <= self.shape[0]
+
+
+def _conv2d_args(what, x, w, G, kernel, stride):
+    T, B, D = _chk_f32_3d(what, x, "[T, B, G * F]")
+    _chk_f32(w)
+    (kt, kf), (st, sf) = kernel, stride
+    if w.dim() != 2 or D % G != 0 or w.shape[0] != G * kt * kf:
+        raise ValueError("%s: w %s is not [%d * %d * %d, C] for x %s" % (what, tuple(w.shape), G, kt, kf, tuple(x.shape)))
+    return T, B, D // G, w.shape[1], kt, kf, st, sf
+
+
+def conv2d_fwd(x, w, bias, lengths, G, kernel, stride, out=None, lengths_out=None):
+    """(y [T', B, F' * C], lengths_out int32 [B]) = the strided "same" convolution of x [T, B, G * F] with w [G * kt * kf, C], + bias,
+    clipped to 0 .. 20, zeros past each row's ceil(length / st) (amdspeech.h: amdspeech_conv2d_fwd).  lengths: int32 [B] on the device."""
+    T, B, F, C, kt, kf, st, sf = _conv2d_args("conv2d_fwd", x, w, G, kernel, stride)
+    _chk_f32(bias, out)
+    _chk_i32(lengths)
+    To, W = conv2d_out_shape(T, F, C, st, sf)
+    if out is None:
+        out = torch.empty(To, B, W, device=x.device, dtype=torch.float32)
+    if lengths_out is None:
+        lengths_out = torch.empty(B, device=x.device, dtype=torch.int32)
+    _chk_i32(lengths_out)
+    if tuple(out.shape) != (To, B, W) or lengths.numel() != B or lengths_out.numel() != B or tuple(bias.shape) != (C,):
+        raise ValueError("conv2d_fwd: out %s / lengths %d / bias %s beside x %s, w %s" % (tuple(out.shape), lengths.numel(), tuple(bias.shape),
+                                                                                      tuple(x.shape), tuple(w.shape)))
+    _l.check(_l.load().amdspeech_conv2d_fwd(_stream(), _p(x), _p(w), _p(bias), _p(lengths), T, B, G, F, C, kt, kf, st, sf, _p(out),
+                                            _p(lengths_out)), "conv2d_fwd")
+    return out, lengths_out
+
+
+def conv2d_bwd(x, y, dy, lengths, G, kernel, stride, dw, db, ws=None):
+    """dw [G * kt * kf, C] += and db [C] += the layer's gradients from its input x, its output y (the activation's mask is read from
+    it) and dy (amdspeech.h: amdspeech_conv2d_bwd).  lengths are the SOURCE lengths.  Returns (dw, db)."""
+    T, B, F, C, kt, kf, st, sf = _conv2d_args("conv2d_bwd", x, dw, G, kernel, stride)
+    _chk_f32(y, dy, db)
+    _chk_i32(lengths)
+    To, W = conv2d_out_shape(T, F, C, st, sf)
+    if tuple(y.shape) != (To, B, W) or tuple(dy.shape) != (To, B, W) or lengths.numel() != B or tuple(db.shape) != (C,):
+        raise ValueError("conv2d_bwd: y %s / dy %s / db %s beside x %s, dw %s" % (tuple(y.shape), tuple(dy.shape), tuple(db.shape),
+                                                                                 tuple(x.shape), tuple(dw.shape)))
+    if ws is None or not ws.fits(T, B, G, F, C, kt, kf, st, sf):
+        ws = Conv2dWorkspace(T, B, G, F, C, kt, kf, st, sf, x.device)
+    _l.check(_l.load().amdspeech_conv2d_bwd(_stream(), _p(x), _p(y), _p(dy), _p(lengths), T, B, G, F, C, kt, kf, st, sf, _p(dw), _p(db),
+                                            _p(ws.buf)), "conv2d_bwd")
+    return dw, db
+
+
 # ------------------------------------------------------------ voice activity / long recordings
 _vad_ws = {}
 

@@ -114,12 +114,25 @@ def build_audio_processor(hyper_params):
     hyper_params["input_dim"] = audio_processor.feature_size
     hyper_params["out_seq_length"] = audio_processor.out_seq_length
     hyper_params["spec_augment"] = spec_augment_policy(hyper_params, audio_processor)
-    if hyper_params["out_seq_length"] < hyper_params["max_target_seq_length"]:
-        logging.warning("out_seq_length %d (max_input_seq_length %d at frame_skip %d) is below max_target_seq_length %d: "
+    conv = conv_option(hyper_params)
+    step = conv[3] if conv else audio_processor.frame_skip      # (the two are refused together: one of them is 1)
+    model_frames_max = -(-hyper_params["out_seq_length"] // (conv[3] if conv else 1))
+    if model_frames_max < hyper_params["max_target_seq_length"]:
+        logging.warning("%d model frames (max_input_seq_length %d at %s %d) is below max_target_seq_length %d: "
                         "a transcript with more tokens than its utterance has frames is ignored by the loss",
-                        hyper_params["out_seq_length"], hyper_params["max_input_seq_length"],
-                        audio_processor.frame_skip, hyper_params["max_target_seq_length"])
+                        model_frames_max, hyper_params["max_input_seq_length"], "conv_stride" if conv else "frame_skip", step,
+                        hyper_params["max_target_seq_length"])
     return audio_processor
+
+
+def conv_option(hyper_params):
+    """AcousticModel.conv from the conv_* keys: None at conv_channels 0 (the default: no such layer), else (C, kt, kf, st, sf, G)
+    with G the groups of a source frame -- static, delta and delta-delta of 40 mel bins for fbank, one group of n_mfcc for mfcc."""
+    channels = int(hyper_params.get("conv_channels", 0) or 0)
+    if channels == 0:
+        return None
+    (kt, kf), (st, sf) = hyper_params.get("conv_kernel", (11, 21)), hyper_params.get("conv_stride", (2, 2))
+    return channels, int(kt), int(kf), int(st), int(sf), 3 if hyper_params["signal_processing"] == "fbank" else 1
 
 
 def pipeline_options(hyper_params, dataset=False):
@@ -189,6 +202,7 @@ def _set_model_options(model, hyper_params):
     model.bidirectional = hyper_params.get("bidirectional", False)
     model.bidirectional_mode = hyper_params.get("bidirectional_mode", "top")
     model.lookahead_context = hyper_params.get("lookahead_context", 0)
+    model.conv = conv_option(hyper_params)
     model.sync_batch_norm = hyper_params.get("sync_batch_norm", False)
     model.spec_augment = hyper_params.get("spec_augment")       # (build_audio_processor; only run_step with gradients masks)
     opts = pipeline_options(hyper_params)                       # (evaluate_full builds its AudioProcessor from these five)
@@ -469,7 +483,8 @@ def align_file(audio_processor, hyper_params, file, transcript):
     """--align: when was each word of a known transcript spoken?  The restored model at batch 1, the best CTC alignment of the
     transcript's tokens to the frames (AcousticModel.align), tokens grouped into words.  Prints one line per word:
     start_s end_s confidence word -- the times of the word's first and last frame, frame t being t * frame_hop_samples / sample_rate
-    into the file (the front end's 10 ms hop times frame_skip: the start of the model frame's first source frame)."""
+    into the file (the front end's 10 ms hop times frame_skip, or times the front convolution's time stride: the start of the
+    model frame's first source frame)."""
     feat_vec, original_length = audio_processor.process_audio_file(file)
     T = audio_processor.out_seq_length
     if original_length > T:
@@ -484,16 +499,17 @@ def align_file(audio_processor, hyper_params, file, transcript):
     tokens = model.align(None, padded, [min(original_length, T)], [ids])[0]
     if not tokens:
         sys.exit("the transcript cannot be aligned to this recording (more tokens than frames?)")
-    frame_s = frame_seconds(audio_processor)
+    frame_s = frame_seconds(audio_processor, conv_option(hyper_params))
     words = dataprocessor.DataProcessor.group_words(char_map, tokens)
     for word, first, last, conf in words:
         print("%.3f %.3f %.3f %s" % (first * frame_s, last * frame_s, conf, word))
     return words
 
 
-def frame_seconds(audio_processor):
-    """Seconds between the starts of two model frames: what --align multiplies a frame index by."""
-    return audio_processor.frame_hop_samples / float(audio_processor.load_sr)
+def frame_seconds(audio_processor, conv=None):
+    """Seconds between the starts of two model frames: what --align multiplies a frame index by.  Behind the front convolution
+    (conv_option) a model frame is centred on every st-th source frame: the hop times its time stride."""
+    return audio_processor.frame_hop_samples * (conv[3] if conv else 1) / float(audio_processor.load_sr)
 
 
 def evaluate(hyper_params):
