@@ -17,6 +17,7 @@ import torch
 
 from . import lib as _lib
 from . import ops
+from . import stacks
 
 
 def _pad64(n):
@@ -111,7 +112,8 @@ PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16": 2}
 class ParamStore(object):
     """Everything that hangs off a ParamLayout and a device, for every model: the flat fp32 parameter / gradient / Adam buffers,
     views and host copies by tensor name, Glorot initialisation, the optimiser step, and the health predicate and run-length clamp
-    of the engines built on it.  A subclass sets T (its padded length), says what it is in _describe() and implements check()."""
+    of the engines built on it.  A subclass sets T (its padded length) and B, H, its logits / dlogits buffers and its recurrence
+    driver `stack` (stacks.py), and says what it is in _describe()."""
 
     def __init__(self, layout, device):
         self.layout, self.device = layout, torch.device(device)
@@ -182,6 +184,39 @@ class ParamStore(object):
         except _lib.DataflowTimeout:
             return False
 
+    # ---- what the engines built on the store share: the recurrence driver `stack` (stacks.py), logits / dlogits [T,B,C] --------
+    _ws = property(lambda self: self.stack.ws)                # the stack's (forward-direction) workspace at the last run length
+    lstm_ws = property(lambda self: self.stack.lstm_ws)       # ... and its allocation
+
+    def check(self):
+        """Synchronous health check of the dataflow LSTM kernels: their waits are bounded, and a time-out (the
+        workgroups of one launch were not all resident -- another kernel held CUs) leaves an error flag behind
+        instead of hanging.  Raises AmdSpeechError; results of that step are invalid."""
+        self.stack.check()
+
+    def _output_fwd(self, tops, Tr):
+        """The output layer over the one or two top outputs [(y, dy), ..]: logits[:Tr] = [y_0 ; y_1] . W_o + b_o."""
+        n, H, wo = Tr * self.B, self.H, self.p("output_w")
+        out = self.logits[:Tr].view(n, -1)
+        ops.linear_fwd(tops[0][0].view(n, H), wo[:H], self.p("output_b"), out=out)
+        for y, _ in tops[1:]:
+            ops.gemm(y.view(n, H), wo[H:], out=out, accumulate=True)
+
+    def _fill_tail(self, Tr):
+        """Rows past the run length are the output bias (what the reference produces there: the LSTM output is zero past the length)."""
+        if Tr < self.T:
+            self.logits[Tr:] = self.p("output_b")          # broadcast fill of the never-visited tail
+
+    def _output_bwd(self, tops, Tr, need_dx=True):
+        """dW_o += [y_0 ; y_1]^T . dlogits, db_o += column sums of dlogits and (need_dx) dy_i = dlogits . W_o[half i]^T."""
+        n, H = Tr * self.B, self.H
+        wo, gwo, dl = self.p("output_w"), self.g("output_w"), self.dlogits[:Tr].view(n, -1)
+        y, dy = tops[0]
+        ops.linear_bwd(y.view(n, H), wo[:H], dl, gwo[:H], self.g("output_b"), need_dx=need_dx, dx=dy.view(n, H) if need_dx else None)
+        for y, dy in tops[1:]:
+            ops.gemm(y.view(n, H), dl, trans_a=True, out=gwo[H:], accumulate=True)
+            ops.gemm(dl, wo[H:], trans_b=True, out=dy.view(n, H))
+
     def _run_length(self, max_len):
         """Steps the recurrence has to visit: the longest row of this batch when the host knows it (`max_len`, from the dataset
         pipeline -- no device sync), else the padded length.  Mirrors tf.nn.dynamic_rnn, whose while-loop runs to
@@ -236,15 +271,9 @@ class Engine(ParamStore):
             raise ValueError("precision must be 'f32' (exact, default), 'bf16x3' (split-precision MFMA) or 'bf16' (plain bf16 "
                              "operands, f32 accumulation and master weights)")
         self.precision = precision
-        if self.layerwise:
-            self.lstm_ws = ops.BidirWorkspace(max_T, batch_size, hidden, num_layers, device=self.device, precision=PRECISIONS[precision])
-        else:
-            self.lstm_ws = ops.LstmWorkspace(max_T, batch_size, hidden, num_layers, device=self.device, precision=PRECISIONS[precision])
-        if self.bidirectional and not self.layerwise:
-            self.lstm_ws_b = ops.LstmWorkspace(max_T, batch_size, hidden, num_layers, device=self.device,
-                                               precision=PRECISIONS[precision])
-            self.ytop_b = torch.empty(max_T, batch_size, hidden, device=self.device)      # backward stack's output, in forward time
-            self.dytop_b = torch.empty(max_T, batch_size, hidden, device=self.device)
+        # the recurrence driver: the one place that knows which arrangement of stacks this engine runs
+        driver = stacks.LayerStack if self.layerwise else stacks.JoinedStack if self.bidirectional else stacks.UniStack
+        self.stack = driver(self, max_T, batch_size, hidden, num_layers, PRECISIONS[precision])
         if self.lookahead:               # f32 in every precision mode
             self.la_y = torch.empty(max_T, batch_size, hidden, device=self.device)        # the convolution's output: what the output layer reads
             self.la_dy = torch.empty(max_T, batch_size, hidden, device=self.device)
@@ -273,16 +302,17 @@ class Engine(ParamStore):
             self.bn_xhat = torch.empty(max_T, batch_size, hidden, device=self.device)
             self.bn_inv_std = torch.empty(max_T, hidden, device=self.device)
             self.bn_scratch = torch.empty(2, max_T, hidden, device=self.device)       # cross-rank sums under data parallelism
-        self._ws, self._Tr = self.lstm_ws, max_T
+        self._Tr = max_T                 # frames the last forward visited
         self._head = None                # ops.CtcHead of the mini-batch in flight, when its CTC stage runs inside the LSTM launches
-        self._per_diagonal = False       # the last forward ran on the launch-per-diagonal kernels by request
-        self._paired = False             # the last forward ran a bidirectional model's two stacks side by side (ops.lstm_fwd_pair)
-        self._ws_b = self.lstm_ws_b if self.bidirectional and not self.layerwise else None
+        self._tops = self._la_x = None   # (y, dy) pairs of the last forward: what the output layer read, what the lookahead read
         # a real (non-NULL) stream for callers that want the overlapped backward pass: see on_stream()
         self.stream = torch.cuda.Stream(device=self.device, priority=-1)      # (ahead of the side stream that prefetches the next batch)
         self._aux_stream = None          # (mini_batch: carries the "beside the forward kernel" ordering point to the caller's hook)
-        self._tail_stream = None         # (backward: the dense layers' weight gradients beside the LSTM's)
         self.init_parameters(seed)
+
+    # (names that tests of the two bidirectional arrangements read: the backward-direction stack's workspace, the 2L cell tensors)
+    _ws_b = property(lambda self: self.stack.bw.ws)
+    _cells = property(lambda self: self.stack.cells)
 
     def _describe(self):
         return "the model (L=%d, H=%d, D=%d, C=%d)" % (self.L, self.H, self.D, self.C)
@@ -308,83 +338,63 @@ class Engine(ParamStore):
         frames; model_lengths() has the rows' lengths in model frames."""
         T, B, D = x.shape
         assert (T, B, D) == (self.T_in, self.B, self.D_in), ((T, B, D), (self.T_in, self.B, self.D_in))
-        T, D = self.T, self.D
+        D, H = self.D, self.H
         x = x.contiguous()
         if self.conv and max_len is not None:
             max_len = -(-max(int(max_len), 0) // self.conv[3])       # the run length is counted in model frames
-        Tr = self._run_length(max_len)
-        ws = self.lstm_ws.prefix(Tr)
-        self._ws, self._Tr = ws, Tr
-        ws.set_dropout(keep_in, keep_out, seed)
+        Tr = self._Tr = self._run_length(max_len)
+        stack = self.stack
+        stack.lay_out(Tr, keep_in, keep_out, seed)
+        z0 = stack.z0
+        # 1. front convolution
         if self.conv:
             c, kt, kf, st, sf, g = self.conv
             ops.conv2d_fwd(x[:self._source_run(Tr)], self.p("conv_w"), self.p("conv_b"), lengths, g, (kt, kf), (st, sf),
                            out=self.cv_y[:Tr], lengths_out=self.cv_len)
             x, lengths = self.cv_y, self.cv_len          # from here on: model frames, model lengths
-        ops.linear_fwd(x[:Tr].view(Tr * B, D), self.p("input_w"), self.p("input_b"), out=ws.z0.view(Tr * B, self.H))
+        # 2. input Linear
+        ops.linear_fwd(x[:Tr].view(Tr * B, D), self.p("input_w"), self.p("input_b"), out=z0.view(Tr * B, H))
+        # 3. batch norm
         if self.normalization:
-            grp = self._dp_group() if self.sync_batch_norm else None
-            if grp is not None and grp.world > 1:      # moments over the GLOBAL batch: local sums -> all-reduce -> finish (Tr == T on every rank)
-                ops.batchnorm_fwd_dp(ws.z0, ws.z0, self.bn_xhat, self.bn_inv_std, grp, self.bn_scratch, 1e-3)
-            else:
-                ops.batchnorm_fwd(ws.z0, ws.z0, self.bn_xhat[:Tr], self.bn_inv_std[:Tr], 1e-3)
-        if self.layerwise:
-            return self._forward_layerwise(ws, lengths, keep_in, keep_out, seed, use_state, after_lstm, per_diagonal, Tr)
-        if self.bidirectional:
-            # the backward-direction stack reads the time-reversed input-layer output.  Taken BEFORE the forward stack runs:
-            # lstm_fwd applies its layer-0 input-dropout mask to Z_0 in place, and the two stacks' DropoutWrappers are
-            # independent (each masks its own copy of the same Z_0)
-            wb = self.lstm_ws_b.prefix(Tr)
-            self._ws_b = wb
-            ops.reverse_sequences(ws.z0, lengths, out=wb.z0)
-        # the CTC head inside the LSTM launches (ops.CtcHead; dense_labels given = a training mini-batch): the output layer, the
-        # log-softmax and alpha follow the forward recurrence, beta and the gradient lead the backward one
-        self._per_diagonal = bool(per_diagonal)
+            self._batchnorm_fwd(z0, Tr)
+        # 4. recurrence.  With the CTC head inside the LSTM launches (ops.CtcHead; dense_labels given = a training mini-batch) the
+        # output layer, the log-softmax and alpha follow the forward recurrence, beta and the gradient lead the backward one
         self._head = None
-        if (dense_labels is not None and _FUSED_CTC and not self.bidirectional and not self.lookahead
-                and ops.lstm_ctc_fusable(ws, self.C, dense_labels.shape[1], per_diagonal=per_diagonal)):
+        if (dense_labels is not None and _FUSED_CTC and not self.lookahead
+                and stack.ctc_fusable(self.C, dense_labels.shape[1], per_diagonal)):
             self._head = ops.CtcHead(self.p("output_w"), self.p("output_b"), self.logits[:Tr], dense_labels, self.loss,
                                      self.dlogits[:Tr], self.ctc_ws)
-        paired = self.bidirectional and _BIDIR_PAIR and not per_diagonal and ops.lstm_pair_fusable(ws)
-        self._paired = bool(paired)
-        if paired:
-            # the two stacks in ONE call: where the forward kernel places a batch tile's group on one XCD (1024 wide in plain bf16)
-            # their layers run side by side, one launch per layer for both (ops.lstm_fwd_pair)
-            wb.set_dropout(keep_in, keep_out, seed ^ 0x5bd1e995)
-            ops.lstm_fwd_pair(ws, self.p("kernel_0"), self.p("bias_0"), wb, self.p("bw_kernel_0"), self.p("bw_bias_0"),
-                              self.layout.kernel_stride, self.layout.bias_stride, lengths,
-                              self.state_h if use_state else None, self.state_c if use_state else None)
-        else:
-            ops.lstm_fwd(ws, self.p("kernel_0"), self.layout.kernel_stride, self.p("bias_0"),
-                         self.layout.bias_stride, lengths,
-                         self.state_h if use_state else None, self.state_c if use_state else None, training=training,
-                         per_diagonal=per_diagonal, head=self._head)
-        H = self.H
-        if not self.bidirectional:
-            if after_lstm is not None:
-                after_lstm()           # (mini_batch: from here on other streams may use the chip -- see beside_ctc)
-            top = ws.ztop
-            if self.lookahead:           # (the fused head is never taken with it: the output layer reads the convolution's output)
-                top = ops.lookahead_fwd(ws.ztop, self.p("lookahead_w"), lengths, out=self.la_y[:Tr])
-            if self._head is None:
-                ops.linear_fwd(top.view(Tr * B, H), self.p("output_w"), self.p("output_b"),
-                               out=self.logits[:Tr].view(Tr * B, self.C))
-        else:
-            # backward-direction stack on the time-reversed input-layer output (its own dropout stream; it always starts
-            # from a zero state: a state carried from the END of the previous batch's utterances means nothing here)
-            if not paired:
-                wb.set_dropout(keep_in, keep_out, seed ^ 0x5bd1e995)
-                ops.lstm_fwd(wb, self.p("bw_kernel_0"), self.layout.kernel_stride, self.p("bw_bias_0"),
-                             self.layout.bias_stride, lengths, None, None, training=training, per_diagonal=per_diagonal)
-            if after_lstm is not None:
-                after_lstm()
-            ops.reverse_sequences(wb.ztop, lengths, out=self.ytop_b[:Tr])
-            wo = self.p("output_w")
-            ops.linear_fwd(ws.ztop.view(Tr * B, H), wo[:H], self.p("output_b"), out=self.logits[:Tr].view(Tr * B, self.C))
-            ops.gemm(self.ytop_b[:Tr].view(Tr * B, H), wo[H:], out=self.logits[:Tr].view(Tr * B, self.C), accumulate=True)
-        if Tr < T:
-            self.logits[Tr:] = self.p("output_b")          # broadcast fill of the never-visited tail
+        stack.forward(lengths, self.state_h if use_state else None, self.state_c if use_state else None, training, per_diagonal,
+                      self._head, pair=_BIDIR_PAIR)
+        # 5. the caller's hook
+        if after_lstm is not None:
+            after_lstm()           # (mini_batch: from here on other streams may use the chip -- see beside_ctc)
+        # 6. lookahead (the fused head is never taken with it: the output layer reads the convolution's output)
+        self._tops = stack.tops(lengths)
+        if self.lookahead:
+            self._la_x = self._tops[0]
+            ops.lookahead_fwd(self._la_x[0], self.p("lookahead_w"), lengths, out=self.la_y[:Tr])
+            self._tops = [(self.la_y[:Tr], self.la_dy[:Tr])]
+        # 7. output layer
+        if self._head is None:
+            self._output_fwd(self._tops, Tr)
+        # 8. tail fill
+        self._fill_tail(Tr)
         return self.logits
+
+    def _batchnorm_fwd(self, z0, Tr):
+        grp = self._dp_group() if self.sync_batch_norm else None
+        if grp is not None and grp.world > 1:      # moments over the GLOBAL batch: local sums -> all-reduce -> finish (Tr == T on every rank)
+            ops.batchnorm_fwd_dp(z0, z0, self.bn_xhat, self.bn_inv_std, grp, self.bn_scratch, 1e-3)
+        else:
+            ops.batchnorm_fwd(z0, z0, self.bn_xhat[:Tr], self.bn_inv_std[:Tr], 1e-3)
+
+    def _batchnorm_bwd(self, dz0, Tr):
+        grp = self._dp_group() if self.sync_batch_norm else None
+        if grp is not None and grp.world > 1:
+            ops.batchnorm_bwd_dp(dz0, self.bn_xhat, self.bn_inv_std, dz0, grp, self.bn_scratch)
+        else:
+            ops.batchnorm_bwd(dz0, self.bn_xhat[:Tr], self.bn_inv_std[:Tr], dz0)
 
     def _source_run(self, Tr):
         """Source frames behind a run of Tr model frames (ceil(that / st) == Tr)."""
@@ -395,42 +405,17 @@ class Engine(ParamStore):
         the LAST forward wrote (ceil(min(length, run) / st)), or `lengths` itself without that layer."""
         return self.cv_len if getattr(self, "conv", None) else lengths      # (getattr: engines that stand in for this one in tests)
 
-    def _input_linear_bwd(self, x, lengths, ws, Tr):
+    def _input_linear_bwd(self, x, lengths, Tr):
         """The input Linear's weight gradients from dZ_0; with the front convolution also dZ_0 . W_i^T into its dy buffer and the
         convolution's own gradients (x and lengths are the SOURCE ones), queued on the current stream."""
-        B = self.B
-        dz0 = ws.dz0.view(Tr * B, self.H)
-        if not self.conv:
-            ops.linear_bwd(x[:Tr].view(Tr * B, self.D), self.p("input_w"), dz0, self.g("input_w"), self.g("input_b"), need_dx=False)
-            return
-        c, kt, kf, st, sf, g = self.conv
-        ops.linear_bwd(self.cv_y[:Tr].view(Tr * B, self.D), self.p("input_w"), dz0, self.g("input_w"), self.g("input_b"),
-                       need_dx=True, dx=self.cv_dy[:Tr].view(Tr * B, self.D))
-        ops.conv2d_bwd(x[:self._source_run(Tr)], self.cv_y[:Tr], self.cv_dy[:Tr], lengths, g, (kt, kf), (st, sf),
-                       self.g("conv_w"), self.g("conv_b"), ws=self.cv_ws)
-
-    def _cells(self, flat):
-        """The 2L cell kernels and biases of the layer-wise mode (forward cells first) as views into `flat`."""
-        L = self.L
-        ks = [self.layout.view(flat, "kernel_%d" % l) for l in range(L)] + [self.layout.view(flat, "bw_kernel_%d" % l) for l in range(L)]
-        bs = [self.layout.view(flat, "bias_%d" % l) for l in range(L)] + [self.layout.view(flat, "bw_bias_%d" % l) for l in range(L)]
-        return ks, bs
-
-    def _forward_layerwise(self, ws, lengths, keep_in, keep_out, seed, use_state, after_lstm, per_diagonal, Tr):
-        B, H = self.B, self.H
-        ws.set_dropout(keep_in, keep_out, seed)
-        ks, bs = self._cells(self.params)
-        self._per_diagonal = bool(per_diagonal)
-        ops.lstm_bidir_fwd(ws, ks, bs, lengths, self.state_h if use_state else None, self.state_c if use_state else None,
-                           per_frame=per_diagonal)
-        if after_lstm is not None:
-            after_lstm()
-        wo = self.p("output_w")
-        ops.linear_fwd(ws.ytop_fw.view(Tr * B, H), wo[:H], self.p("output_b"), out=self.logits[:Tr].view(Tr * B, self.C))
-        ops.gemm(ws.ytop_bw.view(Tr * B, H), wo[H:], out=self.logits[:Tr].view(Tr * B, self.C), accumulate=True)
-        if Tr < self.T:
-            self.logits[Tr:] = self.p("output_b")
-        return self.logits
+        n = Tr * self.B
+        x_in, dx = (self.cv_y, self.cv_dy[:Tr].view(n, self.D)) if self.conv else (x, None)
+        ops.linear_bwd(x_in[:Tr].view(n, self.D), self.p("input_w"), self.stack.dz0.view(n, self.H), self.g("input_w"), self.g("input_b"),
+                       need_dx=dx is not None, dx=dx)
+        if self.conv:
+            c, kt, kf, st, sf, g = self.conv
+            ops.conv2d_bwd(x[:self._source_run(Tr)], self.cv_y[:Tr], self.cv_dy[:Tr], lengths, g, (kt, kf), (st, sf),
+                           self.g("conv_w"), self.g("conv_b"), ws=self.cv_ws)
 
     def kernel_path(self):
         """Which shape-driven choices the LAST forward made -- what a parity test has to assert before it may claim to have checked
@@ -439,17 +424,11 @@ class Engine(ParamStore):
         `lookahead` (the row convolution's context, 0 = none: with it the fused head is never taken), `conv` (the front
         convolution's channels, 0 = none: with it `run_length` counts model frames of its output), `lstm_fwd` / `lstm_bwd`: the
         kernel path of that forward and of the backward that belongs to it ("flow", "big1", "big", "hoist", "diag", "diag_bf3":
-        ops.lstm_plan at the run length, with the head and the per-diagonal request of the call)."""
-        path = {"fused_ctc_head": self._head is not None, "lookahead": self.lookahead, "paired": self._paired, "run_length": self._Tr,
-                "conv": self.conv[0] if self.conv else 0}
-        if not self.layerwise:
-            plan = ops.lstm_plan(self._ws, head=self._head, per_diagonal=self._per_diagonal)
-            # (side by side: ops.lstm_fwd_pair runs the one-XCD forward kernel whatever one stack alone would take)
-            path["lstm_fwd"], path["lstm_bwd"] = ("big1" if self._paired else plan["fwd_path"]), plan["bwd_path"]
-        if self.layerwise:      # the layer-wise recurrence: "persistent" (one launch per layer for both directions, or per direction) or "per_frame"
-            plan = ops.lstm_bidir_plan(self._ws, per_frame=self._per_diagonal)      # (at the run length, with the call's per-frame request)
-            path["layer_recurrence"] = {2: "persistent", 1: "persistent_per_direction", 0: "per_frame"}[plan["path"]]
-            path["layer_product"] = self.precision      # its recurrent product: "f32" (vector ALUs) or "bf16x3" (bf16 MFMA)
+        ops.lstm_plan at the run length, with the head and the per-diagonal request of the call); a layer-wise stack names
+        `layer_recurrence` and `layer_product` instead (stacks.LayerStack.kernel_path)."""
+        path = {"fused_ctc_head": self._head is not None, "lookahead": self.lookahead, "paired": self.stack.paired,
+                "run_length": self._Tr, "conv": self.conv[0] if self.conv else 0}
+        path.update(self.stack.kernel_path(self._head))
         return path
 
     def final_state(self):
@@ -469,13 +448,10 @@ class Engine(ParamStore):
     def ctc(self, dense_labels, lengths, stage=0):
         Tr = self._Tr
         lengths = self.model_lengths(lengths)
-        if self._head is not None:       # (the loss is the forward launch's; dlogits will be the backward launch's)
-            if Tr < self.T and stage != 1:
-                self.dlogits[Tr:].zero_()
-            return self.loss
-        ops.ctc_loss_fwd_bwd(self.logits[:Tr], dense_labels, lengths, ws=self.ctc_ws, loss=self.loss,
-                             dlogits=self.dlogits[:Tr], stage=stage)
-        if Tr < self.T and stage != 1:
+        if self._head is None:           # (with the head the loss is the forward launch's; dlogits will be the backward launch's)
+            ops.ctc_loss_fwd_bwd(self.logits[:Tr], dense_labels, lengths, ws=self.ctc_ws, loss=self.loss,
+                                 dlogits=self.dlogits[:Tr], stage=stage)
+        if Tr < self.T and stage != 1:   # the never-visited tail carries no gradient
             self.dlogits[Tr:].zero_()
         return self.loss
 
@@ -509,120 +485,43 @@ class Engine(ParamStore):
     def backward(self, x, lengths, wait_for=None, per_diagonal=False):
         """Accumulates d(sum_b loss_b)/d(theta) into self.grads (for the batch of the last forward).
         wait_for: an event the backward RECURRENCE has to wait for (side-stream work placed beside the CTC stage)."""
-        T, B, D = x.shape
         x = x.contiguous()
-        ws, Tr = self._ws, self._Tr
-        H = self.H
-        dl = self.dlogits[:Tr].view(Tr * B, self.C)
+        stack, Tr = self.stack, self._Tr
         src_lengths, lengths = lengths, self.model_lengths(lengths)      # (the source lengths are the front convolution's alone)
-        if self.layerwise:
-            self._backward_layerwise(x, src_lengths, wait_for, per_diagonal)
-            return
-        head = self._head if not per_diagonal else None
-        if self._head is not None and head is None:
+        head = self._head
+        if head is not None and per_diagonal:
             raise _lib.AmdSpeechError("backward(per_diagonal=True) after a forward with the fused CTC head: repeat the forward too")
-        if head is not None:
-            pass                         # dlogits and dZ_top are formed inside lstm_bwd; dW_o / db_o follow it
-        elif self.lookahead:             # the output layer read the convolution's output; its dx is the convolution's dy
-            ops.linear_bwd(self.la_y[:Tr].view(Tr * B, H), self.p("output_w"), dl,
-                           self.g("output_w"), self.g("output_b"), need_dx=True, dx=self.la_dy[:Tr].view(Tr * B, H))
-            ops.lookahead_bwd(ws.ztop, self.p("lookahead_w"), self.la_dy[:Tr], lengths, dx=ws.dztop, dw=self.g("lookahead_w"),
-                              ws=self.la_ws)
-        elif not self.bidirectional:
-            ops.linear_bwd(ws.ztop.view(Tr * B, H), self.p("output_w"), dl,
-                           self.g("output_w"), self.g("output_b"), need_dx=True, dx=ws.dztop.view(Tr * B, H))
-        else:
-            wo, gwo, wb = self.p("output_w"), self.g("output_w"), self._ws_b
-            ops.linear_bwd(ws.ztop.view(Tr * B, H), wo[:H], dl, gwo[:H], self.g("output_b"), need_dx=True,
-                           dx=ws.dztop.view(Tr * B, H))
-            yb = self.ytop_b[:Tr].view(Tr * B, H)
-            ops.gemm(yb, dl, trans_a=True, out=gwo[H:], accumulate=True)                     # dW_o[H:] += y_b^T . dlogits
-            ops.gemm(dl, wo[H:], trans_b=True, out=self.dytop_b[:Tr].view(Tr * B, H))        # d y_b = dlogits . W_o[H:]^T
-            ops.reverse_sequences(self.dytop_b[:Tr], lengths, out=wb.dztop)
+        if head is None:                 # (with the head dlogits and dZ_top are formed inside the recurrence's launch; dW_o / db_o follow it)
+            # 1. output layer
+            self._output_bwd(self._tops, Tr)
+            # 2. lookahead: the output layer read the convolution's output; its dx is the convolution's dy
+            if self.lookahead:
+                y, dy = self._la_x
+                ops.lookahead_bwd(y, self.p("lookahead_w"), self.la_dy[:Tr], lengths, dx=dy, dw=self.g("lookahead_w"), ws=self.la_ws)
+            stack.take_dtops(lengths)
+        # 3. the side work the recurrence must not start beside
         if wait_for is not None:
             torch.cuda.current_stream(self.device).wait_event(wait_for)
-        paired = self.bidirectional and _BIDIR_PAIR and not per_diagonal and ops.lstm_pair_fusable(ws)
-        if paired:                       # the two stacks' layers side by side (ops.lstm_bwd_pair)
-            wb = self._ws_b
-            ops.lstm_bwd_pair(ws, self.p("kernel_0"), self.g("kernel_0"), self.g("bias_0"),
-                              wb, self.p("bw_kernel_0"), self.g("bw_kernel_0"), self.g("bw_bias_0"),
-                              self.layout.kernel_stride, self.layout.bias_stride, lengths)
-        else:
-            ops.lstm_bwd(ws, self.p("kernel_0"), self.layout.kernel_stride, self.g("kernel_0"), self.g("bias_0"),
-                         self.layout.bias_stride, lengths, per_diagonal=per_diagonal, head=head)
-        # the dense layers' weight gradients need nothing but the backward kernel's results: beside the first of the weight-gradient
-        # launches that follow it (ops.lstm_beside_tail) instead of behind the last
-        side = None
-        if _BESIDE_TAIL and not self.bidirectional and not self.normalization and not per_diagonal:
-            if self._tail_stream is None:
-                self._tail_stream = torch.cuda.Stream(self.device)
-            flags = ops.lstm_beside_tail(ws, self._tail_stream)
-            if flags & 1:
-                side = self._tail_stream
-                with torch.cuda.stream(side):
-                    if head is not None:
-                        ops.linear_bwd(ws.ztop.view(Tr * B, H), self.p("output_w"), dl, self.g("output_w"), self.g("output_b"), need_dx=False)
-                    if flags & 2:        # (with the front convolution: its gradients too, queued before the join below)
-                        self._input_linear_bwd(x, src_lengths, ws, Tr)
-                torch.cuda.current_stream(self.device).wait_stream(side)
-                if flags & 2:
-                    return
-                head = None
-        if head is not None:             # dW_o += Z_top^T . dlogits, db_o += column sums of dlogits
-            ops.linear_bwd(ws.ztop.view(Tr * B, H), self.p("output_w"), dl, self.g("output_w"), self.g("output_b"), need_dx=False)
-        if self.bidirectional:
-            wb = self._ws_b
-            if not paired:
-                ops.lstm_bwd(wb, self.p("bw_kernel_0"), self.layout.kernel_stride, self.g("bw_kernel_0"), self.g("bw_bias_0"),
-                             self.layout.bias_stride, lengths, per_diagonal=per_diagonal)
-            ops.reverse_sequences(wb.dz0, lengths, out=ws.dz0, accumulate=True)              # both stacks read the same Z_0
+        # 4. recurrence
+        stack.backward(lengths, per_diagonal, head, pair=_BIDIR_PAIR)
+        # 5. tail overlap: the dense layers' weight gradients beside the first of the weight-gradient launches that follow the
+        # backward kernel (stacks.UniStack.beside_tail) instead of behind the last
+        side, dz0_ready = stack.beside_tail() if _BESIDE_TAIL and not self.normalization and not per_diagonal else (None, False)
+        if side is not None:
+            with torch.cuda.stream(side):
+                if head is not None:
+                    self._output_bwd(self._tops, Tr, need_dx=False)
+                if dz0_ready:            # (with the front convolution: its gradients too, queued before the join below)
+                    self._input_linear_bwd(x, src_lengths, Tr)
+            torch.cuda.current_stream(self.device).wait_stream(side)
+        elif head is not None:
+            self._output_bwd(self._tops, Tr, need_dx=False)
+        # 6. batch norm
         if self.normalization:
-            grp = self._dp_group() if self.sync_batch_norm else None
-            if grp is not None and grp.world > 1:
-                ops.batchnorm_bwd_dp(ws.dz0, self.bn_xhat, self.bn_inv_std, ws.dz0, grp, self.bn_scratch)
-            else:
-                ops.batchnorm_bwd(ws.dz0, self.bn_xhat[:Tr], self.bn_inv_std[:Tr], ws.dz0)
-        self._input_linear_bwd(x, src_lengths, ws, Tr)
-
-    def _backward_layerwise(self, x, src_lengths, wait_for, per_diagonal):
-        ws, Tr, B, H, D = self._ws, self._Tr, self.B, self.H, self.D
-        lengths = self.model_lengths(src_lengths)
-        dl = self.dlogits[:Tr].view(Tr * B, self.C)
-        wo, gwo = self.p("output_w"), self.g("output_w")
-        ops.linear_bwd(ws.ytop_fw.view(Tr * B, H), wo[:H], dl, gwo[:H], self.g("output_b"), need_dx=True,
-                       dx=ws.dytop_fw.view(Tr * B, H))
-        ops.gemm(ws.ytop_bw.view(Tr * B, H), dl, trans_a=True, out=gwo[H:], accumulate=True)          # dW_o[H:] += y_bw^T . dlogits
-        ops.gemm(dl, wo[H:], trans_b=True, out=ws.dytop_bw.view(Tr * B, H))                            # d y_bw (forward time)
-        if wait_for is not None:
-            torch.cuda.current_stream(self.device).wait_event(wait_for)
-        ks, _ = self._cells(self.params)
-        dks, dbs = self._cells(self.grads)
-        ops.lstm_bidir_bwd(ws, ks, dks, dbs, lengths, per_frame=per_diagonal)
-        if self.normalization:
-            grp = self._dp_group() if self.sync_batch_norm else None
-            if grp is not None and grp.world > 1:
-                ops.batchnorm_bwd_dp(ws.dz0, self.bn_xhat, self.bn_inv_std, ws.dz0, grp, self.bn_scratch)
-            else:
-                ops.batchnorm_bwd(ws.dz0, self.bn_xhat[:Tr], self.bn_inv_std[:Tr], ws.dz0)
-        self._input_linear_bwd(x, src_lengths, ws, Tr)
-
-    def check(self):
-        """Synchronous health check of the dataflow LSTM kernels: their waits are bounded, and a time-out (the
-        workgroups of one launch were not all resident -- another kernel held CUs) leaves an error flag behind
-        instead of hanging.  Raises AmdSpeechError; results of that step are invalid.  Two stacks: BOTH workspaces are asked
-        before anything is raised (the status call is what makes a workspace distrust the hand-off state an incomplete launch
-        left behind), and a fault that is no time-out goes first: it must not hide behind a recoverable one."""
-        if self.layerwise:
-            ops.lstm_bidir_status(self._ws)
-            return
-        errors = []
-        for ws in (self._ws, self._ws_b) if self.bidirectional else (self._ws,):
-            try:
-                ops.lstm_status(ws)
-            except _lib.AmdSpeechError as exc:
-                errors.append(exc)
-        if errors:
-            raise next((e for e in errors if not isinstance(e, _lib.DataflowTimeout)), errors[0])
+            self._batchnorm_bwd(stack.dz0, Tr)
+        # 7. input Linear and convolution
+        if side is None or not dz0_ready:
+            self._input_linear_bwd(x, src_lengths, Tr)
 
     def mini_batch(self, x, lengths, dense_labels, keep_in=1.0, keep_out=1.0, seed=0, use_state=False,
                    compute_gradients=True, max_len=None, beside_ctc=None, marks=None, beside_forward=None, per_diagonal=False):
@@ -654,7 +553,7 @@ class Engine(ParamStore):
                 return
             if self._aux_stream is None:
                 self._aux_stream = torch.cuda.Stream(self.device)
-            if not self.layerwise and ops.lstm_beside_forward(self._ws, self._aux_stream) > 0:
+            if self.stack.beside_forward(self._aux_stream) > 0:
                 after = torch.cuda.Event()
                 after.record(self._aux_stream)
                 placed.append(beside_forward(after))
@@ -664,49 +563,47 @@ class Engine(ParamStore):
         mark("forward")
         pending = [ev for ev in placed if ev is not None]
         late = [h for h in (beside_ctc, (beside_forward if not placed else None)) if h is not None]
-        if self._head is not None:
+
+        def place_late():              # the late hooks, ordered behind what the current stream holds now
+            after = torch.cuda.Event()
+            after.record(torch.cuda.current_stream(self.device))
+            for h in late:
+                ev = h(after)
+                if ev is not None:
+                    pending.append(ev)
+
+        fused = self._head is not None
+        if fused:
             # The CTC stage ran inside the forward launch and will finish inside the backward one: there is no stage to place work
             # beside.  Hooks that need the logits are ordered behind the forward launch and JOINED BEHIND the backward pass: short
             # kernels and copies that become runnable together with the backward kernel either slip in front of it (the library's
             # own side-stream fills keep that launch waiting ~0.1 ms anyway) or run when it ends -- they depend on nothing of it,
             # so its workgroups never wait for more than their duration.
-            after = torch.cuda.Event()
-            after.record(torch.cuda.current_stream(self.device))
-            for h in late:
-                ev = h(after)
-                if ev is not None:
-                    pending.append(ev)
+            place_late()
             self.ctc(dense_labels, lengths)
-            mark("ctc")
-            if compute_gradients:
-                self.backward(x, lengths, per_diagonal=per_diagonal)
-                mark("backward")
-            cur = torch.cuda.current_stream(self.device)
-            for ev in pending:
-                cur.wait_event(ev)
-            return self.loss
-        if late:
+        elif late:
             # behind the output layer and the log-softmax (both fill the chip and are short), beside the CTC recursions
             self.ctc(dense_labels, lengths, stage=1)
-            after = torch.cuda.Event()
-            after.record(torch.cuda.current_stream(self.device))
-            for h in late:
-                ev = h(after)
-                if ev is not None:
-                    pending.append(ev)
+            place_late()
             self.ctc(dense_labels, lengths, stage=2)
         else:
             self.ctc(dense_labels, lengths)
         mark("ctc")
         cur = torch.cuda.current_stream(self.device)
-        for ev in pending[:-1]:
+        # the side work is joined in front of the backward RECURRENCE (its last event inside backward(), behind the output layer's
+        # gradients) -- or, with the fused head, behind the whole backward pass
+        ahead = [] if fused else pending
+        for ev in ahead[:-1]:
             cur.wait_event(ev)
-        done = pending[-1] if pending else None
+        done = ahead[-1] if ahead else None
         if compute_gradients:
             self.backward(x, lengths, wait_for=done, per_diagonal=per_diagonal)
             mark("backward")
         elif done is not None:
             cur.wait_event(done)      # the next recurrence kernel must not start beside it
+        if fused:
+            for ev in pending:
+                cur.wait_event(ev)
         return self.loss
 
     # ---- data parallel (the optimiser step itself is ParamStore.apply) ----------------

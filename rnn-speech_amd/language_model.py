@@ -20,6 +20,7 @@ import torch
 from . import checkpoint
 from . import labels as _labels
 from . import ops
+from . import stacks
 from .engine import PRECISIONS, ParamLayout, ParamStore
 
 
@@ -36,12 +37,12 @@ class LmEngine(ParamStore):
         self.B, self.T = batch_size, max_len
         self.precision = precision
         ParamStore.__init__(self, ParamLayout(num_layers, hidden, num_labels, num_labels), device)
-        self.lstm_ws = ops.LstmWorkspace(max_len, batch_size, hidden, num_layers, device=self.device, precision=PRECISIONS[precision])
+        self.stack = stacks.UniStack(self, max_len, batch_size, hidden, num_layers, PRECISIONS[precision])
         self.logits = torch.empty(max_len, batch_size, num_labels, device=self.device)
         self.dlogits = torch.empty_like(self.logits)
         self.nll = torch.zeros(max_len, batch_size, device=self.device)
         self.loss = torch.zeros(batch_size, device=self.device)
-        self._ws, self._Tr, self._per_diagonal = self.lstm_ws, max_len, False
+        self._Tr = max_len               # steps the last forward visited
         self.init_parameters(seed)
 
     def _describe(self):
@@ -57,17 +58,12 @@ class LmEngine(ParamStore):
         """tok int32 [B, >= T+1] device, lengths int32 [B] device -> logits [T,B,V] (the engine's buffer; rows past the run length
         are the output bias)."""
         self._check_batch(tok, lengths)
-        B, H = self.B, self.H
-        Tr = self._run_length(max_len)
-        ws = self.lstm_ws.prefix(Tr)
-        self._ws, self._Tr, self._per_diagonal = ws, Tr, bool(per_diagonal)
-        ws.set_dropout(keep_in, keep_out, seed)
-        ops.embed_fwd(tok, lengths, self.p("input_w"), self.p("input_b"), ws.z0)
-        ops.lstm_fwd(ws, self.p("kernel_0"), self.layout.kernel_stride, self.p("bias_0"), self.layout.bias_stride, lengths,
-                     None, None, training=training, per_diagonal=per_diagonal)
-        ops.linear_fwd(ws.ztop.view(Tr * B, H), self.p("output_w"), self.p("output_b"), out=self.logits[:Tr].view(Tr * B, self.V))
-        if Tr < self.T:
-            self.logits[Tr:] = self.p("output_b")
+        Tr = self._Tr = self._run_length(max_len)
+        self.stack.lay_out(Tr, keep_in, keep_out, seed)
+        ops.embed_fwd(tok, lengths, self.p("input_w"), self.p("input_b"), self.stack.z0)
+        self.stack.forward(lengths, None, None, training, per_diagonal)      # (zero initial state: rows are independent sentences)
+        self._output_fwd(self.stack.tops(lengths), Tr)
+        self._fill_tail(Tr)
         return self.logits
 
     def mini_batch(self, tok, lengths, keep_in=1.0, keep_out=1.0, seed=0, max_len=None, scale=1.0, compute_gradients=True,
@@ -76,7 +72,7 @@ class LmEngine(ParamStore):
         embed_bwd.  The gradient ADDED to self.grads is `scale` times that of the SUM of the NLL over tokens and rows; self.loss [B]
         and self.nll [T,B] are unscaled.  per_diagonal: the repeat of a mini-batch whose whole-sequence launch timed out."""
         self.forward(tok, lengths, keep_in, keep_out, seed, max_len, training=compute_gradients, per_diagonal=per_diagonal)
-        ws, Tr, B, H = self._ws, self._Tr, self.B, self.H
+        stack, Tr = self.stack, self._Tr
         targets = tok[:, 1:]
         if Tr < self.T:
             self.nll[Tr:].zero_()
@@ -84,11 +80,9 @@ class LmEngine(ParamStore):
                          dlogits=self.dlogits[:Tr] if compute_gradients else None, want_grad=compute_gradients)
         if not compute_gradients:
             return self.loss
-        ops.linear_bwd(ws.ztop.view(Tr * B, H), self.p("output_w"), self.dlogits[:Tr].view(Tr * B, self.V),
-                       self.g("output_w"), self.g("output_b"), need_dx=True, dx=ws.dztop.view(Tr * B, H))
-        ops.lstm_bwd(ws, self.p("kernel_0"), self.layout.kernel_stride, self.g("kernel_0"), self.g("bias_0"),
-                     self.layout.bias_stride, lengths, per_diagonal=per_diagonal)
-        ops.embed_bwd(tok, lengths, ws.dz0, self.g("input_w"), self.g("input_b"))
+        self._output_bwd(stack.tops(lengths), Tr)
+        stack.backward(lengths, per_diagonal)
+        ops.embed_bwd(tok, lengths, stack.dz0, self.g("input_w"), self.g("input_b"))
         return self.loss
 
     def mini_batch_recovering(self, tok, lengths, kept_grads=None, compute_gradients=True, **kw):
@@ -113,11 +107,7 @@ class LmEngine(ParamStore):
 
     def kernel_path(self):
         """The LSTM path of the LAST forward and of the backward that belongs to it, named as Engine.kernel_path names them."""
-        plan = ops.lstm_plan(self._ws, per_diagonal=self._per_diagonal)
-        return {"run_length": self._Tr, "lstm_fwd": plan["fwd_path"], "lstm_bwd": plan["bwd_path"]}
-
-    def check(self):
-        ops.lstm_status(self._ws)
+        return dict(self.stack.kernel_path(), run_length=self._Tr)
 
 
 def sentence_rows(id_lists, num_labels, width=None):

@@ -432,13 +432,25 @@ def lstm_ctc_fusable(ws, C_, U, per_diagonal=False):
     return bool(ws.lib.amdspeech_lstm_ctc_fusable(C.byref(ws.desc), int(C_), int(U)))
 
 
+def _plan_desc(ws, per_diagonal):
+    """A copy of the workspace's descriptor with the per-diagonal (per-frame) request as its only flag: what the plan queries read,
+    so that they leave ws.desc alone."""
+    d = ws.desc
+    return _l.LstmDesc(d.T, d.B, d.H, d.L, d.keep_in, d.keep_out, d.seed, d.precision, _l.LSTM_PER_DIAGONAL if per_diagonal else 0)
+
+
+def _head_c_u(head):
+    """(C, U) of the CTC head a plan query is asked about: a CtcHead, or (C, U), or None (no head: (0, 0))."""
+    if head is None:
+        return 0, 0
+    return (head.c.C, head.c.U) if isinstance(head, CtcHead) else (int(head[0]), int(head[1]))
+
+
 def lstm_plan(ws, head=None, per_diagonal=False):
     """The kernel path lstm_fwd / lstm_bwd on this workspace layout take (amdspeech.h: amdspeech_lstm_plan), as a dict of ints with
     "fwd_path" / "bwd_path" as names ("flow", "big1", "big", "hoist", "diag", "diag_bf3").  head: a CtcHead, or (C, U), or None.
     Read-only: nothing is launched and the workspace's state is left alone."""
-    c_u = (0, 0) if head is None else ((head.c.C, head.c.U) if isinstance(head, CtcHead) else (int(head[0]), int(head[1])))
-    d = _l.LstmDesc(ws.desc.T, ws.desc.B, ws.desc.H, ws.desc.L, ws.desc.keep_in, ws.desc.keep_out, ws.desc.seed, ws.desc.precision,
-                    _l.LSTM_PER_DIAGONAL if per_diagonal else 0)
+    c_u, d = _head_c_u(head), _plan_desc(ws, per_diagonal)
     info = _l.LstmPlanInfo()
     _l.check(ws.lib.amdspeech_lstm_plan(C.byref(d), c_u[0], c_u[1], C.byref(info)), "lstm_plan")
     out = _plan_dict(info)
@@ -446,28 +458,25 @@ def lstm_plan(ws, head=None, per_diagonal=False):
     return out
 
 
+def _plan_xw(entry, ws, head, per_diagonal):
+    """One of the forward dataflow launch's x-worker plan numbers (amdspeech_<entry>: an int, negative for a bad descriptor)."""
+    c_u, d = _head_c_u(head), _plan_desc(ws, per_diagonal)
+    n = int(getattr(ws.lib, "amdspeech_" + entry)(C.byref(d), c_u[0], c_u[1]))
+    if n < 0:
+        raise ValueError(entry + ": bad descriptor")
+    return n
+
+
 def lstm_plan_xw_halves(ws, head=None, per_diagonal=False):
     """The x-product workers' share of the forward dataflow launch in HALF K blocks per recurrence wave (amdspeech.h:
     amdspeech_lstm_plan_xw_halves): 0 none, 2 one block, 3 a block and a half (half roles).  Read-only, like lstm_plan."""
-    c_u = (0, 0) if head is None else ((head.c.C, head.c.U) if isinstance(head, CtcHead) else (int(head[0]), int(head[1])))
-    d = _l.LstmDesc(ws.desc.T, ws.desc.B, ws.desc.H, ws.desc.L, ws.desc.keep_in, ws.desc.keep_out, ws.desc.seed, ws.desc.precision,
-                    _l.LSTM_PER_DIAGONAL if per_diagonal else 0)
-    n = int(ws.lib.amdspeech_lstm_plan_xw_halves(C.byref(d), c_u[0], c_u[1]))
-    if n < 0:
-        raise ValueError("lstm_plan_xw_halves: bad descriptor")
-    return n
+    return _plan_xw("lstm_plan_xw_halves", ws, head, per_diagonal)
 
 
 def lstm_plan_xw_ksteps(ws, head=None, per_diagonal=False):
     """How many of the four k-steps of the K block below theirs the half roles of the forward dataflow launch take as well
     (amdspeech.h: amdspeech_lstm_plan_xw_ksteps); 0: none.  Read-only, like lstm_plan."""
-    c_u = (0, 0) if head is None else ((head.c.C, head.c.U) if isinstance(head, CtcHead) else (int(head[0]), int(head[1])))
-    d = _l.LstmDesc(ws.desc.T, ws.desc.B, ws.desc.H, ws.desc.L, ws.desc.keep_in, ws.desc.keep_out, ws.desc.seed, ws.desc.precision,
-                    _l.LSTM_PER_DIAGONAL if per_diagonal else 0)
-    n = int(ws.lib.amdspeech_lstm_plan_xw_ksteps(C.byref(d), c_u[0], c_u[1]))
-    if n < 0:
-        raise ValueError("lstm_plan_xw_ksteps: bad descriptor")
-    return n
+    return _plan_xw("lstm_plan_xw_ksteps", ws, head, per_diagonal)
 
 
 def lstm_fwd(ws, kernels, kernel_stride, biases, bias_stride, lengths, h0=None, c0=None, training=False, per_diagonal=False, head=None):
@@ -646,8 +655,7 @@ def lstm_bidir_plan(ws, per_frame=False):
     """What lstm_bidir_fwd / lstm_bidir_bwd on this workspace layout launch for the recurrence (amdspeech.h: amdspeech_lstm_bidir_plan),
     as a dict of ints: path, cus, and kpw / waves / groups / wgs / lds of the forward (fwd_*) and backward (bwd_*) kernel.
     Read-only: nothing is launched and ws.desc.flags is left alone."""
-    d = _l.LstmDesc(ws.desc.T, ws.desc.B, ws.desc.H, ws.desc.L, ws.desc.keep_in, ws.desc.keep_out, ws.desc.seed, ws.desc.precision,
-                    _l.LSTM_PER_DIAGONAL if per_frame else 0)
+    d = _plan_desc(ws, per_frame)
     info = _l.LstmBidirPlanInfo()
     _l.check(ws.lib.amdspeech_lstm_bidir_plan(C.byref(d), C.byref(info)), "lstm_bidir_plan")
     return _plan_dict(info)

@@ -10,7 +10,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from dp_oracle_engine import CpuLanguageModel, OracleAcousticModel  # noqa: E402
-from rnn_speech_amd import checkpoint, lib, ops  # noqa: E402
+from rnn_speech_amd import checkpoint, lib, ops, stacks  # noqa: E402
 from rnn_speech_amd.engine import Engine, ParamLayout  # noqa: E402
 
 
@@ -168,9 +168,13 @@ def test_loading_is_strict_about_names_and_shapes(which):
 
 
 class _TwoStacks(object):
-    """What Engine.check() reads of a bidirectional "top" engine."""
-    layerwise, bidirectional, _ws, _ws_b = False, True, "ws", "ws_b"
+    """What Engine.check() reads of a bidirectional "top" engine: its driver, and of that the two stacks' workspaces."""
     check, healthy = Engine.check, Engine.healthy
+
+    def __init__(self):
+        self.stack = object.__new__(stacks.JoinedStack)
+        self.stack.fw, self.stack.bw = object.__new__(stacks.UniStack), object.__new__(stacks.UniStack)
+        self.stack.fw.ws, self.stack.bw.ws = "ws", "ws_b"
 
 
 @pytest.mark.parametrize("fault_on_b", (False, True))

@@ -12,6 +12,7 @@ reference-generated vectors ("parity unpinned" -- see oracle/*.py headers).
 Usage:  python tools/make_golden.py
         python tools/make_golden.py --checkpoints <checkout of 9bbf15b>     (checkpoint_*.npz only; needs no reference)
         AMDSPEECH_LIB=<libamdspeech.so of the parent commit> python tools/make_golden.py --gemm-plans     (gemm_plans.npz only; no reference, no GPU)
+        python tools/make_golden.py --engine-calls     (engine_calls.json only; on the MI355X, from the engine of the parent commit; no reference)
 """
 import json
 import os
@@ -283,7 +284,27 @@ def gemm_plan_goldens(child_out=None):
     print("variants:", seen)
 
 
+def engine_call_goldens(out_path=None):
+    """tests/golden/engine_calls.json: what tests/engine_calls.py records for every configuration of its CONFIGS, one line per entry.
+    Needs the MI355X and no reference.  Run it on the engine.py / language_model.py / ops.py of the commit BEFORE a change of the
+    engine's structure, never on the tree under test: tests/test_gpu_engine_calls.py holds the current engine against this file."""
+    root = os.path.dirname(OUT)
+    sys.path[:0] = [os.path.dirname(root), root]
+    import engine_calls
+    recorded = {}
+    for name in engine_calls.CONFIGS:
+        recorded[name] = engine_calls.record(name)
+        print(name, len(recorded[name]), "entries", flush=True)
+    path = out_path or os.path.join(OUT, "engine_calls.json")
+    engine_calls.dump(recorded, path)
+    print(path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
+    if "--engine-calls" in sys.argv:      # python tools/make_golden.py --engine-calls [file]     (on the MI355X, at the parent commit's engine)
+        rest = sys.argv[sys.argv.index("--engine-calls") + 1:]
+        engine_call_goldens(rest[0] if rest else None)
+        sys.exit(0)
     if "--gemm-plans" in sys.argv or "--gemm-plans-child" in sys.argv:      # AMDSPEECH_LIB=<parent build> python tools/make_golden.py --gemm-plans
         gemm_plan_goldens(sys.argv[sys.argv.index("--gemm-plans-child") + 1] if "--gemm-plans-child" in sys.argv else None)
         sys.exit(0)
