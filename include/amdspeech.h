@@ -1292,6 +1292,58 @@ int amdspeech_ctc_beam_search_host_fused(const float* logits, const int* lengths
                                          amdspeech_lm_step_fn step, void* user, int* ids, int* out_len, float* log_prob,
                                          int* n_found, int max_threads);
 
+/* ------------------------------------------------- blank-frame skipping ---
+ * What shortens the input of the host beam decoders above (no reference counterpart: an opt-in deviation, config key
+ * decode_blank_skip; nothing of it is called at the key's default): the frames on which a CTC model is nearly sure of blank are
+ * dropped before the search, per utterance and in order ("phone-synchronous decoding").  ctc_blank_skip.hip; DESIGN.md 4.7b.
+ *   logits      float [T][B][C] (device)    blank is class C-1
+ *   lengths     int32 [B] (device)          as amdspeech_ctc_greedy_decode takes them; n_b = min(max(lengths[b], 0), T)
+ *   log_threshold  log of the blank probability above which a frame is skippable; finite and <= 0
+ * Per utterance b, every operation one float32 operation:
+ *   lpb[t]  = (logits[t][b][C-1] - max_c logits[t][b][c]) - log(sum_c exp(logits[t][b][c] - max))
+ *   skip[t] = t < n_b && lpb[t] >= log_threshold        (a NaN lpb compares false: the frame is kept)
+ *   keep[t] = t < n_b && !(skip[t] && t > 0 && skip[t-1])
+ * The run rule: of every maximal run of skippable frames the FIRST is kept and the rest are dropped.  A repeated label on both
+ * sides of a blank run then still has a blank frame between its two spikes, so merge_repeated and the prefix beam's "a repeat
+ * starts a new character only after a blank" rule see what they saw before; dropping whole runs would merge "a _ a" into "a".
+ * Outputs, with j = 0 .. n'_b - 1 walking the kept frames of b in increasing t:
+ *   out_logits  float [T][B][C]   out_logits[j][b][:] = logits[t_j][b][:], copied bit for bit; every other word is written as 0
+ *   out_lengths int32 [B]         n'_b
+ *   src_frame   int32 [B][T]      src_frame[b][j] = t_j; every other word is written as -1
+ *   blank_logp  float [T][B] or NULL   the stage quantity lpb[t] for t < n_b, 0 elsewhere (for the tests)
+ * The maximum and the sum of a row are taken in an order that is a fixed function of C (lane l of a wavefront, or of a 256-thread
+ * workgroup above 1024 classes, adds its own words in increasing c, the lanes meet in a 32-16-8-4-2-1 xor butterfly, the four
+ * waves of a workgroup in wave order): no floating-point atomics, two calls give the same bits, and a row's outputs depend only on
+ * that row's own frames and length -- not on B or on the row's position.  |lpb - exact| <= u (6 M + C + 5 ln C + 4) to first order,
+ * u = 2^-24, M the largest |logit| of the frame.  A frame at or past n_b is not read.
+ * The call is stream-ordered, does not synchronise on the host and does not allocate: three plain launches (rows, scan, gather).
+ *   ws   device, amdspeech_ctc_blank_skip_workspace_bytes(T, B, C) bytes (0 for a bad shape): one flag byte per frame
+ * out_logits must not overlap logits (rows move forward in time): such a call is refused.  Limits: 2 <= C <= 4096, T >= 1, B >= 1,
+ * T * B * C < 2^31; logits and out_logits 16-byte aligned when C % 4 == 0.  AMDSPEECH_EINVAL (a bad argument: T, B or C below its
+ * minimum, a log_threshold that is NaN, infinite or above 0, a null pointer but for blank_logp, overlap, alignment) or
+ * AMDSPEECH_EUNSUPPORTED (a size limit of the kernels: C > 4096, T * B * C >= 2^31) with a message that names the limit, and
+ * nothing is launched.
+ * amdspeech_ctc_blank_skip_plan: the kernels and launch geometry of a shape as plain numbers, a READ-ONLY view of the plan the
+ * launch itself reads (one function decides for both); no device is needed and nothing is launched.
+ *   kernel, words_per_lane, vec   the row kernel, the words of a row each lane holds (4, 8, 16 | 8, 16) and how it loads them: 4 = 16-byte
+ *                    vectors (C % 4 == 0), 1 = single words.  The gather copies with the same width
+ *   c_min .. c_max   the range of C with the same kernel and words_per_lane: the tests walk the boundaries from it
+ *   rows_threads, rows_per_workgroup, rows_grid   256; 4 (wave) or 1 (block); ceil(T B / rows_per_workgroup)
+ *   t_chunk, chunks  256 frames per step of the per-utterance scan, one per thread, the count of kept frames carried; ceil(T / 256)
+ *   scan_threads, scan_grid       256; B
+ *   gather_threads, gather_grid   256; ceil(T B C / vec / 256)
+ *   launches, workspace_bytes     3; T B rounded up to 256                                                                     */
+#define AMDSPEECH_BLANK_SKIP_KERNEL_WAVE 0  /* one wavefront per row, words_per_lane logits in each lane's registers (C <= 1024) */
+#define AMDSPEECH_BLANK_SKIP_KERNEL_BLOCK 1 /* one 256-thread workgroup per row, the maximum and the sum across its four waves through LDS */
+typedef struct amdspeech_ctc_blank_skip_plan_info {
+    int kernel, words_per_lane, vec, c_min, c_max, rows_threads, rows_per_workgroup, rows_grid, t_chunk, chunks, scan_threads, scan_grid,
+        gather_threads, gather_grid, launches, workspace_bytes;
+} amdspeech_ctc_blank_skip_plan_info;
+size_t amdspeech_ctc_blank_skip_workspace_bytes(int T, int B, int C);
+int amdspeech_ctc_blank_skip_plan(int T, int B, int C, amdspeech_ctc_blank_skip_plan_info* out);
+int amdspeech_ctc_blank_skip(void* stream, const float* logits, const int* lengths, int T, int B, int C, float log_threshold,
+                             float* out_logits, int* out_lengths, int* src_frame, float* blank_logp, void* ws);
+
 #ifdef __cplusplus
 }
 #endif

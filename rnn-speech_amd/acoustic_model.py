@@ -108,25 +108,40 @@ class _AsyncBeamDecoder(object):
         self._pending = collections.deque()
         self._results_ready = []
         self._last_copy = None
+        self._len_bufs = {}                       # blank-frame skipping: a pinned int32 [B] per logits buffer, made when first needed
 
-    def submit(self, after_event, Tr, lengths, dense, num_labels):
-        """Called where the logits of this mini-batch are complete on the engine's stream (`after_event`)."""
+    def submit(self, after_event, Tr, lengths, dense, num_labels, skipped=None):
+        """Called where the logits of this mini-batch are complete on the engine's stream (`after_event`).  skipped: None, or what
+        blank-frame skipping made of logits[:Tr] on that stream (device tensors: compact [Tr,B,C], new lengths [B]) -- the copy
+        then takes those, the new lengths into a pinned row of their own, and the host thread cuts the buffer at their maximum."""
         while not self._free:                     # (every buffer in flight: collect the oldest first)
             self._results_ready.append(self._collect_one())
         buf = self._free.pop()
+        host_len = None
+        if skipped is not None:
+            after_event = torch.cuda.Event()      # (the skip's launches are on the engine's stream, behind the caller's event)
+            after_event.record(torch.cuda.current_stream(self.engine.device))
+            host_len = self._len_bufs.get(id(buf))
+            if host_len is None:
+                host_len = self._len_bufs[id(buf)] = torch.empty(buf.shape[1], dtype=torch.int32).pin_memory()
         self._copy_stream.wait_event(after_event)
         with torch.cuda.stream(self._copy_stream):
-            buf[:Tr].copy_(self.engine.logits[:Tr], non_blocking=True)
+            buf[:Tr].copy_(self.engine.logits[:Tr] if skipped is None else skipped[0], non_blocking=True)
+            if skipped is not None:
+                host_len.copy_(skipped[1], non_blocking=True)
             done = torch.cuda.Event()
             done.record(self._copy_stream)
         self._last_copy = done
         lens = np.minimum(np.asarray(lengths, np.int32), Tr).astype(np.int32)
-        fut = self._pool.submit(self._decode, buf, done, Tr, lens, _truth_rows(dense, num_labels), num_labels)
+        fut = self._pool.submit(self._decode, buf, done, Tr, lens, _truth_rows(dense, num_labels), num_labels, host_len)
         self._pending.append((fut, buf))
 
-    def _decode(self, buf, done, Tr, lens, truth_rows, num_labels):
+    def _decode(self, buf, done, Tr, lens, truth_rows, num_labels, host_len=None):
         while not done.query():              # (not done.synchronize(): that spins on a core for the milliseconds the copy
             time.sleep(0.0002)               #  waits behind the backward kernel, which leaves it no compute unit)
+        if host_len is not None:             # blank-frame skipping: the kept frames lie at the front, host_len of them per row
+            lens = host_len.numpy().copy()
+            Tr = max(int(lens.max()), 1)
         ids, out_len, _ = ops.ctc_beam_search(buf[:Tr].numpy(), lens, self.beam_width, self.merge_repeated,
                                               max_threads=self.threads)
         B = len(truth_rows)
@@ -239,6 +254,10 @@ class AcousticModel(checkpoint.TrainedModel):
         self.save_optimizer_state = True   # native .npz also carries Adam m/v/step and the RNN state
         self.beam_width = 100
         self.merge_repeated = True
+        # config key `decode_blank_skip`: 0 (off: every beam decoder reads the logits themselves, nothing is launched or allocated) or
+        # the blank probability at and above which a frame is skippable in front of EVERY beam decoder (_decoder_input)
+        self.decode_blank_skip = 0.0
+        self._skip_bufs = None
         # config key `lm_weight` > 0: a language_model.NbestRescorer that picks among the beam decoder's n-best paths in process_input /
         # evaluate_full.  None (the default): the decoder's own best path, nothing of the language model is loaded
         self.rescorer = None
@@ -498,7 +517,8 @@ class AcousticModel(checkpoint.TrainedModel):
 
             def decode_hook(after, _self=self, _lengths=self._model_lengths_host(lengths), _dense=dense):
                 # (the logits of THIS mini-batch exist behind `after`: their way to the host starts beside the CTC stage)
-                _self._async_beam.submit(after, eng._Tr, _lengths, _dense, _self.num_labels)
+                skipped = _self._blank_skip(eng.logits[:eng._Tr], _self._model_lengths_dev(dlen)) if _self.decode_blank_skip else None
+                _self._async_beam.submit(after, eng._Tr, _lengths, _dense, _self.num_labels, skipped=skipped)
                 return None
         # the next batch's upload + front end need nothing of this step: beside the forward recurrence where that leaves XCDs
         # idle, else beside the CTC stage (Engine.mini_batch)
@@ -586,12 +606,36 @@ class AcousticModel(checkpoint.TrainedModel):
         dist, tlen = self._error_rate_launch(dlen, dense)
         return float(np.mean(dist.cpu().numpy() / tlen.astype(np.float64)))
 
+    def _blank_skip(self, logits, dlen):
+        """ops.ctc_blank_skip on the current (the engine's) stream into buffers of the model's own, made at the first call:
+        (compact, new lengths), both on the device.  Nothing waits."""
+        if self._skip_bufs is None or self._skip_bufs[0].shape[1:] != logits.shape[1:] or self._skip_bufs[0].shape[0] < logits.shape[0]:
+            T, B, _ = logits.shape
+            self._skip_bufs = (torch.empty_like(logits), torch.empty(B, device=logits.device, dtype=torch.int32),
+                               torch.empty(B * T, device=logits.device, dtype=torch.int32))
+        out, new_len, src = self._skip_bufs
+        T, B = logits.shape[:2]
+        compact, new_len, _ = ops.ctc_blank_skip(logits, dlen, self.decode_blank_skip, out=out[:T], new_lengths=new_len,
+                                                 src_frame=src[:B * T].view(B, T))
+        return compact, new_len
+
+    def _decoder_input(self, logits, dlen):
+        """What a beam decoder reads: (logits, lengths).  With decode_blank_skip at 0 the very objects it was given -- nothing is
+        launched.  Otherwise the blank-frame skip runs on the engine's stream, the new lengths come to the host (the copy the
+        decoders make of their lengths anyway; it drains the stream as their copy of the logits would), and the decoders get the
+        compact logits cut at the longest row: every cost of theirs is proportional to the frames they are handed."""
+        if not getattr(self, "decode_blank_skip", 0.0):       # (getattr: objects that stand in for the model in tests)
+            return logits, dlen
+        compact, new_len = self._blank_skip(logits, dlen)
+        lens = new_len.cpu()
+        return compact[:max(int(lens.max()), 1)], lens
+
     def _error_rate_launch(self, dlen, dense):
         """mean over the batch of edit_distance(prediction, truth) / len(truth) (:370); truth keeps the
         EOS token, drops id 0, and empty rows are [C-1] (:155-159).  Decode, merge and distance run on
         the GPU; returns (device distances [B], host truth lengths): one 4*B-byte copy comes back later."""
         if self.train_decoder == "beam":
-            hid, hlen, _ = ops.ctc_beam_search(self.engine.logits, dlen, self.beam_width, self.merge_repeated)
+            hid, hlen, _ = ops.ctc_beam_search(*AcousticModel._decoder_input(self, self.engine.logits, dlen), self.beam_width, self.merge_repeated)
             dev0 = self.engine.device
             ids, out_len = torch.as_tensor(hid).to(dev0), torch.as_tensor(hlen).to(dev0)
         else:
@@ -779,9 +823,9 @@ class AcousticModel(checkpoint.TrainedModel):
     def _decode(self, dlen):
         """Dense int32 prediction matrix [B, width] padded with num_labels."""
         if self.decoder == "beam" and self.rescorer is not None:      # config key lm_weight > 0: n-best list, the language model's pick
-            ids, out_len = self.rescorer(self.engine.logits, dlen, self.beam_width, self.merge_repeated)
+            ids, out_len = self.rescorer(*AcousticModel._decoder_input(self, self.engine.logits, dlen), self.beam_width, self.merge_repeated)
         elif self.decoder == "beam":
-            ids, out_len, _ = ops.ctc_beam_search(self.engine.logits, dlen, self.beam_width, self.merge_repeated)
+            ids, out_len, _ = ops.ctc_beam_search(*AcousticModel._decoder_input(self, self.engine.logits, dlen), self.beam_width, self.merge_repeated)
         else:
             ids, out_len = ops.ctc_greedy_decode(self.engine.logits, dlen, ws=self.engine.ctc_ws)
             ids, out_len = ids.cpu().numpy(), out_len.cpu().numpy()

@@ -116,6 +116,7 @@ def read_config_file(config_file):
     d.update(read_augment_keys(lambda key, dflt: cp.get(_TRAINING, key, fallback=dflt)))
     d.update(read_lm_keys(lambda key, dflt: cp.get(_LM, key, fallback=dflt)))
     d.update(read_long_audio_keys(lambda key, dflt: cp.get(_GENERAL, key, fallback=dflt)))
+    d.update(read_decode_keys(lambda key, dflt: cp.get(_GENERAL, key, fallback=dflt)))
     return d
 
 
@@ -179,6 +180,22 @@ def read_long_audio_keys(get):
             raise ValueError("%s must be %s, not %r" % (key, "an integer" if kind is int else "a decimal", text))
         d[key] = check_range(key, v, lo, hi)
     return d
+
+
+def read_decode_keys(get):
+    """Blank-frame skipping in front of every beam decoder ([general]; ops.ctc_blank_skip): decode_blank_skip is 0 (off, the default:
+    the decoders read every frame, nothing is launched or allocated) or the blank probability, above 0.5 and at most 1, at and above
+    which a frame is skippable; of every run of skippable frames the first is kept.  0.95 .. 0.99 are the customary values; nobody
+    has tuned them on a corpus here.  NOT structural: a checkpoint is usable either way.  get(key, default) -> text; a bad value
+    raises ValueError naming the range."""
+    text = get("decode_blank_skip", "0")
+    try:
+        v = float(str(text).strip() or "0")
+    except (ValueError, OverflowError):
+        v = float("nan")
+    if not (v == 0.0 or 0.5 < v <= 1.0):
+        raise ValueError("decode_blank_skip : %r -- 0 (off) or a blank probability above 0.5 and at most 1" % (text,))
+    return {"decode_blank_skip": v}
 
 
 _LM = "lm_network_params"

@@ -118,6 +118,12 @@ class LmStepPlanInfo(C.Structure):     # amdspeech_lm_step_plan_info (include/am
                                        "out_row_tile", "out_row_tiles", "v_max")]
 
 
+class BlankSkipPlanInfo(C.Structure):     # amdspeech_ctc_blank_skip_plan_info (include/amdspeech.h): the kernels and launch geometry of a blank-skipping call, read-only
+    _fields_ = [(n, C.c_int) for n in ("kernel", "words_per_lane", "vec", "c_min", "c_max", "rows_threads", "rows_per_workgroup", "rows_grid",
+                                       "t_chunk", "chunks", "scan_threads", "scan_grid", "gather_threads", "gather_grid", "launches",
+                                       "workspace_bytes")]
+
+
 # amdspeech_lm_step_fn (include/amdspeech.h): (user, n, parent, token, dest, logq) -> status, called on the thread that called the decoder
 LM_STEP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float))
 
@@ -127,6 +133,7 @@ GEMM_GROUP_MAX = 10                                                             
 CTC_KERNELS = ("wave", "shift", "pair", "edge")      # AMDSPEECH_CTC_KERNEL_* (include/amdspeech.h)
 LSTM_PATHS = ("flow", "big1", "big", "hoist", "diag", "diag_bf3")      # AMDSPEECH_LSTM_PATH_* (include/amdspeech.h)
 XENT_KERNELS = ("wave", "block")      # AMDSPEECH_XENT_KERNEL_* (include/amdspeech.h)
+BLANK_SKIP_KERNELS = ("wave", "block")      # AMDSPEECH_BLANK_SKIP_KERNEL_* (include/amdspeech.h)
 LM_STEP_KERNELS = ("mfma16",)      # AMDSPEECH_LM_STEP_KERNEL_* (include/amdspeech.h)
 FEATURE_NORM_MODES = ("none", "utterance", "global")      # AMDSPEECH_FEATURE_NORM_* (include/amdspeech.h)
 LSTM_ARMED, LSTM_ARM_NEXT, LSTM_SAME_WS, LSTM_PER_DIAGONAL, LSTM_INJECT_TIMEOUT = 1, 2, 4, 8, 16      # amdspeech_lstm_desc.flags (include/amdspeech.h)
@@ -285,6 +292,9 @@ PROTOTYPES = {
     "amdspeech_lm_step_pool_bytes": (_SZ, [_I, _I, _I]),
     "amdspeech_ctc_beam_search_fused_slots": (_I, [_I, _I]),
     "amdspeech_ctc_beam_search_host_fused": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, LM_STEP_FN, _P, _P, _P, _P, _P, _I]),
+    "amdspeech_ctc_blank_skip_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "amdspeech_ctc_blank_skip_plan": (_I, [_I, _I, _I, C.POINTER(BlankSkipPlanInfo)]),
+    "amdspeech_ctc_blank_skip": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -886,6 +886,53 @@ def ctc_beam_search_nbest(logits, lengths, n_best, beam_width=100, merge_repeate
     return ids, out_len, logp, n_found
 
 
+def ctc_blank_skip_plan(T, B, C_):
+    """The kernels ctc_blank_skip takes for a shape (amdspeech.h: amdspeech_ctc_blank_skip_plan), as a dict of ints with "kernel" as
+    a name ("wave", "block"); c_min .. c_max is the range of C on the same row kernel, t_chunk the frames per step of the
+    per-utterance scan.  Read-only, no device needed; a shape the call refuses raises here too."""
+    info = _l.BlankSkipPlanInfo()
+    _l.check(_l.load().amdspeech_ctc_blank_skip_plan(int(T), int(B), int(C_), C.byref(info)), "ctc_blank_skip_plan")
+    out = _plan_dict(info)
+    out["kernel"] = _l.BLANK_SKIP_KERNELS[out["kernel"]]
+    return out
+
+
+_blank_skip_ws = {}
+
+
+def ctc_blank_skip(logits, lengths, threshold, out=None, new_lengths=None, src_frame=None, blank_logp=None):
+    """Blank-frame skipping in front of a beam decoder (amdspeech.h: amdspeech_ctc_blank_skip).  logits float32 [T,B,C] and lengths
+    int32 [B] on the device; threshold: the blank probability in (0, 1] at and above which a frame is skippable (the library gets
+    its log).  Of every run of skippable frames the first is kept.  Returns (compact [T,B,C]: the kept frames of every utterance
+    moved to the front, zeros behind them; new_lengths int32 [B]; src_frame int32 [B,T]: the source frame of every kept one, -1
+    behind them).  blank_logp: an optional float32 [T,B] that receives the blank log-posterior of every frame inside its row."""
+    import math
+    T, B, C_ = _chk_f32_3d("ctc_blank_skip", logits, "[T, B, C]")
+    _chk_i32(lengths)
+    _chk_f32(out, blank_logp)
+    threshold = float(threshold)
+    if not 0.0 < threshold <= 1.0:
+        raise ValueError("ctc_blank_skip: threshold %r is not a probability in (0, 1]" % threshold)
+    if lengths.numel() != B:
+        raise ValueError("ctc_blank_skip: %d lengths for %d utterances" % (lengths.numel(), B))
+    dev = logits.device
+    if out is None:
+        out = torch.empty_like(logits)
+    if new_lengths is None:
+        new_lengths = torch.empty(B, device=dev, dtype=torch.int32)
+    if src_frame is None:
+        src_frame = torch.empty(B, T, device=dev, dtype=torch.int32)
+    _chk_i32(new_lengths, src_frame)
+    if tuple(out.shape) != (T, B, C_) or new_lengths.numel() != B or tuple(src_frame.shape) != (B, T) \
+            or (blank_logp is not None and tuple(blank_logp.shape) != (T, B)):
+        raise ValueError("ctc_blank_skip: an output does not fit T = %d, B = %d, C = %d" % (T, B, C_))
+    lib = _l.load()
+    ws = _cached_ws(_blank_skip_ws, (T, B, C_, dev), lambda: max(int(lib.amdspeech_ctc_blank_skip_workspace_bytes(T, B, C_)), 16))
+    _l.check(lib.amdspeech_ctc_blank_skip(_stream(), _p(logits), _p(lengths), T, B, C_, math.log(threshold), _p(out), _p(new_lengths),
+                                          _p(src_frame), _p(blank_logp), _p(ws)), "ctc_blank_skip")
+    return out, new_lengths, src_frame
+
+
 # --------------------------------------------------------------------- optimiser
 _optim_ws = {}
 

@@ -205,6 +205,7 @@ def _set_model_options(model, hyper_params):
     model.conv = conv_option(hyper_params)
     model.sync_batch_norm = hyper_params.get("sync_batch_norm", False)
     model.spec_augment = hyper_params.get("spec_augment")       # (build_audio_processor; only run_step with gradients masks)
+    model.decode_blank_skip = hyper_params.get("decode_blank_skip", 0.0)      # (every beam decoder's input; 0: the decoders read every frame)
     opts = pipeline_options(hyper_params)                       # (evaluate_full builds its AudioProcessor from these five)
     for name in ("frame_stack", "frame_skip", "feature_norm", "feature_norm_variance", "feature_stats"):
         setattr(model, name, opts[name])
