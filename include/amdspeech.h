@@ -1344,6 +1344,106 @@ int amdspeech_ctc_blank_skip_plan(int T, int B, int C, amdspeech_ctc_blank_skip_
 int amdspeech_ctc_blank_skip(void* stream, const float* logits, const int* lengths, int T, int B, int C, float log_threshold,
                              float* out_logits, int* out_lengths, int* src_frame, float* blank_logp, void* ws);
 
+/* ------------------------------------------------------------ transducer ---
+ * The transducer (RNN-T) objective: label preparation, the joint network forward and backward, and the lattice loss with its
+ * gradient (no reference counterpart: an opt-in deviation; nothing of it is called by a CTC model).  transducer.hip; DESIGN.md 4.10.
+ * All pointers are device memory; the calls are stream-ordered, do not synchronise, do not allocate and use no floating-point
+ * atomics: two runs give the same bits.  Every offset into a lattice tensor is computed in 64 bits.
+ *   f        float [T][B][J]       the encoder projection, time-major
+ *   g        float [U+1][B][J]     the prediction projection, time-major
+ *   w_out    float [J][C], b_out float [C]
+ *   lattice tensors (logits, dlogits)   float [B][T][U+1][C]
+ *   lengths  int32 [B]; T_b = min(max(lengths[b], 0), T).   n int32 [B]: the target count n_b of row b (clamped to 0 .. U).
+ * Blank is class C-1.  Node (b, t, u) is LIVE when t < T_b and u <= n_b.
+ * Limits, the same for every call: J a multiple of 16 in 16 .. 1024, 2 <= C <= 256, 1 <= U <= 2559, T >= 1, B >= 1,
+ * B T (U+1) C < 2^31.  Anything else is AMDSPEECH_EINVAL (a bad argument) or AMDSPEECH_EUNSUPPORTED (a size limit of the
+ * kernels: J > 1024, C > 256, U > 2559, the product) with a message that names the limit, and nothing is launched.
+ *
+ * amdspeech_rnnt_targets: the label sparsification of amdspeech_ctc_loss_fwd_bwd on dense_labels [B][U] -- zeros are dropped, the
+ *   target is every kept label before the first one >= C-1 -- WITHOUT its empty-row and required-time rules: an empty target is
+ *   n_b = 0, a valid row.  Negative ids are dropped with the zeros (every target is a class in 1 .. C-2: ln P is finite).  Writes targets [B][U] (0 past n_b), n [B], the prediction network's token rows tok [B][U+2] =
+ *   [C-1, y_1 .. y_n, C-1, ...] (the start symbol is the EOS id, as the language model has it) and tok_len [B] = n_b + 1.
+ * amdspeech_rnnt_joint_fwd: logits[b,t,u,:] = tanh(f[t,b,:] + g[u,b,:]) . w_out + b_out on every live node, exact f32 on
+ *   v_mfma_f32_16x16x4_f32.  z = tanh(.) is formed in registers from LDS strips of f and g and is never written to memory.  The k
+ *   order of a node's sum is a fixed function of J, so a node's bits do not depend on B, T, U or its neighbours.  Dead nodes are
+ *   not written; nothing downstream reads them.
+ * amdspeech_rnnt_loss_fwd_bwd: row log-softmax in float32 (the row maximum subtracted), alpha and beta over the lattice in log
+ *   space with a float64 state, walked by anti-diagonals, the two walks of an utterance concurrently;
+ *     loss[b] = -ln P = -(alpha(T_b-1, n_b) + lp_blank(T_b-1, n_b)),
+ *     dlogits[b,t,u,v] = p_v gamma - [v = C-1] exp(alpha + lp_blank + beta(t+1,u) - ln P) - [v = y_{u+1}, u < n_b] exp(alpha +
+ *     lp_y + beta(t,u+1) - ln P),   gamma = exp(alpha + beta - ln P) at (t,u), beta past the terminal node 0
+ *   = d(sum_b loss_b)/dlogits.  dlogits may BE logits (a row is read completely before it is written).  Dead nodes get zero rows;
+ *   a row with T_b = 0 gets loss 0 and no gradient.  ws: amdspeech_rnnt_workspace_bytes (any valid J), 256-byte aligned.
+ * amdspeech_rnnt_joint_bwd: with dz = (dlogits . w_out^T) (1 - z^2), z recomputed on the chip:  dw_out += z^T . dlogits,
+ *   db_out += sum dlogits (accumulated, as amdspeech_linear_bwd),  df[t,b,:] = sum_u dz,  dg[u,b,:] = sum_t dz (overwritten; rows
+ *   without a live node are zero).  Neither z nor dz is written to memory: df is complete inside a workgroup, dg leaves one
+ *   partial per chunk of frames and dw_out / db_out one per workgroup, added by a second pass in a fixed order.  Reads the dlogits
+ *   of live nodes only.  ws: the same workspace.
+ * amdspeech_rnnt_workspace_bytes (0 for a bad shape), with N = B T (U+1) and every region rounded up to 256 bytes:
+ *     4 N + 4 N (blank / label log-probabilities) + 8 N + 8 N (alpha, beta) + 8 B (ln P)
+ *     + 4 bwd_t_chunks (U+1) B J (dg partials) + 4 bwd_items J C + 4 bwd_items C (dw_out / db_out partials)
+ *   -- bwd_t_chunks = ceil(T / bwd_t_chunk) is at most 8 up to T = 1024 (no term grows with N J there); beyond, bwd_t_chunk stays
+ *   128 frames and the dg partials are N J / 128 words.
+ * amdspeech_rnnt_plan: a READ-ONLY view of the plan the launches themselves read (one function decides for both); no device is
+ *   needed and nothing is launched.
+ *   threads                      256, every joint and row kernel
+ *   col_tiles, c_min .. c_max    column tiles of 16 classes of the joint kernels, and the range of C with the same instantiation
+ *   j_min .. j_max               the range of J with the same instantiation (J is a loop count: all of it)
+ *   fwd_t_tile, fwd_u_tile, fwd_k_chunk   joint_fwd: 4 frames (one per wave) x 16 / 32 / 64 prefix positions per workgroup, 32 k per
+ *                                LDS chunk;  fwd_t_tiles, fwd_u_tiles, fwd_grid = their product times B;  fwd_lds_bytes
+ *   rows_per_workgroup, rows_grid   the log-probability and gradient kernels: one wavefront per node
+ *   rec_kernel, rec_threads, rec_states, u_min .. u_max   the recursion kernel (AMDSPEECH_RNNT_REC_* below), its threads per
+ *                                (utterance, direction), the lattice columns a thread holds, and the range of U on that kernel;
+ *                                rec_grid = 2 B;  rec_lds_bytes
+ *   bwd_t_tile, bwd_u_tile       joint_bwd: 4 frames (one per wave) x 16 prefix positions per step
+ *   bwd_k_slice, bwd_k_slices    the slice of J a workgroup owns (64 / 32 / 16) and their number
+ *   bwd_t_chunk, bwd_t_chunks    frames per workgroup (32 .. 128) and the chunks of T;  bwd_items = B bwd_t_chunks;
+ *                                bwd_grid = bwd_items bwd_k_slices;  bwd_lds_bytes
+ *   dg_terms, dw_terms           partials the second pass adds per element;  reduce_dg_grid, reduce_dw_grid
+ *   launches_fwd, launches_loss, launches_bwd   1, 3, 3                                                                        */
+#define AMDSPEECH_RNNT_REC_WAVE 0    /* one wavefront per (utterance, direction): U <= 63 */
+#define AMDSPEECH_RNNT_REC_BLOCK1 1  /* 256 threads, one lattice column each: U <= 255 */
+#define AMDSPEECH_RNNT_REC_BLOCK4 2  /* 256 threads, four columns each: U <= 1023 */
+#define AMDSPEECH_RNNT_REC_BLOCK10 3 /* 256 threads, ten columns each: U <= 2559 */
+typedef struct amdspeech_rnnt_plan_info {
+    int threads, col_tiles, c_min, c_max, j_min, j_max, fwd_t_tile, fwd_u_tile, fwd_k_chunk, fwd_t_tiles, fwd_u_tiles, fwd_grid,
+        fwd_lds_bytes, rows_per_workgroup, rows_grid, rec_kernel, rec_threads, rec_states, u_min, u_max, rec_grid, rec_lds_bytes,
+        bwd_t_tile, bwd_u_tile, bwd_k_slice, bwd_k_slices, bwd_t_chunk, bwd_t_chunks, bwd_items, bwd_grid, bwd_lds_bytes, dg_terms,
+        dw_terms, reduce_dg_grid, reduce_dw_grid, launches_fwd, launches_loss, launches_bwd;
+} amdspeech_rnnt_plan_info;
+int amdspeech_rnnt_plan(int T, int B, int U, int J, int C, amdspeech_rnnt_plan_info* out);
+size_t amdspeech_rnnt_workspace_bytes(int T, int B, int U, int J, int C);
+int amdspeech_rnnt_targets(void* stream, const int* dense_labels, int B, int U, int C, int* targets, int* n, int* tok,
+                           int* tok_len);
+int amdspeech_rnnt_joint_fwd(void* stream, const float* f, const float* g, const float* w_out, const float* b_out,
+                             const int* lengths, const int* n, int T, int B, int U, int J, int C, float* logits);
+int amdspeech_rnnt_loss_fwd_bwd(void* stream, const float* logits, const int* targets, const int* n, const int* lengths,
+                                int T, int B, int U, int C, float* loss, float* dlogits, void* ws);
+int amdspeech_rnnt_joint_bwd(void* stream, const float* dlogits, const float* f, const float* g, const float* w_out,
+                             const int* lengths, const int* n, int T, int B, int U, int J, int C, float* df, float* dg,
+                             float* dw_out, float* db_out, void* ws);
+/* The L layer launches of amdspeech_lm_step without the output launch (the same code, not a copy): the same slot contract and the
+ * same bits in the pool.  What a decoder calls that reads the top layer's h' itself (the transducer's prediction network).      */
+int amdspeech_lm_step_state(void* stream, int N, const int* parent, const int* token, const int* dest,
+                            float* pool_h, float* pool_c, int n_slots, int L, int H, int V,
+                            const float* input_w, const float* input_b, const float* kernel_0, long kernel_stride,
+                            const float* bias_0, long bias_stride);
+
+/* amdspeech_rnnt_greedy_step: ONE iteration of time-synchronous greedy transducer decoding for B rows in lockstep.  Row b holds a
+ * frame index t_idx[b], an emitted count m[b] and its current prediction-network slot slot[b] (2 b or 2 b + 1 of the pool
+ * pool_h [2 B][L][H]), all in device arrays.  The call forms g_b = pool_h[slot_b][L-1] . w_pred + b_pred (w_pred [H][J]), the joint
+ * row tanh(f[t_b, b, :] + g_b) . w_out + b_out, and its argmax over C, ties to the smallest class (every sum in increasing k).
+ *   blank (C-1):  t_idx[b] += 1;  dest[b] = -1
+ *   otherwise:    ids[b][m_b] = class, m[b] += 1, and (parent, token, dest)[b] = (slot_b, class, the row's other slot) for the
+ *                 amdspeech_lm_step_state call that follows; slot[b] becomes dest[b]
+ * A row is finished when t_b = T_b or m_b = U: a no-op that writes dest -1, and by the lm_step contract such a row is not
+ * written.  The host launches T_run + U iterations (each followed by amdspeech_lm_step_state on B rows) and reads nothing in
+ * between.  ids int32 [B][U].  The limits of the other transducer calls, 1 <= L <= 8, 2 B L H < 2^31.                         */
+int amdspeech_rnnt_greedy_step(void* stream, const float* f, const int* lengths, int T, int B, int U, int J, int C,
+                               const float* pool_h, int L, int H, const float* w_pred, const float* b_pred,
+                               const float* w_out, const float* b_out, int* t_idx, int* m, int* slot, int* ids, int* parent,
+                               int* token, int* dest);
+
 #ifdef __cplusplus
 }
 #endif

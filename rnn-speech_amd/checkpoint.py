@@ -15,12 +15,18 @@ TF_NAMES = {"input_w": "Input_Layer/input_w", "input_b": "Input_Layer/input_b",
             "output_w": "Output_layer/output_w", "output_b": "Output_layer/output_b",
             "lookahead_w": "Lookahead_Layer/lookahead_w",       # (the row convolution's taps; only a model with lookahead > 0 has them)
             "conv_w": "Conv_Layer/conv_w", "conv_b": "Conv_Layer/conv_b"}       # (the front convolution; only a model with conv_channels > 0)
+# the parts of a transducer's store: the encoder and the prediction network keep their own names under a scope
+PART_SCOPES = {"encoder/": "Encoder/", "prediction/": "Prediction/"}
+TF_NAMES.update({"joint_w": "Joint_Layer/joint_w", "joint_b": "Joint_Layer/joint_b"})
 
 
 def tf_name(name, layerwise=False):
     """ParamLayout name -> TensorFlow variable name: the plain stack (tf.nn.dynamic_rnn), the `bw_` stack of the "top" mode
     (tf.nn.bidirectional_dynamic_rnn) and, with `layerwise`, both stacks of the "layer" mode
     (tf.contrib.rnn.stack_bidirectional_dynamic_rnn)."""
+    for prefix, scope in PART_SCOPES.items():       # a part of a composed store (transducer.TransducerEngine)
+        if name.startswith(prefix):
+            return scope + tf_name(name[len(prefix):], layerwise)
     if name in TF_NAMES:
         return TF_NAMES[name]
     d = "bw" if name.startswith("bw_") else "fw"

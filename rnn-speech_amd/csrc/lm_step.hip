@@ -336,13 +336,15 @@ extern "C" size_t amdspeech_lm_step_pool_bytes(int n_slots, int L, int H) {
     return (size_t)n_slots * L * H * sizeof(float);
 }
 
-extern "C" int amdspeech_lm_step(void* stream, int N, const int* parent, const int* token, const int* dest, float* pool_h, float* pool_c,
-                                 int n_slots, int L, int H, int V, const float* input_w, const float* input_b, const float* kernel_0,
-                                 long kernel_stride, const float* bias_0, long bias_stride, const float* output_w,
-                                 const float* output_b, float* logq) {
+// The L layer launches, and the output launch when `output` is set (amdspeech_lm_step; amdspeech_lm_step_state stops at the state)
+static int lm_step_launch(void* stream, int N, const int* parent, const int* token, const int* dest, float* pool_h, float* pool_c,
+                          int n_slots, int L, int H, int V, const float* input_w, const float* input_b, const float* kernel_0,
+                          long kernel_stride, const float* bias_0, long bias_stride, bool output, const float* output_w,
+                          const float* output_b, float* logq) {
     StepPlan p;
     if (int rc = plan_lm_step(N, L, H, V, &p)) return rc;
-    AS_CHECK_ARG(parent && token && dest && pool_h && pool_c && input_w && input_b && kernel_0 && bias_0 && output_w && output_b && logq,
+    AS_CHECK_ARG(parent && token && dest && pool_h && pool_c && input_w && input_b && kernel_0 && bias_0 &&
+                     (!output || (output_w && output_b && logq)),
                  "lm_step: null pointer");
     AS_CHECK_ARG(n_slots >= 1 && (long)n_slots * L * H < (1L << 31), "lm_step: n_slots = %d must be positive with n_slots * L * H below 2^31",
                  n_slots);
@@ -360,6 +362,7 @@ extern "C" int amdspeech_lm_step(void* stream, int N, const int* parent, const i
     a.pool_h = pool_h; a.pool_c = pool_c;
     a.input_w = input_w; a.input_b = input_b; a.output_w = output_w; a.output_b = output_b;
     a.logq = logq;
+    a.layer = 0; a.kernel = kernel_0; a.bias = bias_0;
     for (int l = 0; l < L; ++l) {
         a.layer = l;
         a.kernel = kernel_0 + (size_t)l * kernel_stride;
@@ -369,7 +372,23 @@ extern "C" int amdspeech_lm_step(void* stream, int N, const int* parent, const i
         else hipLaunchKernelGGL(lm_step_layer_kernel<2>, grid, block, 0, s, a);
         AS_CHECK_LAUNCH();
     }
+    if (!output) return AMDSPEECH_OK;
     hipLaunchKernelGGL(lm_step_out_kernel, dim3(p.out_row_tiles), dim3(p.threads), 0, s, a);
     AS_CHECK_LAUNCH();
     return AMDSPEECH_OK;
+}
+
+extern "C" int amdspeech_lm_step(void* stream, int N, const int* parent, const int* token, const int* dest, float* pool_h, float* pool_c,
+                                 int n_slots, int L, int H, int V, const float* input_w, const float* input_b, const float* kernel_0,
+                                 long kernel_stride, const float* bias_0, long bias_stride, const float* output_w,
+                                 const float* output_b, float* logq) {
+    return lm_step_launch(stream, N, parent, token, dest, pool_h, pool_c, n_slots, L, H, V, input_w, input_b, kernel_0, kernel_stride, bias_0,
+                          bias_stride, true, output_w, output_b, logq);
+}
+
+extern "C" int amdspeech_lm_step_state(void* stream, int N, const int* parent, const int* token, const int* dest, float* pool_h,
+                                       float* pool_c, int n_slots, int L, int H, int V, const float* input_w, const float* input_b,
+                                       const float* kernel_0, long kernel_stride, const float* bias_0, long bias_stride) {
+    return lm_step_launch(stream, N, parent, token, dest, pool_h, pool_c, n_slots, L, H, V, input_w, input_b, kernel_0, kernel_stride, bias_0,
+                          bias_stride, false, nullptr, nullptr, nullptr);
 }

@@ -115,9 +115,15 @@ class ParamStore(object):
     of the engines built on it.  A subclass sets T (its padded length) and B, H, its logits / dlogits buffers and its recurrence
     driver `stack` (stacks.py), and says what it is in _describe()."""
 
-    def __init__(self, layout, device):
+    def __init__(self, layout, device, storage=None):
+        """storage: the four flat buffers (params, grads, adam_m, adam_v) of layout.total floats each, for a store that is a part
+        of a larger one (transducer.TransducerEngine: one clip and one Adam over every part); None allocates them."""
         self.layout, self.device = layout, torch.device(device)
-        self.params, self.grads, self.adam_m, self.adam_v = (torch.zeros(layout.total, device=self.device) for _ in range(4))
+        if storage is None:
+            storage = tuple(torch.zeros(layout.total, device=self.device) for _ in range(4))
+        if len(storage) != 4 or any(t.numel() != layout.total or not t.is_contiguous() for t in storage):
+            raise ValueError("storage must be four contiguous flat buffers of %d floats" % layout.total)
+        self.params, self.grads, self.adam_m, self.adam_v = storage
         self.norm = torch.zeros(1, device=self.device)
         self.adam_step = 0
 
@@ -227,7 +233,7 @@ class ParamStore(object):
 class Engine(ParamStore):
     def __init__(self, num_layers, hidden, input_dim, num_labels, batch_size, max_T, max_U,
                  device="cuda", seed=1234, normalization=False, precision="f32", bidirectional=False,
-                 sync_batch_norm=False, bidirectional_mode="top", lookahead=0, conv=None):
+                 sync_batch_norm=False, bidirectional_mode="top", lookahead=0, conv=None, storage=None):
         if not torch.cuda.is_available():
             raise RuntimeError("rnn_speech_amd needs a ROCm GPU (MI355X); there is no CPU path")
         # strided time-frequency convolution between the features and the input Linear (ops.conv2d_fwd; no reference counterpart,
@@ -266,7 +272,7 @@ class Engine(ParamStore):
                              "context; a bidirectional stack already reads the whole utterance" % self.lookahead)
         ParamStore.__init__(self, ParamLayout(num_layers, hidden, input_dim, num_labels, bidirectional=self.bidirectional,
                                               bidirectional_mode="layer" if self.layerwise else "top", lookahead=self.lookahead,
-                                              conv=self.conv), device)
+                                              conv=self.conv), device, storage)
         if precision not in PRECISIONS:
             raise ValueError("precision must be 'f32' (exact, default), 'bf16x3' (split-precision MFMA) or 'bf16' (plain bf16 "
                              "operands, f32 accumulation and master weights)")

@@ -18,9 +18,12 @@ _ACOUSTIC, _GENERAL, _TRAINING, _LOGGING = "acoustic_network_params", "general",
 _STRUCTURAL = ("num_layers", "hidden_size", "signal_processing", "language", "n_mfcc", "sample_rate", "bidirectional",
                "bidirectional_mode", "frame_stack", "frame_skip", "feature_norm", "feature_norm_variance", "lookahead_context",
                "conv_channels", "conv_kernel", "conv_stride")
+# ... and the training objective with the transducer's sizes (a list of its own: it names a second and a third network)
+_STRUCTURAL_OBJECTIVE = ("objective", "transducer_joint_size", "transducer_pred_layers", "transducer_pred_hidden")
 _STRUCTURAL_DEFAULTS = {"signal_processing": "mfcc", "language": "", "n_mfcc": 20, "sample_rate": 22050, "bidirectional": False,
                         "bidirectional_mode": "top", "frame_stack": 1, "frame_skip": 1, "feature_norm": "none", "feature_norm_variance": True,
-                        "lookahead_context": 0, "conv_channels": 0, "conv_kernel": (11, 21), "conv_stride": (2, 2)}
+                        "lookahead_context": 0, "conv_channels": 0, "conv_kernel": (11, 21), "conv_stride": (2, 2),
+                        "objective": "ctc", "transducer_joint_size": 512, "transducer_pred_layers": 1, "transducer_pred_hidden": 0}
 CONV_CHANNELS = (0, 16, 32, 48, 64)
 
 
@@ -81,6 +84,9 @@ def read_config_file(config_file):
     # frequency, both odd; conv_stride "st, sf".  The time stride is the learned form of frame_stack / frame_skip: refused with them
     d.update(read_conv_keys(lambda key, dflt: cp.get(_ACOUSTIC, key, fallback=dflt), d["signal_processing"], d["n_mfcc"],
                             d["frame_stack"], d["frame_skip"]))
+    # the training objective: ctc (the reference's, the default: nothing of the transducer is loaded, launched or allocated) |
+    # transducer (rnn_speech_amd/transducer.py: a prediction network and a joint network trained with the encoder)
+    d.update(read_objective_keys(lambda key, dflt: cp.get(_ACOUSTIC, key, fallback=dflt)))
     # feature normalisation between the front end and the frame stacking (ops.feature_norm): none (the reference's behaviour) |
     # utterance (mean / variance of the utterance itself) | global (of the training corpus, from the file feature_norm_stats names,
     # which `stt.py --feature_stats` writes).  feature_norm_variance False: means only
@@ -118,6 +124,24 @@ def read_config_file(config_file):
     d.update(read_long_audio_keys(lambda key, dflt: cp.get(_GENERAL, key, fallback=dflt)))
     d.update(read_decode_keys(lambda key, dflt: cp.get(_GENERAL, key, fallback=dflt)))
     return d
+
+
+def read_objective_keys(get):
+    """objective : ctc | transducer and the transducer's three sizes ([acoustic_network_params], all structural):
+    transducer_joint_size (a multiple of 16 in 16 .. 1024, default 512), transducer_pred_layers (1 .. 8, default 1),
+    transducer_pred_hidden (a multiple of 16 in 16 .. 4096; 0, the default, stands for hidden_size).  With objective : ctc the
+    sizes are only checked."""
+    objective = str(get("objective", "ctc")).strip()
+    if objective not in ("ctc", "transducer"):
+        raise ValueError("objective must be 'ctc' or 'transducer', not %r" % objective)
+    joint = check_range("transducer_joint_size", int(get("transducer_joint_size", 512)), 16, 1024)
+    if joint % 16:
+        raise ValueError("transducer_joint_size : %d must be a multiple of 16" % joint)
+    layers = check_range("transducer_pred_layers", int(get("transducer_pred_layers", 1)), 1, 8)
+    hidden = check_range("transducer_pred_hidden", int(get("transducer_pred_hidden", 0)), 0, 4096)
+    if hidden % 16:
+        raise ValueError("transducer_pred_hidden : %d must be a multiple of 16 (0: hidden_size)" % hidden)
+    return {"objective": objective, "transducer_joint_size": joint, "transducer_pred_layers": layers, "transducer_pred_hidden": hidden}
 
 
 def read_conv_keys(get, signal_processing="fbank", n_mfcc=20, frame_stack=1, frame_skip=1):
@@ -340,6 +364,6 @@ class HyperParameterHandler(object):
         old = self.get_params()
         for k, v in _STRUCTURAL_DEFAULTS.items():     # compatibility defaults (older pickles, the reference's own)
             old.setdefault(k, v)
-        return any(old[k] != new_params.get(k, _STRUCTURAL_DEFAULTS.get(k)) for k in _STRUCTURAL)
+        return any(old[k] != new_params.get(k, _STRUCTURAL_DEFAULTS.get(k)) for k in _STRUCTURAL + _STRUCTURAL_OBJECTIVE)
 
     read_config_file = staticmethod(read_config_file)

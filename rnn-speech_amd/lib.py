@@ -124,6 +124,15 @@ class BlankSkipPlanInfo(C.Structure):     # amdspeech_ctc_blank_skip_plan_info (
                                        "workspace_bytes")]
 
 
+class RnntPlanInfo(C.Structure):     # amdspeech_rnnt_plan_info (include/amdspeech.h): the instantiations and launch geometry of the transducer calls, read-only
+    _fields_ = [(n, C.c_int) for n in ("threads", "col_tiles", "c_min", "c_max", "j_min", "j_max", "fwd_t_tile", "fwd_u_tile", "fwd_k_chunk",
+                                       "fwd_t_tiles", "fwd_u_tiles", "fwd_grid", "fwd_lds_bytes", "rows_per_workgroup", "rows_grid",
+                                       "rec_kernel", "rec_threads", "rec_states", "u_min", "u_max", "rec_grid", "rec_lds_bytes", "bwd_t_tile",
+                                       "bwd_u_tile", "bwd_k_slice", "bwd_k_slices", "bwd_t_chunk", "bwd_t_chunks", "bwd_items", "bwd_grid",
+                                       "bwd_lds_bytes", "dg_terms", "dw_terms", "reduce_dg_grid", "reduce_dw_grid", "launches_fwd",
+                                       "launches_loss", "launches_bwd")]
+
+
 # amdspeech_lm_step_fn (include/amdspeech.h): (user, n, parent, token, dest, logq) -> status, called on the thread that called the decoder
 LM_STEP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float))
 
@@ -134,6 +143,7 @@ CTC_KERNELS = ("wave", "shift", "pair", "edge")      # AMDSPEECH_CTC_KERNEL_* (i
 LSTM_PATHS = ("flow", "big1", "big", "hoist", "diag", "diag_bf3")      # AMDSPEECH_LSTM_PATH_* (include/amdspeech.h)
 XENT_KERNELS = ("wave", "block")      # AMDSPEECH_XENT_KERNEL_* (include/amdspeech.h)
 BLANK_SKIP_KERNELS = ("wave", "block")      # AMDSPEECH_BLANK_SKIP_KERNEL_* (include/amdspeech.h)
+RNNT_REC_KERNELS = ("wave", "block1", "block4", "block10")      # AMDSPEECH_RNNT_REC_* (include/amdspeech.h)
 LM_STEP_KERNELS = ("mfma16",)      # AMDSPEECH_LM_STEP_KERNEL_* (include/amdspeech.h)
 FEATURE_NORM_MODES = ("none", "utterance", "global")      # AMDSPEECH_FEATURE_NORM_* (include/amdspeech.h)
 LSTM_ARMED, LSTM_ARM_NEXT, LSTM_SAME_WS, LSTM_PER_DIAGONAL, LSTM_INJECT_TIMEOUT = 1, 2, 4, 8, 16      # amdspeech_lstm_desc.flags (include/amdspeech.h)
@@ -295,6 +305,14 @@ PROTOTYPES = {
     "amdspeech_ctc_blank_skip_workspace_bytes": (_SZ, [_I, _I, _I]),
     "amdspeech_ctc_blank_skip_plan": (_I, [_I, _I, _I, C.POINTER(BlankSkipPlanInfo)]),
     "amdspeech_ctc_blank_skip": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    "amdspeech_rnnt_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(RnntPlanInfo)]),
+    "amdspeech_rnnt_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "amdspeech_rnnt_targets": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "amdspeech_rnnt_joint_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "amdspeech_rnnt_loss_fwd_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "amdspeech_rnnt_joint_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "amdspeech_rnnt_greedy_step": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "amdspeech_lm_step_state": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _L]),
 }
 
 _lib = None

@@ -1739,3 +1739,147 @@ def ctc_beam_search_fused(logits, lengths, step, n_best=0, beam_width=100, merge
         raise raised[0]
     _l.check(rc, "ctc_beam_search_host_fused")
     return (ids, out_len, logp) if n_best == 0 else (ids, out_len, logp, n_found)
+
+
+# ---------------------------------------------------------------- transducer
+_rnnt_ws = {}
+
+
+def rnnt_plan(T, B, U, J, C_):
+    """The instantiations and launch geometry of the transducer calls for a shape (amdspeech.h: amdspeech_rnnt_plan), as a dict of
+    ints with "rec_kernel" as a name ("wave", "block1", "block4", "block10") and "workspace_bytes" added.  Read-only, no device
+    needed; a refused shape raises."""
+    info = _l.RnntPlanInfo()
+    lib = _l.load()
+    _l.check(lib.amdspeech_rnnt_plan(int(T), int(B), int(U), int(J), int(C_), C.byref(info)), "rnnt_plan")
+    out = _plan_dict(info)
+    out["rec_kernel"] = _l.RNNT_REC_KERNELS[out["rec_kernel"]]
+    out["workspace_bytes"] = int(lib.amdspeech_rnnt_workspace_bytes(int(T), int(B), int(U), int(J), int(C_)))
+    return out
+
+
+def rnnt_workspace(T, B, U, J, C_, device):
+    """The (cached) workspace rnnt_loss_fwd_bwd and rnnt_joint_bwd share for a shape."""
+    lib = _l.load()
+    return _cached_ws(_rnnt_ws, (T, B, U, J, C_, device), lambda: max(int(lib.amdspeech_rnnt_workspace_bytes(T, B, U, J, C_)), 256))
+
+
+def rnnt_targets(dense_labels, C_):
+    """dense_labels int32 [B, U] -> (targets [B, U], n [B], tok [B, U+2], tok_len [B]) (amdspeech.h: amdspeech_rnnt_targets)."""
+    _chk_i32(dense_labels)
+    if dense_labels.dim() != 2:
+        raise ValueError("rnnt_targets: dense_labels must be [B, U]")
+    B, U = dense_labels.shape
+    dev = dense_labels.device
+    targets = torch.empty(B, U, device=dev, dtype=torch.int32)
+    n = torch.empty(B, device=dev, dtype=torch.int32)
+    tok = torch.empty(B, U + 2, device=dev, dtype=torch.int32)
+    tok_len = torch.empty(B, device=dev, dtype=torch.int32)
+    _l.check(_l.load().amdspeech_rnnt_targets(_stream(), _p(dense_labels), B, U, int(C_), _p(targets), _p(n), _p(tok), _p(tok_len)),
+             "rnnt_targets")
+    return targets, n, tok, tok_len
+
+
+def _rnnt_shapes(what, f, g, w_out):
+    _chk_f32(f, g, w_out)
+    if f.dim() != 3 or g.dim() != 3 or w_out.dim() != 2 or g.shape[1:] != f.shape[1:] or w_out.shape[0] != f.shape[2]:
+        raise ValueError("%s: f [T, B, J], g [U+1, B, J] and w_out [J, C] do not fit: %s %s %s"
+                         % (what, tuple(f.shape), tuple(g.shape), tuple(w_out.shape)))
+    T, B, J = f.shape
+    return T, B, g.shape[0] - 1, J, w_out.shape[1]
+
+
+def rnnt_joint_fwd(f, g, w_out, b_out, lengths, n, logits=None):
+    """logits [B, T, U+1, C] = tanh(f[t, b] + g[u, b]) . w_out + b_out on every live node (amdspeech.h: amdspeech_rnnt_joint_fwd);
+    dead nodes are not written."""
+    T, B, U, J, C_ = _rnnt_shapes("rnnt_joint_fwd", f, g, w_out)
+    _chk_f32(b_out, logits)
+    _chk_i32(lengths, n)
+    if b_out.numel() != C_ or lengths.numel() != B or n.numel() != B:
+        raise ValueError("rnnt_joint_fwd: b_out, lengths or n do not fit B = %d, C = %d" % (B, C_))
+    if logits is None:
+        logits = torch.empty(B, T, U + 1, C_, device=f.device, dtype=torch.float32)
+    elif logits.numel() != B * T * (U + 1) * C_:
+        raise ValueError("rnnt_joint_fwd: logits holds %d values, the lattice has %d" % (logits.numel(), B * T * (U + 1) * C_))
+    _l.check(_l.load().amdspeech_rnnt_joint_fwd(_stream(), _p(f), _p(g), _p(w_out), _p(b_out), _p(lengths), _p(n), T, B, U, J, C_,
+                                                _p(logits)), "rnnt_joint_fwd")
+    return logits
+
+
+def rnnt_loss_fwd_bwd(logits, targets, n, lengths, loss=None, dlogits=None, ws=None):
+    """The transducer loss [B] and dlogits [B, T, U+1, C] of logits (amdspeech.h: amdspeech_rnnt_loss_fwd_bwd); dlogits may be
+    `logits` itself."""
+    _chk_f32(logits, loss, dlogits)
+    _chk_i32(targets, n, lengths)
+    if logits.dim() != 4 or targets.dim() != 2 or targets.shape != (logits.shape[0], logits.shape[2] - 1):
+        raise ValueError("rnnt_loss_fwd_bwd: logits [B, T, U+1, C] and targets [B, U] do not fit: %s %s"
+                         % (tuple(logits.shape), tuple(targets.shape)))
+    B, T, U1, C_ = logits.shape
+    if n.numel() != B or lengths.numel() != B:
+        raise ValueError("rnnt_loss_fwd_bwd: n and lengths must have one entry per row")
+    if loss is None:
+        loss = torch.empty(B, device=logits.device, dtype=torch.float32)
+    if dlogits is None:
+        dlogits = torch.empty_like(logits)
+    if ws is None:
+        ws = rnnt_workspace(T, B, U1 - 1, 16, C_, logits.device)
+    _l.check(_l.load().amdspeech_rnnt_loss_fwd_bwd(_stream(), _p(logits), _p(targets), _p(n), _p(lengths), T, B, U1 - 1, C_, _p(loss),
+                                                   _p(dlogits), _p(ws)), "rnnt_loss_fwd_bwd")
+    return loss, dlogits
+
+
+def rnnt_joint_bwd(dlogits, f, g, w_out, lengths, n, dw_out, db_out, df=None, dg=None, ws=None):
+    """df [T, B, J] and dg [U+1, B, J] (overwritten), dw_out / db_out (accumulated) from dlogits (amdspeech.h:
+    amdspeech_rnnt_joint_bwd)."""
+    T, B, U, J, C_ = _rnnt_shapes("rnnt_joint_bwd", f, g, w_out)
+    _chk_f32(dlogits, dw_out, db_out, df, dg)
+    _chk_i32(lengths, n)
+    if dlogits.numel() != B * T * (U + 1) * C_ or dw_out.shape != w_out.shape or db_out.numel() != C_:
+        raise ValueError("rnnt_joint_bwd: dlogits, dw_out or db_out do not fit the lattice")
+    if df is None:
+        df = torch.empty_like(f)
+    if dg is None:
+        dg = torch.empty_like(g)
+    if df.shape != f.shape or dg.shape != g.shape:
+        raise ValueError("rnnt_joint_bwd: df / dg do not fit f / g")
+    if ws is None:
+        ws = rnnt_workspace(T, B, U, J, C_, f.device)
+    _l.check(_l.load().amdspeech_rnnt_joint_bwd(_stream(), _p(dlogits), _p(f), _p(g), _p(w_out), _p(lengths), _p(n), T, B, U, J, C_,
+                                                _p(df), _p(dg), _p(dw_out), _p(db_out), _p(ws)), "rnnt_joint_bwd")
+    return df, dg
+
+
+def lm_step_state(parent, token, dest, pool_h, pool_c, input_w, input_b, kernel_0, kernel_stride, bias_0, bias_stride, V):
+    """The layer launches of lm_step without the output layer (amdspeech.h: amdspeech_lm_step_state): the same bits in the pool."""
+    _chk_i32(parent, token, dest)
+    _chk_f32(pool_h, pool_c, input_w, input_b, kernel_0, bias_0)
+    N = parent.numel()
+    if token.numel() != N or dest.numel() != N:
+        raise ValueError("lm_step_state: parent, token and dest must have one entry per row")
+    if pool_h.dim() != 3 or pool_h.shape != pool_c.shape:
+        raise ValueError("lm_step_state: pool_h / pool_c must be [n_slots, L, H], got %s / %s" % (tuple(pool_h.shape), tuple(pool_c.shape)))
+    n_slots, L, H = pool_h.shape
+    if tuple(input_w.shape) != (V, H) or input_b.numel() != H or tuple(kernel_0.shape) != (2 * H, 4 * H) or bias_0.numel() != 4 * H:
+        raise ValueError("lm_step_state: the parameters do not fit L = %d, H = %d, V = %d" % (L, H, V))
+    _l.check(_l.load().amdspeech_lm_step_state(_stream(), N, _p(parent), _p(token), _p(dest), _p(pool_h), _p(pool_c), n_slots, L, H, int(V),
+                                               _p(input_w), _p(input_b), _p(kernel_0), int(kernel_stride or 0), _p(bias_0),
+                                               int(bias_stride or 0)), "lm_step_state")
+
+
+def rnnt_greedy_step(f, lengths, U, pool_h, w_pred, b_pred, w_out, b_out, t_idx, m, slot, ids, parent, token, dest):
+    """One iteration of greedy transducer decoding for the B rows of f [T, B, J] (amdspeech.h: amdspeech_rnnt_greedy_step); the
+    decoding state t_idx / m / slot [B], ids [B, U] and the (parent, token, dest) rows of the following lm_step_state call are
+    updated in place."""
+    _chk_f32(f, pool_h, w_pred, b_pred, w_out, b_out)
+    _chk_i32(lengths, t_idx, m, slot, ids, parent, token, dest)
+    T, B, J = f.shape
+    if pool_h.dim() != 3 or pool_h.shape[0] != 2 * B:
+        raise ValueError("rnnt_greedy_step: pool_h must be [2 B, L, H], got %s" % (tuple(pool_h.shape),))
+    _, L, H = pool_h.shape
+    C_ = b_out.numel()
+    if tuple(w_pred.shape) != (H, J) or b_pred.numel() != J or tuple(w_out.shape) != (J, C_) or tuple(ids.shape) != (B, U) \
+            or any(x.numel() != B for x in (lengths, t_idx, m, slot, parent, token, dest)):
+        raise ValueError("rnnt_greedy_step: the arguments do not fit B = %d, U = %d, J = %d, C = %d, H = %d" % (B, U, J, C_, H))
+    _l.check(_l.load().amdspeech_rnnt_greedy_step(_stream(), _p(f), _p(lengths), T, B, int(U), J, C_, _p(pool_h), L, H, _p(w_pred),
+                                                  _p(b_pred), _p(w_out), _p(b_out), _p(t_idx), _p(m), _p(slot), _p(ids), _p(parent),
+                                                  _p(token), _p(dest)), "rnnt_greedy_step")

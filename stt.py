@@ -197,6 +197,22 @@ def _model_length(hyper_params):
     return hyper_params.get("out_seq_length", -(-hyper_params["max_input_seq_length"] // pipeline_options(hyper_params)["frame_skip"]))
 
 
+def _acoustic_model(hyper_params, batch_size, training):
+    """The model class the `objective` key names, constructed; objective : ctc (the default) imports nothing of the transducer."""
+    args = (hyper_params["num_layers"], hyper_params["hidden_size"], batch_size, _model_length(hyper_params),
+            hyper_params["max_target_seq_length"], hyper_params["input_dim"], hyper_params["batch_normalization"],
+            hyper_params["char_map_length"])
+    if hyper_params.get("objective", "ctc") != "transducer":
+        return AcousticModel(*args)
+    from rnn_speech_amd import transducer
+    transducer.check_options(hyper_params, training)
+    model = transducer.TransducerModel(*args)
+    model.joint_size = hyper_params.get("transducer_joint_size", 512)
+    model.pred_layers = hyper_params.get("transducer_pred_layers", 1)
+    model.pred_hidden = hyper_params.get("transducer_pred_hidden", 0) or None
+    return model
+
+
 def _set_model_options(model, hyper_params):
     model.precision = hyper_params.get("precision", "f32")
     model.bidirectional = hyper_params.get("bidirectional", False)
@@ -212,10 +228,7 @@ def _set_model_options(model, hyper_params):
 
 
 def build_acoustic_training_rnn(sess, hyper_params, prog_params, train_set, test_set):
-    model = AcousticModel(hyper_params["num_layers"], hyper_params["hidden_size"], hyper_params["batch_size"],
-                          _model_length(hyper_params), hyper_params["max_target_seq_length"],
-                          hyper_params["input_dim"], hyper_params["batch_normalization"],
-                          hyper_params["char_map_length"])
+    model = _acoustic_model(hyper_params, hyper_params["batch_size"], True)
     ds_args = (hyper_params["batch_size"], hyper_params["max_input_seq_length"],
                hyper_params["max_target_seq_length"], hyper_params["signal_processing"], hyper_params["char_map"])
     _set_model_options(model, hyper_params)
@@ -340,10 +353,7 @@ def _train_loop(model, sess, step_args, rebuild, evaluate, ckpt_dir, epoch_limit
 
 
 def _forward_model(hyper_params, batch_size):
-    model = AcousticModel(hyper_params["num_layers"], hyper_params["hidden_size"], batch_size,
-                          _model_length(hyper_params), hyper_params["max_target_seq_length"],
-                          hyper_params["input_dim"], hyper_params["batch_normalization"],
-                          hyper_params["char_map_length"])
+    model = _acoustic_model(hyper_params, batch_size, False)
     _set_model_options(model, hyper_params)
     model.create_forward_rnn()
     model.initialize(None)
